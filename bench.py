@@ -34,6 +34,8 @@ sys.path.insert(0, ROOT)
 PEAK_F32_MFMA_TFLOPS = 157.3      # /opt/skills/guides/MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 PEAK_F16_MFMA_TFLOPS = 2500.0     # same guide: dense f16/bf16 MFMA
 Z, OM = 0.5, 0.3
+DUMP_BYTES = 60_000_000           # --dump-outputs: data bytes of all .npy files together (64 MB cap, headers included)
+DUMP_SEED = 4242
 
 
 def cpu_baseline(threads, tile_budget_s=100.0):
@@ -77,6 +79,25 @@ def cpu_baseline(threads, tile_budget_s=100.0):
     return out
 
 
+def dump_outputs(dirname, fields, rank, world):
+    """--dump-outputs: what the timed path returned in its last step, as DIR/<name>.npy (float32, shape (3, n)).  Every
+    field is sampled at the same fixed, seeded set of voxels (sorted flat indices into the box -- the rank's brick with
+    N > 1, files then named <name>_rank<r>.npy); the whole field when it fits DUMP_BYTES."""
+    import torch
+    fields = {k: v for k, v in fields.items() if v is not None}
+    chans, nvox = next(iter(fields.values())).shape[0], int(np.prod(next(iter(fields.values())).shape[1:]))
+    n = DUMP_BYTES // (len(fields) * world * chans * 4)
+    idx = None
+    if n < nvox:
+        idx = np.unique(np.random.default_rng(DUMP_SEED + rank).integers(0, nvox, n))
+        idx = torch.from_numpy(idx).to(next(iter(fields.values())).device)
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in fields.items():
+        flat = t.reshape(chans, -1)
+        a = (flat if idx is None else flat.index_select(1, idx)).to(torch.float32).cpu().numpy()
+        np.save(os.path.join(dirname, name + ("_rank%d" % rank if world > 1 else "") + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -100,7 +121,12 @@ def main():
     ap.add_argument("--no-profile", action="store_true",
                     help="no per-kernel HIP events in the timed region (no roofline object): the tiles then replay from "
                          "captured hipGraphs, which profiling turns off -- for the graph A/B (NBE_GRAPH=0 / 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the displacement and velocity of the last timed step as "
+                         "DIR/disp.npy and DIR/vel.npy (float32, a fixed seeded sample of voxels, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -270,6 +296,8 @@ def main():
                 "mfma_per_product": mpp, "mfma_issue_frac": ach * mpp / full}
 
     dt, prof, ok, plan = measure(args.precision, args.warmup, args.steps)
+    if args.dump_outputs:                          # before the passes below overwrite disp / velo
+        dump_outputs(args.dump_outputs, {"disp": disp, "vel": velo}, rank, world)
     main_replays = graph_info.get("replays")
     main_waits = graph_info.get("exchange_wait_ms_per_step")
 
