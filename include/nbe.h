@@ -235,6 +235,34 @@ int nbe_set_periodic(nbe_ctx* ctx, int on);
 double nbe_growth_factor(double z, double Om);
 double nbe_vel_norm(double z, double Om);
 
+/* ---- Density (no context: painting has no weights) -----------------------------------------------
+ * The fork's pipeline turns the emulated displacement into a density field right after process_box (scripts/core.py:447-458).
+ * All pointers are DEVICE pointers allocated by the caller; the work is enqueued on `stream` (a hipStream_t, NULL = the null
+ * stream) of the current device, asynchronously.  Conventions: particle (i0, i1, i2) of an
+ * (N0, N1, N2) lattice sits at q_c = i_c L_c / N_c + psi_c (periodic, scripts/halos.py:394-403), mesh node j at j L_c / res_c,
+ * one-dimensional windows are the B-splines of order worder (1 NGP, 2 CIC, 3 TSC, 4 PCS) in units of the mesh spacing. */
+
+/* replaces dj.get_delta_from_psi(psi, method="pm", res, worder, deconvolve=False) (scripts/core.py:449): disp =
+ * (3, N0, N1, N2) float32 or float16 (disp_dtype NBE_F32 / NBE_F16); mesh = (res0, res1, res2) int64, ZEROED by the caller,
+ * receives the masses in units of 2^-22 particles, bitwise independent of scheduling; every particle adds exactly 2^22.
+ * stats = 4 int32 (zeroed by the caller): [0] tiles of 8^3 particles whose footprint took the direct (global-atomic) path,
+ * [1] particles with a non-finite or out-of-range position, which are NOT painted, [2:4] one int64: with count_atomics != 0
+ * (measurement only: one more same-address atomic per tile) the number of 64-bit atomic adds into the mesh. */
+int nbe_paint_mesh(const void* disp, int disp_dtype, const int64_t n[3], const double boxsize[3], const int64_t res[3],
+                   int worder, int count_atomics, void* mesh, void* stats, void* stream);
+/* mesh (int64, as above) -> delta = rho / rho_mean - 1 (float32), rho_mean = nparticles / (res0 res1 res2) */
+int nbe_mesh_to_delta(const void* mesh, const int64_t res[3], int64_t nparticles, void* delta, void* stream);
+/* replaces deconvolve_mas_kernel (scripts/utils.py:136-148): in place on the rfft (res0, res1, res2/2+1) complex64 of a
+ * mesh, divide by prod_c sinc(pi f_c / res_c)^worder, sinc(x) = sin(x) / x (the window alone, no alias sum) */
+int nbe_deconvolve_mas(void* field, const int64_t res[3], int worder, void* stream);
+/* replaces Pk_library.Pk (scripts/utils.py:1083-1085): shell sums over the rfft (n, n, n/2+1) complex64 `a` of an n^3 mesh
+ * (b = NULL: |a|^2, else Re(a b*)); shell s = 1 .. n/2 holds the modes with s - 1/2 <= |k| / k_F < s + 1/2, counted over
+ * the full grid.  binmax = (n/2+1) uint32, sums = 3 (n/2+1) int64, both zeroed by the caller.  Out: binmax[s] = float bits
+ * of the shell's largest |term|; with e_s its binary exponent (binmax = m 2^e_s, m in [0.5, 1)): sums[s] = modes,
+ * sums[n/2+1 + s] = sum of (|k| / k_F - s) in units of 2^-36, sums[2 (n/2+1) + s] = sum of the terms in units of
+ * 2^(e_s - 32).  Integer sums: reproducible bit for bit.  2 <= n <= 4096. */
+int nbe_power_spectrum(const void* a, const void* b, int64_t n, void* binmax, void* sums, void* stream);
+
 /* ---- test / measurement hooks (not part of the reference surface) ------------------------------ */
 
 /* One layer through the production kernels, host NCDHW in / out.  kind: 0 conv3 (VALID 3x3x3),

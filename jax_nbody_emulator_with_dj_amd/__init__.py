@@ -8,6 +8,10 @@ Quick start (same as the reference `jax_nbody_emulator/__init__.py:4-20`):
     emulator = create_emulator(processor_config=config)
     displacement, velocity = emulator.process_box(input_box, z=0.0, Om=0.3)
 
+Density fields of the emulated displacement (mass assignment NGP/CIC/TSC/PCS, window deconvolution, power spectra;
+the fork's DISCO-DJ step, reference scripts/core.py:447-458) run on the GPU in the module
+`jax_nbody_emulator_with_dj_amd.density` (paint_density, deconvolve_mas, power_spectrum), not exported here.
+
 Exports mirror reference `src/jax_nbody_emulator/__init__.py:30-47, :73-95`.
 Everything numerical runs in libnbe.so (include/nbe.h); there is no CPU fallback.
 """

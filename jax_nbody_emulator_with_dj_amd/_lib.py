@@ -12,7 +12,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NBE_LIB") or os.path.join(_HERE, "libnbe.so")   # NBE_LIB: timing-probe builds only
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("nbe_kernels.hip", "nbe_kernels_h3.hip", "nbe_engine.cpp")
+SOURCES = ("nbe_kernels.hip", "nbe_kernels_h3.hip", "nbe_density.hip", "nbe_engine.cpp")
 
 
 class NBEError(RuntimeError):
@@ -75,6 +75,11 @@ SIGNATURES = {
     "nbe_check_finite": (C.c_int, [C.c_void_p]),
     "nbe_set_input_range": (C.c_int, [C.c_void_p, C.c_float]),
     "nbe_query": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
+    "nbe_paint_mesh": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                 C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nbe_mesh_to_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_void_p]),
+    "nbe_deconvolve_mas": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+    "nbe_power_spectrum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nbe_growth_factor": (C.c_double, [C.c_double, C.c_double]),
     "nbe_vel_norm": (C.c_double, [C.c_double, C.c_double]),
     "nbe_test_layer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,

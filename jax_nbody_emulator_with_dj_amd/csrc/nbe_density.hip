@@ -1,0 +1,415 @@
+// Density fields from emulated displacements (include/nbe.h, "Density"): mass assignment of the displaced lattice onto
+// a periodic mesh (NGP / CIC / TSC / PCS), the inverse assignment window on the rfft of the mesh, and shell-binned power
+// spectra.  Replaces the DISCO-DJ / Pylians step of the reference's pipeline (scripts/core.py:447-458,
+// scripts/utils.py:136-148, :1083-1085).  No context: these entry points need no weights.
+//
+// Paint.  One workgroup per Lagrangian tile of 8^3 particles.  Pass 1 reads the tile's
+// displacements once and bounds its Eulerian footprint (the nodes its particles touch, from the tile's own positions).
+// Pass 2 splits every particle's unit mass into fixed-point weights of 2^-22 (cumulative rounding: every weight is within
+// one unit of the exact product of the 1-D B-splines and the weights of a particle sum to exactly 2^22) and adds them
+// with 32-bit integer LDS atomics into an image of the footprint (512 particles * 2^22 = 2^31 fits an unsigned cell).
+// Pass 3 flushes the non-zero cells with 64-bit integer atomics into the int64 mesh, row-major so that the lanes of a
+// wave-instruction cover contiguous runs of a mesh row.  Integer adds commute: the mesh is bitwise independent of the
+// order in which workgroups and lanes arrive.  A tile whose footprint exceeds the LDS image adds its weights straight
+// into the global mesh (the same integers, so the same bits) and is counted in stats[0].
+
+#include "../../include/nbe.h"
+
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdarg>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+
+namespace nbe { int api_fail(const char* msg); }
+
+namespace {
+
+constexpr int kTile = 8;                                  // tile edge in particles
+constexpr int kPaintThreads = 256;
+constexpr int kPerThread = kTile * kTile * kTile / kPaintThreads;
+constexpr int kLdsCells = 16384;                          // 64 KiB image: 2 workgroups per CU
+constexpr double kUnit = 4194304.0;                       // 2^22 fixed-point units per particle mass
+constexpr double kUMax = 1073741824.0;                    // |position| beyond 2^30 mesh cells is rejected
+
+struct PaintArgs {
+    const void* disp;
+    long long n0, n1, n2;       // particle lattice
+    double s0, s1, s2;          // mesh cells per unit of length (res_i / L_i)
+    double a0, a1, a2;          // mesh cells per lattice step (res_i / N_i)
+    int r0, r1, r2;             // mesh
+    int tiles1, tiles2;
+    unsigned long long* mesh;   // (r0, r1, r2) int64, zeroed by the caller
+    int* stats;                 // [0] tiles on the direct path, [1] particles with a non-finite or huge position,
+                                // [2:4] (int64) global 64-bit atomic adds when `count` is set (measurement only)
+    int count;
+};
+
+__device__ inline int wrap(int j, int r) {
+    int m = j % r;
+    return m < 0 ? m + r : m;
+}
+
+// 1-D B-spline of order P in units of the mesh spacing: first node j0, weights of nodes j0 .. j0+P-1
+template <int P>
+__device__ inline int bspline(double u, double* w) {
+    const double fl = floor(u + 1.0 - 0.5 * P);
+    if (P == 1) {
+        w[0] = 1.0;
+    } else if (P == 2) {
+        const double f = u - fl;
+        w[0] = 1.0 - f; w[1] = f;
+    } else if (P == 3) {
+        const double d = u - fl - 1.0;                     // [-0.5, 0.5): offset from the middle node
+        w[0] = 0.5 * (0.5 - d) * (0.5 - d); w[1] = 0.75 - d * d; w[2] = 0.5 * (0.5 + d) * (0.5 + d);
+    } else {
+        const double f = u - fl - 1.0, g = 1.0 - f;        // [0, 1): offset from the second node
+        const double f2 = f * f, f3 = f2 * f;
+        w[0] = g * g * g * (1.0 / 6.0);
+        w[1] = (4.0 - 6.0 * f2 + 3.0 * f3) * (1.0 / 6.0);
+        w[2] = (1.0 + 3.0 * f + 3.0 * f2 - 3.0 * f3) * (1.0 / 6.0);
+        w[3] = f3 * (1.0 / 6.0);
+    }
+    return (int)fl;
+}
+
+// the P^3 fixed-point weights of one particle in (a, b, c) order; fn(a, b, c, q)
+template <int P, typename F>
+__device__ inline void particle_weights(const double* u, int* j0, F fn) {
+    double wx[P], wy[P], wz[P];
+    j0[0] = bspline<P>(u[0], wx);
+    j0[1] = bspline<P>(u[1], wy);
+    j0[2] = bspline<P>(u[2], wz);
+    double S = 0.0;
+    long long Qp = 0;
+#pragma unroll
+    for (int a = 0; a < P; ++a)
+#pragma unroll
+        for (int b = 0; b < P; ++b) {
+            const double wab = wx[a] * wy[b];
+#pragma unroll
+            for (int c = 0; c < P; ++c) {
+                S += wab * wz[c];
+                const long long Q = (long long)rint(S * kUnit);     // the weights sum to round(2^22 * 1) = 2^22
+                const unsigned q = (unsigned)(Q - Qp);
+                Qp = Q;
+                if (q) fn(a, b, c, q);
+            }
+        }
+}
+
+// measurement builds of a call (count_atomics != 0): the workgroup's global atomic adds into stats[2:4]
+__device__ inline void count_atomics(const PaintArgs& A, unsigned na, unsigned* shared) {
+    atomicAdd(shared, na);
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd((unsigned long long*)(A.stats + 2), (unsigned long long)*shared);
+}
+
+template <int P, bool HALF>
+__global__ __launch_bounds__(kPaintThreads) void paint_kernel(PaintArgs A) {
+    __shared__ unsigned img[kLdsCells];
+    __shared__ int lo[3], hi[3];
+    __shared__ unsigned natomic;
+    const int tid = threadIdx.x;
+    const long long tile = blockIdx.x;
+    const int t2 = (int)(tile % A.tiles2);
+    const long long rest = tile / A.tiles2;
+    const int t1 = (int)(rest % A.tiles1), t0 = (int)(rest / A.tiles1);
+    if (tid < 3) { lo[tid] = INT_MAX; hi[tid] = INT_MIN; }
+    if (tid == 0) natomic = 0u;
+    __syncthreads();
+
+    const long long ncell = A.n0 * A.n1 * A.n2;
+    double u[kPerThread][3];
+    bool live[kPerThread];
+    int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
+#pragma unroll
+    for (int k = 0; k < kPerThread; ++k) {
+        const int l = tid + k * kPaintThreads;
+        const long long i0 = t0 * kTile + (l >> 6), i1 = t1 * kTile + ((l >> 3) & 7), i2 = t2 * kTile + (l & 7);
+        live[k] = i0 < A.n0 && i1 < A.n1 && i2 < A.n2;
+        if (!live[k]) continue;
+        const long long idx = (i0 * A.n1 + i1) * A.n2 + i2;
+        float p0, p1, p2;
+        if (HALF) {
+            const _Float16* d = (const _Float16*)A.disp;
+            p0 = (float)d[idx]; p1 = (float)d[ncell + idx]; p2 = (float)d[2 * ncell + idx];
+        } else {
+            const float* d = (const float*)A.disp;
+            p0 = d[idx]; p1 = d[ncell + idx]; p2 = d[2 * ncell + idx];
+        }
+        // lattice q = i L / N, position q + psi, in mesh units (periodic wrap applied per node)
+        u[k][0] = (double)i0 * A.a0 + (double)p0 * A.s0;
+        u[k][1] = (double)i1 * A.a1 + (double)p1 * A.s1;
+        u[k][2] = (double)i2 * A.a2 + (double)p2 * A.s2;
+        if (!(fabs(u[k][0]) < kUMax && fabs(u[k][1]) < kUMax && fabs(u[k][2]) < kUMax)) {
+            live[k] = false;
+            atomicAdd(&A.stats[1], 1);
+            continue;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int j = (int)floor(u[k][c] + 1.0 - 0.5 * P);
+            mn[c] = min(mn[c], j);
+            mx[c] = max(mx[c], j + P - 1);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (mn[c] != INT_MAX) { atomicMin(&lo[c], mn[c]); atomicMax(&hi[c], mx[c]); }
+    }
+    __syncthreads();
+    if (hi[0] < lo[0]) return;                             // no live particle in this tile (uniform)
+
+    const long long e0 = (long long)hi[0] - lo[0] + 1, e1 = (long long)hi[1] - lo[1] + 1,
+                    e2 = (long long)hi[2] - lo[2] + 1;
+    const int r0 = A.r0, r1 = A.r1, r2 = A.r2;
+    if (e0 * e1 * e2 > kLdsCells) {
+        // footprint larger than the image: the same integer weights straight into the mesh
+        if (tid == 0) atomicAdd(&A.stats[0], 1);
+        unsigned na = 0;
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) {
+            if (!live[k]) continue;
+            int j0[3];
+            particle_weights<P>(u[k], j0, [&](int a, int b, int c, unsigned q) {
+                const long long g = ((long long)wrap(j0[0] + a, r0) * r1 + wrap(j0[1] + b, r1)) * r2 + wrap(j0[2] + c, r2);
+                atomicAdd(&A.mesh[g], (unsigned long long)q);
+                ++na;
+            });
+        }
+        if (A.count) count_atomics(A, na, &natomic);
+        return;
+    }
+
+    const int E1 = (int)e1, E2 = (int)e2, vol = (int)(e0 * e1 * e2);
+    const int l0 = lo[0], l1 = lo[1], l2 = lo[2];
+    for (int i = tid; i < vol; i += kPaintThreads) img[i] = 0u;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kPerThread; ++k) {
+        if (!live[k]) continue;
+        int j0[3];
+        particle_weights<P>(u[k], j0, [&](int a, int b, int c, unsigned q) {
+            atomicAdd(&img[((j0[0] + a - l0) * E1 + (j0[1] + b - l1)) * E2 + (j0[2] + c - l2)], q);
+        });
+    }
+    __syncthreads();
+    unsigned na = 0;
+    for (int i = tid; i < vol; i += kPaintThreads) {
+        const unsigned v = img[i];
+        if (!v) continue;
+        const int c2 = i % E2, r = i / E2, c1 = r % E1, c0 = r / E1;
+        const long long g = ((long long)wrap(l0 + c0, r0) * r1 + wrap(l1 + c1, r1)) * r2 + wrap(l2 + c2, r2);
+        atomicAdd(&A.mesh[g], (unsigned long long)v);
+        ++na;
+    }
+    if (A.count) count_atomics(A, na, &natomic);
+}
+
+__global__ void mesh_to_delta_kernel(const long long* __restrict__ mesh, float* __restrict__ out, long long n,
+                                     double scale) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        out[i] = (float)((double)mesh[i] * scale - 1.0);
+}
+
+// frequency index of position i on an axis of n points (numpy.fft.fftfreq * n)
+__device__ inline long long freq(long long i, long long n) { return i <= n / 2 ? i : i - n; }
+
+__device__ inline double sinc_pi(long long f, long long n) {            // sinc(pi f / n), sinc(x) = sin(x) / x
+    if (f == 0) return 1.0;
+    const double x = (double)f / (double)n;
+    return sinpi(x) / (3.141592653589793 * x);
+}
+
+template <int P>
+__global__ void deconvolve_kernel(float2* __restrict__ f, long long r0, long long r1, long long r2) {
+    const long long h2 = r2 / 2 + 1, n = r0 * r1 * h2;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long i2 = i % h2, r = i / h2, i1 = r % r1, i0 = r / r1;
+        const double w = sinc_pi(freq(i0, r0), r0) * sinc_pi(freq(i1, r1), r1) * sinc_pi(i2, r2);
+        double wp = w;
+#pragma unroll
+        for (int p = 1; p < P; ++p) wp *= w;
+        const double inv = 1.0 / wp;
+        float2 v = f[i];
+        v.x = (float)(v.x * inv);
+        v.y = (float)(v.y * inv);
+        f[i] = v;
+    }
+}
+
+// One mode of the half spectrum of an n^3 mesh: shell b (0 = not binned), full-grid weight, |k| / k_F, Re(a b*)
+struct Mode { int b; int w; double kk; double p; };
+
+__device__ inline Mode mode_at(const float2* a, const float2* bb, long long i, long long n) {
+    const long long h2 = n / 2 + 1;
+    const long long i2 = i % h2, r = i / h2, i1 = r % n, i0 = r / n;
+    const long long f0 = freq(i0, n), f1 = freq(i1, n);
+    Mode m;
+    m.kk = sqrt((double)(f0 * f0 + f1 * f1 + i2 * i2));
+    m.b = (int)floor(m.kk + 0.5);
+    if (m.b < 1 || m.b > n / 2) { m.b = 0; return m; }
+    m.w = (i2 == 0 || (n % 2 == 0 && i2 == n / 2)) ? 1 : 2;
+    const float2 x = a[i], y = bb ? bb[i] : x;
+    m.p = (double)x.x * y.x + (double)x.y * y.y;
+    return m;
+}
+
+// pass 1: per-shell max |Re(a b*)| as float bits (unsigned order = float order for non-negative floats)
+__global__ void pk_max_kernel(const float2* __restrict__ a, const float2* __restrict__ b, long long n,
+                              unsigned* __restrict__ binmax) {
+    extern __shared__ unsigned smax[];
+    const int nb = (int)(n / 2) + 1;
+    for (int i = threadIdx.x; i < nb; i += blockDim.x) smax[i] = 0u;
+    __syncthreads();
+    const long long total = n * n * (n / 2 + 1);
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const Mode m = mode_at(a, b, i, n);
+        if (m.b) atomicMax(&smax[m.b], __float_as_uint((float)fabs(m.p)));
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nb; i += blockDim.x)
+        if (smax[i]) atomicMax(&binmax[i], smax[i]);
+}
+
+// pass 2: per shell, in integers: sum of weights, sum of w (|k|/k_F - b) in units of 2^-36, sum of w Re(a b*) in units
+// of 2^(e_b - 32) where binmax_b = m 2^e_b, m in [0.5, 1) -- every term is at most 2^32 units
+constexpr double kKUnit = 68719476736.0;                  // 2^36
+__global__ void pk_sum_kernel(const float2* __restrict__ a, const float2* __restrict__ b, long long n,
+                              const unsigned* __restrict__ binmax, unsigned long long* __restrict__ sums) {
+    extern __shared__ unsigned long long ssum[];           // [3][nb]: weight, k, power
+    const int nb = (int)(n / 2) + 1;
+    int* sexp = (int*)(ssum + 3 * nb);
+    for (int i = threadIdx.x; i < 3 * nb; i += blockDim.x) ssum[i] = 0ull;
+    for (int i = threadIdx.x; i < nb; i += blockDim.x) {
+        const float m = __uint_as_float(binmax[i]);
+        int e = 0;
+        if (isfinite(m) && m > 0.0f) frexp((double)m, &e);
+        sexp[i] = isfinite(m) ? 32 - e : INT_MIN;          // INT_MIN: non-finite shell, reported by the caller
+    }
+    __syncthreads();
+    const long long total = n * n * (n / 2 + 1);
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const Mode m = mode_at(a, b, i, n);
+        if (!m.b) continue;
+        const long long kq = (long long)rint((m.kk - m.b) * kKUnit);
+        const int s = sexp[m.b];
+        const long long pq = s == INT_MIN ? 0 : (long long)rint(ldexp(m.p, s));
+        atomicAdd(&ssum[m.b], (unsigned long long)m.w);
+        atomicAdd(&ssum[nb + m.b], (unsigned long long)(m.w * kq));
+        atomicAdd(&ssum[2 * nb + m.b], (unsigned long long)(m.w * pq));
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 3 * nb; i += blockDim.x)
+        if (ssum[i]) atomicAdd(&sums[i], ssum[i]);
+}
+
+int fail(const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return nbe::api_fail(buf);
+}
+
+int launched(const char* what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail("%s: launch failed: %s", what, hipGetErrorString(e));
+}
+
+int grid_for(long long n, int threads) {
+    long long g = (n + threads - 1) / threads;
+    return (int)(g < 1 ? 1 : g > 65536 ? 65536 : g);
+}
+
+}  // namespace
+
+extern "C" {
+
+int nbe_paint_mesh(const void* disp, int disp_dtype, const int64_t n[3], const double boxsize[3], const int64_t res[3],
+                   int worder, int count_atomics, void* mesh, void* stats, void* stream) {
+    if (!disp || !mesh || !stats || !n || !boxsize || !res) return fail("nbe_paint_mesh: NULL argument");
+    if (disp_dtype != NBE_F32 && disp_dtype != NBE_F16) return fail("nbe_paint_mesh: dtype %d unsupported", disp_dtype);
+    if (worder < 1 || worder > 4) return fail("nbe_paint_mesh: worder %d not in 1..4", worder);
+    for (int c = 0; c < 3; ++c) {
+        if (n[c] < 1 || res[c] < 1 || res[c] > (1 << 20) || !(boxsize[c] > 0.0) || !std::isfinite(boxsize[c]))
+            return fail("nbe_paint_mesh: bad geometry on axis %d (n %lld, res %lld, boxsize %g)", c, (long long)n[c],
+                        (long long)res[c], boxsize[c]);
+    }
+    PaintArgs A;
+    A.disp = disp;
+    A.n0 = n[0]; A.n1 = n[1]; A.n2 = n[2];
+    A.s0 = res[0] / boxsize[0]; A.s1 = res[1] / boxsize[1]; A.s2 = res[2] / boxsize[2];
+    A.a0 = (double)res[0] / n[0]; A.a1 = (double)res[1] / n[1]; A.a2 = (double)res[2] / n[2];
+    A.r0 = (int)res[0]; A.r1 = (int)res[1]; A.r2 = (int)res[2];
+    const long long tl0 = (n[0] + kTile - 1) / kTile;
+    A.tiles1 = (int)((n[1] + kTile - 1) / kTile);
+    A.tiles2 = (int)((n[2] + kTile - 1) / kTile);
+    A.mesh = (unsigned long long*)mesh;
+    A.stats = (int*)stats;
+    A.count = count_atomics != 0;
+    const long long tiles = tl0 * A.tiles1 * A.tiles2;
+    if (tiles > INT_MAX) return fail("nbe_paint_mesh: %lld tiles exceed one launch", tiles);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)tiles), block(kPaintThreads);
+    const bool half = disp_dtype == NBE_F16;
+    switch (worder * 2 + half) {
+        case 2: hipLaunchKernelGGL((paint_kernel<1, false>), grid, block, 0, s, A); break;
+        case 3: hipLaunchKernelGGL((paint_kernel<1, true>), grid, block, 0, s, A); break;
+        case 4: hipLaunchKernelGGL((paint_kernel<2, false>), grid, block, 0, s, A); break;
+        case 5: hipLaunchKernelGGL((paint_kernel<2, true>), grid, block, 0, s, A); break;
+        case 6: hipLaunchKernelGGL((paint_kernel<3, false>), grid, block, 0, s, A); break;
+        case 7: hipLaunchKernelGGL((paint_kernel<3, true>), grid, block, 0, s, A); break;
+        case 8: hipLaunchKernelGGL((paint_kernel<4, false>), grid, block, 0, s, A); break;
+        default: hipLaunchKernelGGL((paint_kernel<4, true>), grid, block, 0, s, A); break;
+    }
+    return launched("nbe_paint_mesh");
+}
+
+int nbe_mesh_to_delta(const void* mesh, const int64_t res[3], int64_t nparticles, void* delta, void* stream) {
+    if (!mesh || !delta || !res) return fail("nbe_mesh_to_delta: NULL argument");
+    if (nparticles < 1 || res[0] < 1 || res[1] < 1 || res[2] < 1) return fail("nbe_mesh_to_delta: bad sizes");
+    const long long cells = (long long)res[0] * res[1] * res[2];
+    const double scale = (double)cells / ((double)nparticles * kUnit);
+    hipLaunchKernelGGL(mesh_to_delta_kernel, dim3(grid_for(cells, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const long long*)mesh, (float*)delta, cells, scale);
+    return launched("nbe_mesh_to_delta");
+}
+
+int nbe_deconvolve_mas(void* field, const int64_t res[3], int worder, void* stream) {
+    if (!field || !res) return fail("nbe_deconvolve_mas: NULL argument");
+    if (worder < 1 || worder > 4) return fail("nbe_deconvolve_mas: worder %d not in 1..4", worder);
+    if (res[0] < 1 || res[1] < 1 || res[2] < 1) return fail("nbe_deconvolve_mas: bad sizes");
+    const long long n = (long long)res[0] * res[1] * (res[2] / 2 + 1);
+    const dim3 g(grid_for(n, 256)), b(256);
+    hipStream_t s = (hipStream_t)stream;
+    float2* f = (float2*)field;
+    switch (worder) {
+        case 1: hipLaunchKernelGGL(deconvolve_kernel<1>, g, b, 0, s, f, res[0], res[1], res[2]); break;
+        case 2: hipLaunchKernelGGL(deconvolve_kernel<2>, g, b, 0, s, f, res[0], res[1], res[2]); break;
+        case 3: hipLaunchKernelGGL(deconvolve_kernel<3>, g, b, 0, s, f, res[0], res[1], res[2]); break;
+        default: hipLaunchKernelGGL(deconvolve_kernel<4>, g, b, 0, s, f, res[0], res[1], res[2]); break;
+    }
+    return launched("nbe_deconvolve_mas");
+}
+
+int nbe_power_spectrum(const void* a, const void* b, int64_t n, void* binmax, void* sums, void* stream) {
+    if (!a || !binmax || !sums) return fail("nbe_power_spectrum: NULL argument");
+    if (n < 2 || n > 4096) return fail("nbe_power_spectrum: mesh size %lld unsupported (2 .. 4096)", (long long)n);
+    const long long total = n * n * (n / 2 + 1);
+    const int nb = (int)(n / 2) + 1;
+    const dim3 g(grid_for(total, 256) < 2048 ? grid_for(total, 256) : 2048), blk(256);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(pk_max_kernel, g, blk, nb * sizeof(unsigned), s, (const float2*)a, (const float2*)b, (long long)n,
+                       (unsigned*)binmax);
+    if (int rc = launched("nbe_power_spectrum (max)")) return rc;
+    hipLaunchKernelGGL(pk_sum_kernel, g, blk, nb * (3 * sizeof(unsigned long long) + sizeof(int)), s, (const float2*)a,
+                       (const float2*)b, (long long)n, (const unsigned*)binmax, (unsigned long long*)sums);
+    return launched("nbe_power_spectrum (sum)");
+}
+
+}  // extern "C"

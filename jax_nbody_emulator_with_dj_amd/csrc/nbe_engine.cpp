@@ -38,6 +38,9 @@ static int fail(const char* fmt, ...) {
     return 1;
 }
 
+// error message of the context-free entry points in other translation units (nbe_density.hip)
+namespace nbe { int api_fail(const char* msg) { g_err = msg; return 1; } }
+
 #define HIPCHK(expr)                                                                        \
     do {                                                                                    \
         hipError_t e_ = (expr);                                                             \

@@ -15,6 +15,12 @@ Same command line, file formats, range checks and output names as the reference'
     displacement     (3, N0, N1, N2) z = 0 linear (ZA) displacement field
     outputs          <output_dir>/emu_dis.npy  and, with --vel, <output_dir>/emu_vel.npy
 
+Density fields (the fork's DISCO-DJ step, scripts/core.py:447-458): with `--density_res N` every box also writes
+<output_dir>/emu_delta.npy, the emulated displacement painted onto an N^3 mesh on the GPU (density.py; `--mas_worder`
+1-4 = NGP/CIC/TSC/PCS, default 2; `--no-deconvolve` keeps the assignment window; `--boxsize` in Mpc/h, default 1000),
+and with `--pk` <output_dir>/emu_pk.npz (k, pk, nmodes).  Painting reads the float32 displacement on the device; the
+saved emu_dis.npy is rounded to --output-precision afterwards.
+
 What differs from the reference: the engine, its weights and its ~100 GB workspace stay resident on the
 GPU for the whole batch, and disk I/O overlaps compute -- the next displacement file is read and the
 previous results are written by a background thread while the GPU works on the current box.
@@ -143,7 +149,40 @@ def build_parser():
                     help="Parameter tree: flat .npz (block/layer/leaf arrays, see params_io.py) or the reference's "
                          ".npz with a pickled {'params': ...} dict (read with a restricted unpickler); "
                          'default: the packaged pretrained blob')
+    # density fields: absent from the Namespace unless given, so that runs without them are exactly today's
+    ap.add_argument('--density_res', type=mesh_size, default=argparse.SUPPRESS,
+                    help='Also paint the emulated displacement onto an N^3 mesh: <output_dir>/emu_delta.npy (float32)')
+    ap.add_argument('--boxsize', type=float, default=argparse.SUPPRESS,
+                    help='Box size in Mpc/h for --density_res (default: 1000.0, Quijote)')
+    ap.add_argument('--mas_worder', type=int, choices=(1, 2, 3, 4), default=argparse.SUPPRESS,
+                    help='Mass assignment for --density_res: 1 NGP, 2 CIC, 3 TSC, 4 PCS (default: 2)')
+    ap.add_argument('--deconvolve', action=argparse.BooleanOptionalAction, default=argparse.SUPPRESS,
+                    help='Deconvolve the mass assignment window (default: True)')
+    ap.add_argument('--pk', action='store_true', default=argparse.SUPPRESS,
+                    help='With --density_res: also write the power spectrum to <output_dir>/emu_pk.npz (k, pk, nmodes)')
     return ap
+
+
+def mesh_size(text):
+    n = int(text)
+    if n < 1:
+        raise argparse.ArgumentTypeError(f'mesh size must be >= 1, got {n}')
+    return n
+
+
+def density_options(args):
+    """The density-field settings of a parsed command line, or None without --density_res.  Accepts Namespaces that
+    lack the density attributes (built before they existed)."""
+    res = getattr(args, 'density_res', None)
+    if res is None:
+        if getattr(args, 'pk', False):
+            _die('--pk needs --density_res')
+        return None
+    boxsize = float(getattr(args, 'boxsize', 1000.0))
+    if not boxsize > 0:
+        _die(f'--boxsize must be positive, got {boxsize}')
+    return dict(res=int(res), boxsize=boxsize, worder=int(getattr(args, 'mas_worder', 2)),
+                deconvolve=bool(getattr(args, 'deconvolve', True)), pk=bool(getattr(args, 'pk', False)))
 
 
 def load_params(path):
@@ -170,6 +209,10 @@ def run(args):
     print(f'  Compute velocity: {args.vel}')
     print(f'  Style modulation: {args.style}')
     print(f'  Subbox divisions: {args.ndiv}')
+    dens = density_options(args)
+    if dens is not None:
+        print(f"  Density: {dens['res']}^3 mesh, worder {dens['worder']}, deconvolve {dens['deconvolve']}, "
+              f"boxsize {dens['boxsize']}, P(k) {dens['pk']}")
     print()
 
     shape = None
@@ -181,18 +224,41 @@ def run(args):
 
     params = load_params(args.params)
     mid = int(params['params']['conv_l01']['conv_0']['weight'].shape[0])
-    config = SubboxConfig(size=box, ndiv=args.ndiv, dtype=args.precision, output_dtype=args.output_precision)
+    # density mode: float32 fields on the device (painted from), rounded to --output-precision for the files
+    config = SubboxConfig(size=box, ndiv=args.ndiv, dtype=args.precision,
+                          output_dtype=args.output_precision if dens is None else np.float32)
     emu = create_emulator(premodulate=not args.style, compute_vel=args.vel, load_params=False,
                           processor_config=config, mid_chan=mid)
     if args.style:
         emu.params = emu.processor.params = params
 
-    def save(out_dir, result):
+    def save(out_dir, result, extra=None):
         if args.vel:
             np.save(out_dir / 'emu_dis.npy', result[0])
             np.save(out_dir / 'emu_vel.npy', result[1])
         else:
             np.save(out_dir / 'emu_dis.npy', result)
+        if extra is not None:
+            np.save(out_dir / 'emu_delta.npy', extra['delta'])
+            if 'pk' in extra:
+                k, pk, nmodes = extra['pk']
+                np.savez(out_dir / 'emu_pk.npz', k=k, pk=pk, nmodes=nmodes)
+
+    def with_density(dis_in, z, Om):
+        """process_box on the device, the density field of its float32 displacement, host copies of the fields."""
+        import torch
+        from .density import paint_density, power_spectrum
+        box_t = torch.from_numpy(np.ascontiguousarray(dis_in)).to('cuda')
+        result = emu.process_box(box_t, z=z, Om=Om, show_progress=not args.quiet)
+        disp = result[0] if args.vel else result
+        delta = paint_density(disp, boxsize=dens['boxsize'], res=dens['res'], worder=dens['worder'],
+                              deconvolve=dens['deconvolve'])
+        extra = {'delta': delta.cpu().numpy()}
+        if dens['pk']:
+            extra['pk'] = power_spectrum(delta, boxsize=dens['boxsize'])
+        out_dt = np.dtype(args.output_precision)
+        host = tuple(t.cpu().numpy().astype(out_dt, copy=False) for t in (result if args.vel else (result,)))
+        return (host if args.vel else host[0]), extra
 
     # one reader and one writer thread: disk I/O of the neighbours overlaps the GPU work on the current box
     with ThreadPoolExecutor(max_workers=2) as pool:
@@ -207,11 +273,15 @@ def run(args):
                 tree = (modulate_emulator_parameters_vel if args.vel else modulate_emulator_parameters)(params, z, Om)
                 emu.params = emu.processor.params = tree
             t0 = time.time()
-            result = emu.process_box(dis_in, z=z, Om=Om, show_progress=not args.quiet)
+            extra = None
+            if dens is None:
+                result = emu.process_box(dis_in, z=z, Om=Om, show_progress=not args.quiet)
+            else:
+                result, extra = with_density(dis_in, z, Om)
             dt = time.time() - t0
             if pending is not None:
                 pending.result()
-            pending = pool.submit(save, out_dir, result)
+            pending = pool.submit(save, out_dir, result, extra)
             print(f'[{i + 1}/{n}] z={z:.4f}, Om={Om:.4f}: {dt:.2f}s -> {out_dir}')
         if pending is not None:
             pending.result()

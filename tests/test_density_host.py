@@ -1,0 +1,180 @@
+"""Density fields (jax_nbody_emulator_with_dj_amd.density) on the CPU: the float64 reference's conventions, argument
+validation before any device work, the missing-device error and the CLI flags."""
+
+import argparse
+
+import numpy as np
+import pytest
+
+import mas_ref as R
+from jax_nbody_emulator_with_dj_amd import _lib
+from jax_nbody_emulator_with_dj_amd import density as D
+from jax_nbody_emulator_with_dj_amd import run_emulator as CLI
+
+
+@pytest.mark.parametrize("worder", [1, 2, 3, 4])
+def test_reference_windows_are_a_partition_of_unity(worder):
+    u = np.random.default_rng(worder).uniform(-50.0, 50.0, 10000)
+    j0, w = R.nodes(u, worder)
+    assert w.shape == (u.size, worder)
+    np.testing.assert_allclose(w.sum(axis=1), 1.0, rtol=0, atol=1e-14)
+    assert (w >= 0).all()
+    # every node within the window's support of u is one of the p nodes
+    for t in range(worder):
+        assert (np.abs(u - (j0 + t)) <= 0.5 * worder + 1e-12).all()
+
+
+@pytest.mark.parametrize("worder", [1, 2, 3, 4])
+def test_undisplaced_lattice_paints_zero(worder):
+    disp = np.zeros((3, 8, 12, 16), np.float32)
+    mass, _ = R.paint(disp, (80.0, 120.0, 160.0), (8, 12, 16), worder)
+    np.testing.assert_allclose(R.delta_from_mass(mass, 8 * 12 * 16), 0.0, atol=1e-12)
+
+
+def two_particle_cic_case():
+    """Two particles on a (2, 1, 1) lattice in a box of 4 (mesh spacing 1 at res 4): lattice sites x = 0 and x = 2.
+    Particle 0 ends at (-eps, 0.25, 0), particle 1 at (4 - eps, 0.5, 1.5); both wrap across x = 0."""
+    eps = 1.0 / 64.0
+    disp = np.zeros((3, 2, 1, 1), np.float32)
+    disp[:, 0, 0, 0] = (-eps, 0.25, 0.0)
+    disp[:, 1, 0, 0] = (2.0 - eps, 0.5, 1.5)
+    m = np.zeros((4, 4, 4))
+    for (x, wx) in ((3, eps), (0, 1.0 - eps)):               # both particles sit eps below node 0 = node 4
+        for (y, wy) in ((0, 0.75), (1, 0.25)):
+            m[x, y, 0] += wx * wy
+        for (y, wy) in ((0, 0.5), (1, 0.5)):
+            for (z, wz) in ((1, 0.5), (2, 0.5)):
+                m[x, y, z] += wx * wy * wz
+    return disp, m
+
+
+def test_two_particle_cic_by_hand():
+    disp, m = two_particle_cic_case()
+    mass, count = R.paint(disp, 4.0, 4, 2)
+    np.testing.assert_allclose(mass, m, rtol=0, atol=1e-15)
+    assert mass.sum() == pytest.approx(2.0, abs=1e-14)
+    assert count[0, 0, 0] == 1 and count[0, 0, 1] == 1 and count[0, 1, 2] == 1 and count[1, 1, 1] == 0
+
+
+def plane_wave(n, L, amp, m=(1, 2, 2)):
+    x = np.arange(n) * (L / n)
+    kF = 2.0 * np.pi / L
+    ph = kF * (m[0] * x[:, None, None] + m[1] * x[None, :, None] + m[2] * x[None, None, :])
+    return amp * np.cos(ph)
+
+
+def test_plane_wave_power_in_its_own_shell():
+    n, L, A = 16, 100.0, 0.3
+    k, pk, nm = R.power(plane_wave(n, L, A), L)             # |m| = 3
+    assert k.shape == pk.shape == nm.shape == (n // 2,)
+    for s in range(1, n // 2 + 1):
+        assert nm[s - 1] == R.full_grid_modes(n, s)
+    # the two modes +-(1, 2, 2) carry |delta_k|^2 = (A n^3 / 2)^2 each: P = 2 (A n^3 / 2)^2 L^3 / n^6 / modes
+    np.testing.assert_allclose(pk[2], A * A * L ** 3 / 2.0 / nm[2], rtol=1e-12)
+    assert np.abs(np.delete(pk, 2)).max() < 1e-20 * pk[2]
+    assert k[0] == pytest.approx(2 * np.pi / L * np.mean(_shell_norms(n, 1)), rel=1e-12)
+
+
+def _shell_norms(n, s):
+    f = np.fft.fftfreq(n) * n
+    kk = np.sqrt(f[:, None, None] ** 2 + f[None, :, None] ** 2 + f[None, None, :] ** 2).ravel()
+    return kk[np.floor(kk + 0.5) == s]
+
+
+def test_reference_deconvolution_inverts_the_window():
+    d = np.random.default_rng(0).standard_normal((8, 6, 10))
+    back = np.fft.irfftn(np.fft.rfftn(R.deconvolve(d, 3)) * R.mas_window(d.shape, 3), s=d.shape, axes=(0, 1, 2))
+    np.testing.assert_allclose(back, d, atol=1e-12)
+
+
+# ---- argument validation: ValueError before any device work ---------------------------------------------------------
+
+def test_paint_validation():
+    ok = np.zeros((3, 4, 4, 4), np.float32)
+    for bad in (np.zeros((2, 4, 4, 4), np.float32), np.zeros((3, 4, 4), np.float32), np.zeros((3, 0, 4, 4), np.float32)):
+        with pytest.raises(ValueError, match="shape"):
+            D.paint_density(bad, 100.0, 4)
+    for w in (0, 5, -1, 2.0, True, "2"):
+        with pytest.raises(ValueError, match="worder"):
+            D.paint_density(ok, 100.0, 4, worder=w)
+    for r in (0, -4, (4, 4, 0), (4, 4), 4.0, (4, 4, 4.5)):
+        with pytest.raises(ValueError, match="res"):
+            D.paint_density(ok, 100.0, r)
+    for L in (0.0, -1.0, float("inf"), (1.0, 2.0), (1.0, 2.0, float("nan"))):
+        with pytest.raises(ValueError, match="boxsize"):
+            D.paint_density(ok, L, 4)
+    with pytest.raises(ValueError, match="float32 or float16"):
+        D.paint_density(ok.astype(np.float64), 100.0, 4)
+    with pytest.raises(ValueError, match="NumPy array"):
+        D.paint_density(ok.tolist(), 100.0, 4)
+    import torch
+    with pytest.raises(ValueError, match="CUDA"):
+        D.paint_density(torch.zeros(3, 4, 4, 4), 100.0, 4)
+
+
+def test_deconvolve_and_power_spectrum_validation():
+    with pytest.raises(ValueError, match="worder"):
+        D.deconvolve_mas(np.zeros((4, 4, 4), np.float32), worder=5)
+    with pytest.raises(ValueError, match="3-D"):
+        D.deconvolve_mas(np.zeros((4, 4), np.float32))
+    with pytest.raises(ValueError, match="cubic mesh"):
+        D.power_spectrum(np.zeros((4, 4, 8), np.float32), 100.0)
+    with pytest.raises(ValueError, match="cubic box"):
+        D.power_spectrum(np.zeros((4, 4, 4), np.float32), (100.0, 100.0, 200.0))
+    with pytest.raises(ValueError, match="other must match"):
+        D.power_spectrum(np.zeros((4, 4, 4), np.float32), 100.0, other=np.zeros((8, 8, 8), np.float32))
+    with pytest.raises(ValueError, match="float32"):
+        D.power_spectrum(np.zeros((4, 4, 4), np.float64), 100.0)
+
+
+def test_no_device_means_loud_failure():
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is visible")
+    with pytest.raises(_lib.NBEError, match="no HIP device|no CPU fallback"):
+        D.paint_density(np.zeros((3, 4, 4, 4), np.float32), 100.0, 4)
+    with pytest.raises(_lib.NBEError):
+        D.power_spectrum(np.zeros((4, 4, 4), np.float32), 100.0)
+    with pytest.raises(_lib.NBEError):
+        D.deconvolve_mas(np.zeros((4, 4, 4), np.float32))
+
+
+def test_density_names_stay_out_of_the_package_namespace():
+    import jax_nbody_emulator_with_dj_amd as J
+    for name in D.__all__:
+        assert name not in J.__all__
+    assert "density" in J.__doc__
+
+
+# ---- CLI ---------------------------------------------------------------------------------------------------------------
+
+def _base_argv(tmp_path):
+    cos = tmp_path / "params.npy"
+    np.save(cos, np.array([0.3, 0.05, 0.7, 0.96, 0.8, 0.5]))
+    dis = tmp_path / "dis.npy"
+    np.save(dis, np.zeros((3, 8, 8, 8), np.float32))
+    return ["--cosmo_param_files", str(cos), "--displacement_files", str(dis), "--output_dirs", str(tmp_path),
+            "--ndiv", "1"]
+
+
+def test_cli_density_flags(tmp_path):
+    ap = CLI.build_parser()
+    for opt in ("--density_res", "--boxsize", "--mas_worder", "--deconvolve", "--no-deconvolve", "--pk"):
+        assert any(opt in a.option_strings for a in ap._actions), opt
+    base = _base_argv(tmp_path)
+    plain = vars(ap.parse_args(base))
+    assert not {"density_res", "boxsize", "mas_worder", "deconvolve", "pk"} & set(plain)   # today's Namespace
+    ns = ap.parse_args(base + ["--density_res", "16", "--boxsize", "500", "--mas_worder", "3", "--no-deconvolve", "--pk"])
+    assert (ns.density_res, ns.boxsize, ns.mas_worder, ns.deconvolve, ns.pk) == (16, 500.0, 3, False, True)
+    opts = CLI.density_options(ns)
+    assert opts == dict(res=16, boxsize=500.0, worder=3, deconvolve=False, pk=True)
+    assert CLI.density_options(ap.parse_args(base)) is None
+    assert CLI.density_options(argparse.Namespace()) is None
+    d = CLI.density_options(ap.parse_args(base + ["--density_res", "8"]))
+    assert d == dict(res=8, boxsize=1000.0, worder=2, deconvolve=True, pk=False)
+    with pytest.raises(SystemExit):
+        ap.parse_args(base + ["--density_res", "16", "--mas_worder", "5"])
+    with pytest.raises(SystemExit):
+        ap.parse_args(base + ["--density_res", "0"])
+    with pytest.raises(SystemExit, match="--density_res"):
+        CLI.density_options(ap.parse_args(base + ["--pk"]))
