@@ -521,9 +521,6 @@ static bool narrow_tile(const Layer* L) { return L->pwn.w && !narrow_off(); }
 static int run_conv(nbe_ctx* c, const Layer& L, const ConvLaunch& cl_in, bool has_dx) {
     if (c->dry) return 0;
     ConvLaunch cl = cl_in;
-    // timing experiments of NBE_DBG builds (bits >= 8); production kernels ignore them
-    static const int dbgf = getenv("NBE_DEBUG_FLAGS") ? atoi(getenv("NBE_DEBUG_FLAGS")) & 0xF00 : 0;
-    cl.flags |= dbgf;
     const bool g6 = c->gauge_active && L.g6 && has_dx;
     const bool nov = !c->vel && c->prec == PREC_F16X3 && L.kind == 0 && L.pw.ww && c->wino_ok;   // displacement only: conv_h3w_kernel<., NOVEL>
     if (c->gauge_active) { cl.gout = L.gout; cl.beta = g6 ? L.beta : nullptr; }
@@ -1269,8 +1266,7 @@ static int stream_tail(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S, 
     const int Hs = skip0.p.H - 2 * pad, Ws = skip0.p.W - 2 * pad;
     // Fused blocks on the gauged f16x3 kernel read concat([skip, up]) from two tensors (core :168-169 without the concat):
     // the slab's planes of the skip connection where they are, the up-sampled half in a mid-channel tensor of its own.
-    static const bool two_off = getenv("NBE_TWOSRC") && atoi(getenv("NBE_TWOSRC")) == 0;           // A/B switch
-    const bool two = block_fused(c, Lr00, true) && !two_off && c->mid % 16 == 0;   // the kernel switches sources between 16-channel chunks
+    const bool two = block_fused(c, Lr00, true) && c->mid % 16 == 0;   // the kernel switches sources between 16-channel chunks
     Tensor cat = tallocp(c, two ? m : 2 * m, S + 8, Hs, Ws, pad), hq = alloc_hidden(c, 2 * m, S + 6, cat, block_fused(c, Lr00, true));
     Tensor q = tallocp(c, m, S + 4, Hs - 2 * sy, Ws - 2 * sy, pad), hy = alloc_hidden(c, m, S + 2, q, block_fused(c, Lr01, true));
     Tensor y = tallocp(c, c->out_chan, S, Hs - 4 * sy, Ws - 4 * sy, pad);

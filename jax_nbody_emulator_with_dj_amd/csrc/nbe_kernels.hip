@@ -228,11 +228,7 @@ static void launch_conv_t(const ConvKArgs& ka, int ctiles, hipStream_t s) {
     constexpr int BUF = WP * ((VEL && !G6) ? 2 : 1) + XP * ((VEL && HAS_DX) ? 2 : 1);
     constexpr size_t smem = (size_t)2 * BUF * 16 + 256 * sizeof(int);
     auto kern = conv_mfma_kernel<MODE, VEL, HAS_DX, NI, G6>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        attr_done = true;
-    }
+    ensure_lds_limit((const void*)kern, smem);
     dim3 grid(ka.ntiles, ctiles, 1), block(256, 1, 1);
     hipLaunchKernelGGL(kern, grid, block, smem, s, ka);
 }

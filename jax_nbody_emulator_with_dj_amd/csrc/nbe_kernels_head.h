@@ -238,11 +238,7 @@ static int launch_h3n4(ConvKArgs ka, int ctiles, hipStream_t s) {
     static_assert(smem <= 160 * 1024, "LDS budget of one CU");
     if (ctiles != 1 || ka.cout_groups > 2 || (ka.flags & F_RES) || !ka.beta || ka.Dv % HN4_ZB != 0) return 1;
     if (ka.nchunk + ka.nskip > NBE_MAX_GROUPS) return 1;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)conv_h3n4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        attr_done = true;
-    }
+    ensure_lds_limit((const void*)conv_h3n4_kernel, smem);
     ka.tny = (ka.Hv + HP_ROWS - 1) / HP_ROWS;
     ka.tnx = (ka.Wv + HP_COLS - 1) / HP_COLS;
     ka.ntiles = (ka.Dv / HN4_ZB) * ka.tny * ka.tnx;

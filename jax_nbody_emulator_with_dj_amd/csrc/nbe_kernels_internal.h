@@ -1,6 +1,9 @@
 // Shared between nbe_kernels.hip (float32 path, data movement) and nbe_kernels_h3.hip (f16x3 path).
 #pragma once
 #include "nbe_kernels.h"
+#include <mutex>
+#include <set>
+#include <utility>
 
 namespace nbe {
 
@@ -48,6 +51,18 @@ struct ConvKArgs {
 __device__ __forceinline__ void dma16(const float* src, f32x4* dst_wave_base) {
     // 64 lanes x 16 B: LDS destination = wave-uniform base + lane*16 (hardware rule), source per lane.
     __builtin_amdgcn_global_load_lds((const NBE_GLB_AS void*)src, (NBE_LDS_AS void*)dst_wave_base, 16, 0, 0);
+}
+
+// Allow a kernel more than the default 64 KB of dynamic LDS: set once per (kernel, current device), from any thread.  The
+// result is not checked: a launch beyond the limit fails and surfaces through the callers' error checks.
+inline void ensure_lds_limit(const void* kernel, size_t bytes) {
+    static std::mutex mu;
+    static std::set<std::pair<const void*, int>> done;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.insert({kernel, dev}).second)
+        (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
 // XCD-aware tile order: blocks b and b+8 share an XCD (and its L2); give each XCD a contiguous run

@@ -99,7 +99,7 @@ struct WinoKArgs {
 template <bool SKIP, bool NOVEL, bool F16 = false>
 __global__ __launch_bounds__(512, 2) void conv_h3w_kernel(WinoKArgs a) {
     static_assert(!(F16 && NOVEL), "the float16 form has no displacement-only variant");
-    typedef HGGeom<false, true, false> G;
+    typedef HGGeom<false, true> G;
     constexpr int NW = 8, CT = 64, TAPU = G::TAPU, WGU = G::WG, XBASE = G::XBASE, MT = 4, NT = 2, NTILE = 8;
     constexpr int ZROW = G::LDS_UNITS;                           // 64 zeroed units behind the patch buffers (NBE_WINO_ZROW)
     f32x4* lds = lds_h3;
@@ -799,7 +799,7 @@ void launch_pack_h3w(const float* w_oidhw, int cout, int cin, int cin_pad, int c
 // f16: the float16 model's form (32-channel stages, no fused skip, residual in the epilogue)
 static int launch_h3w(const ConvKArgs& ka_in, const float* ww, const float* wws, long wws_set_floats, int ctiles, hipStream_t s,
                       bool novel = false, bool f16 = false) {
-    typedef HGGeom<false, true, false> G;
+    typedef HGGeom<false, true> G;
     constexpr size_t smem = (size_t)(G::LDS_UNITS + 64) * 16;   // + the zeroed kilobyte (NBE_WINO_ZROW)
     static_assert(smem <= 160 * 1024, "LDS budget of one CU");
     ConvKArgs ka = ka_in;
@@ -814,16 +814,6 @@ static int launch_h3w(const ConvKArgs& ka_in, const float* ww, const float* wws,
     if (ctiles != (ka.cout_groups + 7) / 8) return 1;
     // the raw planes are fetched with buffer loads (32-bit offsets): lane offset + hi -> lo plane distance stay below 2^32
     if (std::max(ka.in_pstride, ka.csplit < ka.nchunk ? ka.in2_pstride : 0L) * 16 + 16L * (HP_ROWS + 2) * ka.W >= (1L << 32) - (1L << 20)) return 1;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)conv_h3w_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        (void)hipFuncSetAttribute((const void*)conv_h3w_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        (void)hipFuncSetAttribute((const void*)conv_h3w_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        (void)hipFuncSetAttribute((const void*)conv_h3w_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        (void)hipFuncSetAttribute((const void*)conv_h3w_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        (void)hipFuncSetAttribute((const void*)conv_h3w_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        attr_done = true;
-    }
     WinoKArgs wa;
     wa.H = ka.H; wa.W = ka.W; wa.Dv = ka.Dv; wa.Hv = ka.Hv; wa.Wv = ka.Wv; wa.Ho = ka.Ho; wa.Wo = ka.Wo;
     wa.nchunk = ka.nchunk; wa.cout_groups = ka.cout_groups; wa.flags = ka.flags;
@@ -836,12 +826,9 @@ static int launch_h3w(const ConvKArgs& ka_in, const float* ww, const float* wws,
     const long rows8 = (long)HP_ROWS * ka.W * 16;                // novel: the "tangent" patch is the input eight rows further down
     wa.inv_scale = 1.0f / (f16 ? WINO_WSCALE_F16 : WINO_WSCALE);
     wa.r = ka.r; wa.dr = ka.dr; wa.res_pstride = ka.res_pstride;
-    {
-        // A/B (profiles/r02_ab_wino_zblock.txt): 0 = all pairs of the launch (z fastest) 1494 ms per box, 1 (x fastest) 1496,
-        // 2 / 4 / 8 / 16: 1479 / 1481 / 1477 / 1482
-        static const int zb = getenv("NBE_WINO_ZBLOCK") ? atoi(getenv("NBE_WINO_ZBLOCK")) : 8;
-        wa.zblock = zb > 0 ? std::min(zb, ka.Dv / 2) : ka.Dv / 2;
-    }
+    // z pairs per block of the tile order.  A/B (profiles/r02_ab_wino_zblock.txt): all pairs of the launch (z fastest) 1494 ms
+    // per box, 1 (x fastest) 1496, 2 / 4 / 8 / 16: 1479 / 1481 / 1477 / 1482
+    wa.zblock = std::min(8, ka.Dv / 2);
     wa.nskip = ka.nskip; wa.dws_delta = wws_set_floats * 4;
     // stage order: phase 0 = (xi 1 -> A, xi 2 -> B) per chunk, phase 1 = (xi 0 -> A, xi 3 -> B) per chunk
     static const int XI[2][2] = {{1, 2}, {0, 3}};
@@ -873,14 +860,13 @@ static int launch_h3w(const ConvKArgs& ka_in, const float* ww, const float* wws,
             WinoSrc& e = wa.st[4 * ka.nchunk + 2 * sc + ab];
             e.xa = x + off; e.xb = e.xa; e.dxd = novel ? rows8 : dx - x; e.w = (const char*)wws + (long)sc * G::TAPU * 16; e.psb = ps * 16; e.sb = 0.f; e.pad_ = 0;
         }
+    const bool skip = ka.nskip > 0;
+    if (novel) wa.dws_delta = 0;
+    auto kern = f16 ? (skip ? conv_h3w_kernel<true, false, true> : conv_h3w_kernel<false, false, true>)
+              : novel ? (skip ? conv_h3w_kernel<true, true> : conv_h3w_kernel<false, true>)
+              : (skip ? conv_h3w_kernel<true, false> : conv_h3w_kernel<false, false>);
+    ensure_lds_limit((const void*)kern, smem);
     dim3 grid(wa.ntiles * ctiles, 1, 1), block(512, 1, 1);
-    if (f16 && ka.nskip > 0) hipLaunchKernelGGL((conv_h3w_kernel<true, false, true>), grid, block, smem, s, wa);
-    else if (f16) hipLaunchKernelGGL((conv_h3w_kernel<false, false, true>), grid, block, smem, s, wa);
-    else if (novel) {
-        wa.dws_delta = 0;
-        if (ka.nskip > 0) hipLaunchKernelGGL((conv_h3w_kernel<true, true>), grid, block, smem, s, wa);
-        else hipLaunchKernelGGL((conv_h3w_kernel<false, true>), grid, block, smem, s, wa);
-    } else if (ka.nskip > 0) hipLaunchKernelGGL((conv_h3w_kernel<true, false>), grid, block, smem, s, wa);
-    else hipLaunchKernelGGL((conv_h3w_kernel<false, false>), grid, block, smem, s, wa);
+    hipLaunchKernelGGL(kern, grid, block, smem, s, wa);
     return 0;
 }

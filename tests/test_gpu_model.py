@@ -264,3 +264,44 @@ def test_full_width_c1_slice(engine_factory):
         d, v = e.forward(x, DZ, VF)
         print("mid64 %s: disp rel_l2 %.3e vel rel_l2 %.3e" % (prec, rel_l2(d, gold["net64_disp"]), rel_l2(v, gold["net64_vel"])))
         _check(d, v, gold["net64_disp"], gold["net64_vel"], "style-vel mid64 " + prec)
+
+
+def test_two_devices_in_one_process():
+    """Engines on devices 0 and 1 of one process, run side by side from two threads, give the one-device result bit for bit
+    on the default f16x3 path at production width (its kernels take more than 64 KB of LDS, a limit raised per kernel AND
+    device)."""
+    import os
+    import threading
+    import torch
+    from oracle import params as P
+    from jax_nbody_emulator_with_dj_amd.engine import Engine
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two visible devices")
+    gold = np.load(os.path.join(os.path.dirname(__file__), "golden", "golden_v1.npz"))
+    seed_p, seed_x, mid, d0, d1, d2 = (int(v) for v in gold["net64_meta"])
+    p = P.synthetic_params(seed=seed_p, mid_chan=mid)
+    x = np.random.default_rng(seed_x).standard_normal((1, 3, d0, d1, d2)).astype(np.float32)[0]
+
+    def run(e):
+        e.load_params(p, premodulated=False)
+        e.set_cosmology(OM, DZ)
+        return [a.copy() for a in e.forward(x, DZ, VF)]
+
+    e0 = Engine(device=0, mid_chan=mid, compute_vel=True, precision="f16x3")
+    e1 = None
+    try:
+        want = run(e0)                                               # one device in the process so far
+        e1 = Engine(device=1, mid_chan=mid, compute_vel=True, precision="f16x3")
+        got = {}
+        threads = [threading.Thread(target=lambda k=k, e=e: got.__setitem__(k, run(e))) for k, e in ((0, e0), (1, e1))]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        for k in (0, 1):
+            assert k in got, "device %d raised" % k
+            assert all(np.array_equal(g, w) for g, w in zip(got[k], want)), "device %d differs from the one-device run" % k
+    finally:
+        e0.close()
+        if e1 is not None:
+            e1.close()
