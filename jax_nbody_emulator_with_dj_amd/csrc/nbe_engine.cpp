@@ -499,8 +499,7 @@ static void prof_collect(nbe_ctx* c) {
 static std::string conv_name(const PackedW& pw, bool vel, bool has_dx, bool g6 = false, bool up8 = false) {
     if (up8) return vel ? "up_h3<8 parities,vel,dx>" : "up_h3<8 parities,novel>";
     const char* m = pw.mode == MODE_FLAT3 ? "FLAT3" : pw.mode == MODE_FLAT1 ? "FLAT1" : "DOWN";
-    const bool stem_on = !(getenv("NBE_STEM") && atoi(getenv("NBE_STEM")) == 0);
-    if (stem_on && pw.stem && !(vel && has_dx) && pw.mode == MODE_FLAT3) return vel ? "stem_h3<FLAT3,vel,nodx>" : "stem_h3<FLAT3,novel>";
+    if (pw.stem && !(vel && has_dx) && pw.mode == MODE_FLAT3) return vel ? "stem_h3<FLAT3,vel,nodx>" : "stem_h3<FLAT3,novel>";
     char b[96];
     if (g6 && prec_is_half(pw.prec)) snprintf(b, sizeof b, "%s<%s,vel,dx>", pw.prec == PREC_F16 ? "conv_h1g" : (pw.cout_t == 16 ? "conv_h3n" : "conv_h3g"), m);
     else if (g6) snprintf(b, sizeof b, "conv_mfma_g<%s,vel,dx,ni%d>", m, pw.ni);
@@ -514,8 +513,9 @@ static std::string conv_name(const PackedW& pw, bool vel, bool has_dx, bool g6 =
 // the float16 model's Winograd-z form (conv_h3w_kernel<., ., F16>): 32-channel stages
 static bool wino_f16_layer(int prec, bool vel, int cin_pad) { return prec == PREC_F16 && vel && cin_pad % 32 == 0 && cin_pad / 32 <= 8; }
 static bool wino_env_off() { return getenv("NBE_WINO") && atoi(getenv("NBE_WINO")) == 0; }   // A/B switch, read per launch
-static bool narrow_off() { return getenv("NBE_NARROW") && atoi(getenv("NBE_NARROW")) == 0; }   // A/B switch (set before the context is created)
-static bool narrow_tile(const Layer* L) { return L->pwn.w && !narrow_off(); }
+// f16-based arithmetic, Cin <= 64 and an input tangent wherever there is velocity: all eight parities of an up-sampling
+// in one launch (up_h3_kernel: the input is read once)
+static bool up8_launch(const nbe_ctx* c, const Layer& L, bool has_dx) { return prec_is_half(c->prec) && (!c->vel || has_dx) && L.pw.cin_pad <= 64; }
 
 // launch one convolution layer (or record it in a dry run)
 static int run_conv(nbe_ctx* c, const Layer& L, const ConvLaunch& cl_in, bool has_dx) {
@@ -528,7 +528,7 @@ static int run_conv(nbe_ctx* c, const Layer& L, const ConvLaunch& cl_in, bool ha
         if (!((g6 || nov) && c->fuse && L.fskip)) return fail("internal error: fused skip requested for %s/%s", L.block.c_str(), L.layer.c_str());
         cl.bias = L.bias_f;
     }
-    const PackedW& pw = (g6 && L.kind == 0 && narrow_tile(&L)) ? L.pwn : L.pw;
+    const PackedW& pw = (g6 && L.kind == 0 && L.pwn.w) ? L.pwn : L.pw;
     // Winograd along z (conv_h3w_kernel): gauged wide 3x3x3 launches without a fused skip or residual, on an even number
     // of output planes (the conditions of launch_h3w).  NBE_WINO=0 is the A/B switch (read per launch: tests flip it).
     // (the float16 model's form adds the residual in its epilogue: its blocks run their skips as launches of their own)
@@ -625,7 +625,7 @@ static int resblock(nbe_ctx* c, const char* name, const Tensor& x, bool has_dx, 
     org_conv(x, 2, og);
     {
         ConvLaunch cl; cl.in = h.p; cl.Dv = D - 4; cl.Hv = s.p.H - 2 * pad; cl.Wv = s.p.W - 2 * pad; cl.out = inner(s);
-        if (fused) { cl.sk = x.p; cl.sk_off = sk_off; cl.skw = narrow_tile(L1) ? &Ls->pwn : &Ls->pw; cl.flags = (final_act ? F_ACT : 0) | (has_dx ? 0 : F_SKIP_NODX); }
+        if (fused) { cl.sk = x.p; cl.sk_off = sk_off; cl.skw = L1->pwn.w ? &Ls->pwn : &Ls->pw; cl.flags = (final_act ? F_ACT : 0) | (has_dx ? 0 : F_SKIP_NODX); }
         else { cl.res = inner(s); cl.flags = F_RES | (final_act ? F_ACT : 0); }
         if (run_conv(c, *L1, cl, true)) return 1;
         if (final_act) probe_act(c, *L1, cl.out, 0, og, cl.Dv, cl.Hv, cl.Wv, pad != 0);
@@ -671,7 +671,7 @@ static int resblock_part(nbe_ctx* c, const char* name, const Tensor& x, const Te
     fill_halo(c, hv);
     {
         ConvLaunch cl; cl.in = zview(h, js, ns + 2).p; cl.Dv = ns; cl.Hv = s.p.H - 2 * pad; cl.Wv = s.p.W - 2 * pad; cl.out = inner(sv);
-        if (fused) { cl.sk = xs.p; cl.sk_off = sk_off; cl.skw = narrow_tile(L1) ? &Ls->pwn : &Ls->pw; cl.flags = (final_act ? F_ACT : 0) | (has_dx ? 0 : F_SKIP_NODX);
+        if (fused) { cl.sk = xs.p; cl.sk_off = sk_off; cl.skw = L1->pwn.w ? &Ls->pwn : &Ls->pw; cl.flags = (final_act ? F_ACT : 0) | (has_dx ? 0 : F_SKIP_NODX);
                      if (x2) { cl.sk2 = zview(*x2, js, ns + 4).p; cl.sk_split_ch = c->mid; } }
         else { cl.res = inner(sv); cl.flags = F_RES | (final_act ? F_ACT : 0); }
         if (run_conv(c, *L1, cl, true)) return 1;
@@ -711,9 +711,7 @@ static int upblock(nbe_ctx* c, const char* name, const Tensor& x, const Tensor& 
     const int Hx = x.p.H - 2 * xcrop, Wx = x.p.W - 2 * xcrop;
     if (cat.p.D != 2 * x.p.D || cat.p.H - 2 * cat.pad != 2 * Hx || cat.p.W - 2 * cat.pad != 2 * Wx)
         return fail("internal: concat geometry mismatch in %s", name);
-    // f16-based arithmetic and Cin <= 64: all eight parities in one launch (up_h3_kernel: the input is read once)
-    const bool up8_off = getenv("NBE_UP8") && atoi(getenv("NBE_UP8")) == 0;                 // A/B switch
-    const bool up8 = prec_is_half(c->prec) && L->pw.cin_pad <= 64 && !up8_off;
+    const bool up8 = up8_launch(c, *L, true);
     const int out_g0 = g0 >= 0 ? g0 : c->mid / (c->prec == PREC_F16 ? 8 : 4);
     for (int p = 0; p < (up8 ? 1 : 8); ++p) {
         ConvLaunch cl; cl.in = x.p; cl.in_off = ((int64_t)xcrop * x.p.W + xcrop);
@@ -1447,10 +1445,8 @@ static int run_tile(nbe_ctx* c, const float* box, int Db, int Hb, int Wb, int o0
     const int geo[18] = {Db, Hb, Wb, o0, o1, o2, D, H, W, out_dtype, OD, OH, OW, a0, a1, a2, c->slab, c->prec};
     memcpy(k.geo, geo, sizeof geo);
     k.f[0] = Dz; k.f[1] = vel_fac; k.f[2] = c->act_scale;
-    // (the A/B switches that launchers read per launch are part of the key: a captured graph holds the kernels they chose)
-    auto sw = [](const char* n, int bit) { const char* e = getenv(n); return (e && atoi(e) == 0) ? (1 << bit) : 0; };
-    k.epoch = c->epoch; k.flags = (c->pyx ? 1 : 0) | (c->pz ? 2 : 0) | (c->gauge_active ? 4 : 0) | (c->fuse ? 8 : 0) |
-              sw("NBE_WINO", 4) | sw("NBE_UP8", 5) | sw("NBE_STEM", 6) | sw("NBE_H3G_TALL", 7) | sw("NBE_NARROW", 8) | sw("NBE_HEAD4", 9);
+    // (the A/B switch that launchers read per launch is part of the key: a captured graph holds the kernels it chose)
+    k.epoch = c->epoch; k.flags = (c->pyx ? 1 : 0) | (c->pz ? 2 : 0) | (c->gauge_active ? 4 : 0) | (c->fuse ? 8 : 0) | (wino_env_off() ? 16 : 0);
     nbe_ctx::GraphVal& g = c->graphs[k];
     g.used = ++c->graph_clock;
     if (!g.exec && g.seen++ == 0) {                              // first time: eager
@@ -1561,8 +1557,7 @@ static int pack_wino(nbe_ctx* c) {
 // (conv_h3w_kernel<SKIP, NOVEL>), as the velocity networks do through wire_gauge
 static int wire_novel(nbe_ctx* c) {
     c->novel_fuse = false;
-    static const bool no_fuse = getenv("NBE_FUSE") && atoi(getenv("NBE_FUSE")) == 0;            // A/B switch
-    if (c->vel || c->prec != PREC_F16X3 || no_fuse) return 0;
+    if (c->vel || c->prec != PREC_F16X3) return 0;
     for (const char* b : kBlocks) {
         if (!strncmp(b, "down_", 5) || !strncmp(b, "up_", 3)) continue;
         auto i1 = c->layers.find(std::string(b) + "/conv_1"), is = c->layers.find(std::string(b) + "/skip");
@@ -1618,15 +1613,14 @@ static int wire_gauge(nbe_ctx* c) {
         if (strcmp(b, "conv_l00")) { L0->g6 = true; Ls->a_in = L0->alpha; }   // conv_l00 reads the input field: no tangent
         // the skip can run inside conv_1 (conv_h3g_kernel<false>): f16x3, the block input has a tangent, the wide tile,
         // and the groups of both fit the kernel's table
-        static const bool no_fuse = getenv("NBE_FUSE") && atoi(getenv("NBE_FUSE")) == 0;        // A/B switch
-        if (c->prec == PREC_F16X3 && !no_fuse && (!L1->pwn.w || Ls->pwn.dw) &&
+        if (c->prec == PREC_F16X3 && (!L1->pwn.w || Ls->pwn.dw) &&
             3 * (L1->pw.cin_pad / 16) + Ls->pw.cin_pad / 16 <= NBE_MAX_GROUPS) {
             L1->fskip = Ls; Ls->b_sub = L1->beta;
             const int nb = L1->pw.ctiles * 32 * L1->pw.ni;
             HIPCHK(hipMalloc((void**)&L1->bias_f, nb * 4));
         }
         // float16 model (style path): the skip runs inside conv_h3w_kernel<SKIP, ., F16> wherever conv_1's launch has that form
-        if (c->prec == PREC_F16 && !no_fuse && L1->pw.ww && Ls->pw.ww && Ls->dwn_f && L1->pw.ctiles == Ls->pw.ctiles &&
+        if (c->prec == PREC_F16 && L1->pw.ww && Ls->pw.ww && Ls->dwn_f && L1->pw.ctiles == Ls->pw.ctiles &&
             2 * (Ls->pw.cin_pad / 32) <= 16) {                   // NBE_MAX_WSKIP (nbe_kernels_wino.h)
             L1->fskip = Ls; Ls->b_sub = L1->beta;
             const int nb = L1->pw.ctiles * 32 * L1->pw.ni;
@@ -2894,8 +2888,7 @@ static int test_layer(nbe_ctx* c, int kind, int crop, int flags, const float* x,
         else if (kind == 1) { cl.in_off = ((int64_t)crop * H + crop) * W + crop; cl.Dv = OD; cl.Hv = OH; cl.Wv = OW; rc = run_conv(c, L, cl, has_dx); }
         else if (kind == 2) { cl.Dv = OD; cl.Hv = OH; cl.Wv = OW; rc = run_conv(c, L, cl, has_dx); }
         else {
-            // as upblock(): one launch for all eight parities where up_h3_kernel applies
-            const bool up8 = prec_is_half(c->prec) && (!vel || has_dx) && pw.cin_pad <= 64 && !(getenv("NBE_UP8") && atoi(getenv("NBE_UP8")) == 0);
+            const bool up8 = up8_launch(c, L, has_dx);          // as upblock()
             for (int p = 0; p < (up8 ? 1 : 8) && !rc; ++p) {
                 ConvLaunch u = cl; u.Dv = D; u.Hv = H; u.Wv = W; u.osz = 2; u.oz = (p >> 2) & 1; u.oy = (p >> 1) & 1; u.ox = p & 1;
                 u.set = up8 ? -1 : p;

@@ -1103,35 +1103,33 @@ static int launch_h3q(ConvKArgs ka, int ctiles, hipStream_t s) {
 // ([group][tap][unit][16 couts][8 ch], packed with cout_t = 16), a group of weights is 9 KB.  Each activation operand
 // then feeds one MFMA instead of two and the patch DMA is spread over a quarter of the MFMAs: the variant is bound by
 // the L2 -> LDS stream (about 2650 cycles per group against 1800 of MFMA), i.e. ~3.8 x faster than the wide tile.
-// TALL (wide tile only): the wave tile is 64 couts x one patch row (4 x 2 MFMA tiles) instead of 32 couts x two rows
-// (2 x 4).  A product has two weight operands (hi, lo) but four activation operands (x, dx~, hi and lo each), so per tap
-// pair a wave reads 2 * MT + 4 * NT 16-byte operand sets from LDS: 20 for 2 x 4, 16 for 4 x 2 -- and on this chip, which
-// runs the kernel against its power limit, an LDS operand read costs 0.58 of an MFMA's energy
-// (tools/micro/mfma_power.hip, profiles/r02_mfma_power.txt), so bytes per MFMA are time.
+// Wide tile: the wave tile is 64 couts x one patch row (4 x 2 MFMA tiles).  A product has two weight operands (hi, lo)
+// but four activation operands (x, dx~, hi and lo each), so per tap pair a wave reads 2 * MT + 4 * NT 16-byte operand
+// sets from LDS: 16 for 4 x 2 against 20 for the 2 x 4 tile it replaced -- and on this chip, which runs the kernel
+// against its power limit, an LDS operand read costs 0.58 of an MFMA's energy (tools/micro/mfma_power.hip,
+// profiles/r02_mfma_power.txt), so bytes per MFMA are time.
 // (A 4 x 4 wave tile with one wave per SIMD read still fewer operands per MFMA but was slower: DESIGN.md section 4c.)
-template <bool NARROW, bool TALL = false>
+// In both geometries wave w owns row w of the 8 x 32 patch.
+template <bool NARROW>
 struct HGGeom {
-    static_assert(!(NARROW && TALL), "one geometry at a time");
     static constexpr int CT = NARROW ? 16 : 64;             // couts per tile = rows of one weight unit in LDS
     static constexpr int TAPU = 4 * CT;                     // 16-byte units per tap
     static constexpr int WG = 9 * TAPU;                     // units of one group's weights (set w)
     static constexpr int XBASE = 2 * WG;                    // the two patch buffers follow the two weight buffers
     static constexpr int LDS_UNITS = XBASE + 2 * HQ_XB;
-    static constexpr int MT = NARROW ? 1 : (TALL ? 4 : 2), NT = (NARROW || TALL) ? 2 : 4, NTILE = MT * NT;   // MFMA tiles of a wave
+    static constexpr int MT = NARROW ? 1 : 4, NT = 2, NTILE = MT * NT;   // MFMA tiles of a wave
     static constexpr int NW = 8;                            // waves per workgroup
     static constexpr int XS = 24 / NW;                      // patch DMA slots per wave and tensor (24 wave-instructions per tensor)
-    static constexpr int SPP = NTILE == 16 ? 4 : 2;         // DMA slots a product can carry (one after every fourth MFMA)
-    static constexpr bool ROWW = NARROW || TALL;            // a wave owns ONE row of the 8 x 32 patch (else two)
+    static constexpr int SPP = 2;                           // DMA slots a product can carry
     static constexpr int NWI = WG / 64;                     // weight DMA wave-instructions per group: 36 / 9
-    static constexpr int NWS = (NWI + NW - 1) / NW;         // ... slots per wave: 5 / 2 / 9
+    static constexpr int NWS = (NWI + NW - 1) / NW;         // ... slots per wave: 5 / 2
     static_assert(NWS + 2 * XS <= 6 * SPP, "the first tap pair carries the whole DMA of the next group");
 };
 static_assert(HGGeom<false>::XBASE == HQ_XBASE, "the two weight buffers fill exactly what conv_h3q_kernel uses for four");
 
-template <bool NARROW, bool TALL>
+template <bool NARROW>
 __global__ __launch_bounds__(512, 2) void conv_h3g_kernel(ConvKArgs a) {
-    typedef HGGeom<NARROW, TALL> G;
-    constexpr bool ROWW = G::ROWW;
+    typedef HGGeom<NARROW> G;
     constexpr int NW = G::NW, XS = G::XS, SPP = G::SPP;
     constexpr int CT = G::CT, TAPU = G::TAPU, WGU = G::WG, XBASE = G::XBASE, MT = G::MT, NT = G::NT, NTILE = G::NTILE;
     constexpr int NWS = G::NWS;
@@ -1147,7 +1145,6 @@ __global__ __launch_bounds__(512, 2) void conv_h3g_kernel(ConvKArgs a) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 15, q = lane >> 4, kh = q & 1, ks = q >> 1;
-    const int it = wave & 1, jq = wave >> 1;
 
     // cout tile fastest, then z (as in conv_h3q_kernel): the workgroups of one patch that differ only in their 64 couts
     // run side by side on one XCD and share the patch through its L2 instead of fetching it from HBM once per cout tile
@@ -1204,7 +1201,7 @@ __global__ __launch_bounds__(512, 2) void conv_h3g_kernel(ConvKArgs a) {
             dma16s((tensor ? nx.dx : nx.x) + (long)pl * nx.psb, xoff[t],
                    lds + XBASE + buf * HQ_XB + tensor * HQ_XT + pl * HQ_PP + k * 64);
     };
-    auto dma_slot = [&](int k, int buf) {                        // slot k of the NWS + 2 XS (11 / 8 / 21) of the group in `nx`
+    auto dma_slot = [&](int k, int buf) {                        // slot k of the NWS + 2 XS (11 / 8) of the group in `nx`
         if (k < NWS) dma_w(buf, k);
         else if (k < NWS + XS) dma_x(0, k - NWS, buf);
         else if (k < NWS + 2 * XS) dma_x(1, k - NWS - XS, buf);
@@ -1224,10 +1221,8 @@ __global__ __launch_bounds__(512, 2) void conv_h3g_kernel(ConvKArgs a) {
         asm("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(A), "v"(B));
     };
 
-    const int rowc = ROWW ? 0 : 32 * it;                         // first cout row of this wave inside the tile
-    const int rowp = ROWW ? wave : 2 * jq;                       // first patch row of this wave
-    const int aP = (ks * 4 + 2 * kh) * CT + rowc + c;
-    const int bB = (2 * kh) * HQ_PP + rowp * HP_RS + c;
+    const int aP = (ks * 4 + 2 * kh) * CT + c;
+    const int bB = (2 * kh) * HQ_PP + wave * HP_RS + c;
     const int bP1 = bB + ks, bP32 = bB + 32 * ks;
     auto LA = [&](half8 (&r)[MT], int idx) {
 #pragma unroll
@@ -1235,7 +1230,7 @@ __global__ __launch_bounds__(512, 2) void conv_h3g_kernel(ConvKArgs a) {
     };
     auto LB = [&](half8 (&r)[NT], int idx) {
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) r[nt] = L8[idx + (ROWW ? 0 : (nt >> 1)) * HP_RS + 16 * (ROWW ? nt : (nt & 1))];
+        for (int nt = 0; nt < NT; ++nt) r[nt] = L8[idx + 16 * nt];
     };
     // one product on the wave tile: NTILE MFMAs; slot >= 0: DMA slots `slot`, `slot + 1` of group gn, one after each
     // MFMA row (wide) or both after the product (narrow)
@@ -1294,9 +1289,9 @@ __global__ __launch_bounds__(512, 2) void conv_h3g_kernel(ConvKArgs a) {
         const int wbn = WGU - wb, xbn = XBASE + nb * HQ_XB;
         half8 a1w[MT], a0[MT], b1x[NT], b1d[NT];
         // single tap 4 = (dy 1, dx 1): the lane-group halves select the PART: [wh|wl].[xl|xh] and [0|wh].[xl|xh]
-        const int aS1 = wb + 4 * TAPU + (2 * kh + ks) * CT + rowc + c;
-        const int aS0 = wb + 4 * TAPU + (2 * kh) * CT + rowc + c;
-        const int bS1 = xb + (2 * kh + 1 - ks) * HQ_PP + rowp * HP_RS + c + SH4;
+        const int aS1 = wb + 4 * TAPU + (2 * kh + ks) * CT + c;
+        const int aS0 = wb + 4 * TAPU + (2 * kh) * CT + c;
+        const int bS1 = xb + (2 * kh + 1 - ks) * HQ_PP + wave * HP_RS + c + SH4;
 
         pair(0, nb, px, wb, xb + bP1,                                                  // taps (0,1) + the DMA of group g+1
              [&] { LB(xl, xb + 2 + bP32 + HQ_PP); }, [&] { LA(wh, wb + 2 * TAPU + aP); }, [&] { LB(xh, xb + 2 + bP32); },
@@ -1342,8 +1337,8 @@ __global__ __launch_bounds__(512, 2) void conv_h3g_kernel(ConvKArgs a) {
             const int nb = (g + 1) & 1;
             const int wb = (g & 1) * WGU, xb = XBASE + (g & 1) * HQ_XB;
             half8 a1w[MT], a0[MT], a1d[MT], a0d[MT], b1x[NT], b1d[NT];
-            const int aS1 = wb + (2 * kh + ks) * CT + rowc + c, aS0 = wb + (2 * kh) * CT + rowc + c;
-            const int bS1 = xb + (2 * kh + 1 - ks) * HQ_PP + rowp * HP_RS + c + SH4;
+            const int aS1 = wb + (2 * kh + ks) * CT + c, aS0 = wb + (2 * kh) * CT + c;
+            const int bS1 = xb + (2 * kh + 1 - ks) * HQ_PP + wave * HP_RS + c + SH4;
             const half8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
             LA(a1w, aS1); LB(b1x, bS1); LA(a0, aS0); LB(b1d, bS1 + HQ_XT);
 #pragma unroll
@@ -1379,7 +1374,7 @@ __global__ __launch_bounds__(512, 2) void conv_h3g_kernel(ConvKArgs a) {
         bool ook[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            const int yy = y0 + rowp + (ROWW ? 0 : (nt >> 1)), xx = x0 + 16 * (ROWW ? nt : (nt & 1)) + c;
+            const int yy = y0 + wave, xx = x0 + 16 * nt + c;
             ook[nt] = yy < a.Hv && xx < a.Wv;
             o[nt] = ook[nt] ? (z * a.Ho + yy) * a.Wo + xx : z * a.Ho * a.Wo;
         }
@@ -1387,7 +1382,7 @@ __global__ __launch_bounds__(512, 2) void conv_h3g_kernel(ConvKArgs a) {
         // (loads first), then the tiles -- all MT rows at once do not fit the registers of the 4 x 2 wave tile
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            int unit = ct * (CT / 8) + (ROWW ? 0 : 4 * it) + 2 * mt + ks;
+            int unit = ct * (CT / 8) + 2 * mt + ks;
             const bool uok = unit < a.cout_groups;
             if (!uok) unit = a.cout_groups - 1;
             const f32x4 bv = *(const f32x4*)(a.bias + unit * 8 + 4 * kh);
@@ -1458,12 +1453,12 @@ __global__ __launch_bounds__(512, 2) void conv_h3g_kernel(ConvKArgs a) {
 #undef NBE_STAMP
 }
 
-template <bool NARROW, bool TALL>
+template <bool NARROW>
 static int launch_h3g(ConvKArgs ka, int ctiles, hipStream_t s) {
-    typedef HGGeom<NARROW, TALL> G;
+    typedef HGGeom<NARROW> G;
     constexpr size_t smem = (size_t)G::LDS_UNITS * 16;
     static_assert(smem <= 160 * 1024, "LDS budget of one CU");
-    ensure_lds_limit((const void*)conv_h3g_kernel<NARROW, TALL>, smem);
+    ensure_lds_limit((const void*)conv_h3g_kernel<NARROW>, smem);
     ka.tny = (ka.Hv + HP_ROWS - 1) / HP_ROWS;
     ka.tnx = (ka.Wv + HP_COLS - 1) / HP_COLS;
     ka.ntiles = ka.Dv * ka.tny * ka.tnx;
@@ -1487,7 +1482,7 @@ static int launch_h3g(ConvKArgs ka, int ctiles, hipStream_t s) {
     }
     ka.dws_delta = nskip ? (const char*)ka.dws - (const char*)ka.ws : 0;
     dim3 grid(ka.ntiles * ctiles, 1, 1), block(G::NW * 64, 1, 1);
-    hipLaunchKernelGGL((conv_h3g_kernel<NARROW, TALL>), grid, block, smem, s, ka);
+    hipLaunchKernelGGL((conv_h3g_kernel<NARROW>), grid, block, smem, s, ka);
     return 0;
 }
 
@@ -2089,8 +2084,7 @@ __global__ __launch_bounds__(256) void pack_stem_kernel(const float* __restrict_
 int launch_conv_h3(const PackedW& pw, const ConvKArgs& ka, bool vel, bool has_dx, hipStream_t s) {
     const int ct = pw.ctiles;
     const bool split = pw.prec == PREC_F16X3;
-    const bool stem_on = !(getenv("NBE_STEM") && atoi(getenv("NBE_STEM")) == 0);   // A/B switch, default on (read per launch: tests flip it)
-    if (stem_on && ka.stem_w && !(vel && has_dx) && pw.mode == MODE_FLAT3 && ka.in_off == 0 && ka.osz == 1 &&
+    if (ka.stem_w && !(vel && has_dx) && pw.mode == MODE_FLAT3 && ka.in_off == 0 && ka.osz == 1 &&
         !(ka.flags & F_RES) && ka.nskip == 0 && !ka.beta) {
         if (split) return vel ? launch_stem<true>(ka, s) : launch_stem<false>(ka, s);
         return vel ? launch_stem<true, false>(ka, s) : launch_stem<false, false>(ka, s);
@@ -2106,14 +2100,12 @@ int launch_conv_h3(const PackedW& pw, const ConvKArgs& ka, bool vel, bool has_dx
     if (ka.beta) {                                               // gauged input tangent: only conv_h3g_kernel reads it
         if (!(pw.mode == MODE_FLAT3 && vel && has_dx && ka.in_off == 0 && ka.osz == 1)) return 1;   // no gauged kernel
         if (split) {
-            const bool tall = !(getenv("NBE_H3G_TALL") && atoi(getenv("NBE_H3G_TALL")) == 0);   // A/B switch, default on (read per launch)
             if (pw.cout_t == 16) {                              // the head convolution: four output planes per workgroup where the launch allows
-                const bool head4 = !(getenv("NBE_HEAD4") && atoi(getenv("NBE_HEAD4")) == 0);   // A/B switch, default on (read per launch)
-                if (head4 && launch_h3n4(ka, ct, s) == 0) return 0;
-                return launch_h3g<true, false>(ka, ct, s);
+                if (launch_h3n4(ka, ct, s) == 0) return 0;
+                return launch_h3g<true>(ka, ct, s);
             }
             if (ka.ww && launch_h3w(ka, ka.ww, ka.wws, ka.wws_set_floats, ct, s) == 0) return 0;     // Winograd along z; 1: no such form for this launch
-            return tall ? launch_h3g<false, true>(ka, ct, s) : launch_h3g<false, false>(ka, ct, s);
+            return launch_h3g<false>(ka, ct, s);
         }
         if (ka.ww && launch_h3w(ka, ka.ww, ka.wws, ka.wws_set_floats, ct, s, false, true) == 0) return 0;   // float16 model: Winograd along z
         return launch_h2q<false, true>(ka, ct, s);

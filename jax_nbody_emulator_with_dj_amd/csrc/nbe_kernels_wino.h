@@ -24,7 +24,7 @@
 //   operand).  All three products of a float32 product then land in the same float32 accumulator; the epilogue
 //   multiplies by 2^-14.
 //   => 128 accumulator registers hold 64 couts x 32 positions x 2 planes x (y, dy): the wave tile, LDS image and operand
-//   reads per MFMA of conv_h3g_kernel<false, TALL>.
+//   reads per MFMA of conv_h3g_kernel<false>.
 // * The transformed planes V = a +- b are built by the workgroup itself: each wave loads its share of the two raw
 //   patches into registers (16 B per lane and part), adds them part-wise in packed f16 (TwoSum for the hi parts' rounding
 //   error: xf_step) and writes the result into the LDS patch buffer of the NEXT stage in the layout the B operands are read in.  Weights still arrive by
@@ -99,7 +99,7 @@ struct WinoKArgs {
 template <bool SKIP, bool NOVEL, bool F16 = false>
 __global__ __launch_bounds__(512, 2) void conv_h3w_kernel(WinoKArgs a) {
     static_assert(!(F16 && NOVEL), "the float16 form has no displacement-only variant");
-    typedef HGGeom<false, true> G;
+    typedef HGGeom<false> G;
     constexpr int NW = 8, CT = 64, TAPU = G::TAPU, WGU = G::WG, XBASE = G::XBASE, MT = 4, NT = 2, NTILE = 8;
     constexpr int ZROW = G::LDS_UNITS;                           // 64 zeroed units behind the patch buffers (NBE_WINO_ZROW)
     f32x4* lds = lds_h3;
@@ -799,7 +799,7 @@ void launch_pack_h3w(const float* w_oidhw, int cout, int cin, int cin_pad, int c
 // f16: the float16 model's form (32-channel stages, no fused skip, residual in the epilogue)
 static int launch_h3w(const ConvKArgs& ka_in, const float* ww, const float* wws, long wws_set_floats, int ctiles, hipStream_t s,
                       bool novel = false, bool f16 = false) {
-    typedef HGGeom<false, true> G;
+    typedef HGGeom<false> G;
     constexpr size_t smem = (size_t)(G::LDS_UNITS + 64) * 16;   // + the zeroed kilobyte (NBE_WINO_ZROW)
     static_assert(smem <= 160 * 1024, "LDS budget of one CU");
     ConvKArgs ka = ka_in;
