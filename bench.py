@@ -2,7 +2,7 @@
 """Headline benchmark: output voxels/s of process_box (displacement + velocity) on a 512^3 box,
 ndiv=(4,4,4), StyleNBodyEmulatorVelCore, float32, on N MI355X of one node.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -10,9 +10,14 @@ A "step" is one pass of process_box over the whole box (64 sub-boxes of 224^3 ->
 merges into the largest tiles whose workspace fits the card -- ONE tile on a free 288 GB MI355X, its two
 full-resolution levels run in z-slabs and, the tile being the periodic box itself, without halo recompute -- when that
 is exact; --max-tile 256 / 0 restrict it to 256^3 tiles / disable it), with the input box and
-the output boxes resident in HBM.  Arithmetic: float32-equivalent f16x3 split MFMA by default (`value`); the
-strict float32 MFMA path is timed on the same box and reported under "strict_f32".  Weights are synthetic (seeded; the pretrained blob is not
-available), which changes neither the FLOPs nor the bytes.  Rank 0 prints ONE JSON line.
+the output boxes resident in HBM.  Arithmetic: float32-equivalent f16x3 split MFMA by default (`value`).  Weights are
+synthetic (seeded; the pretrained blob is not available), which changes neither the FLOPs nor the bytes.  Rank 0 prints
+ONE JSON line.
+
+A plain run sets up, warms up, times the steps (with the per-kernel roofline of those same steps), writes --dump-outputs
+and prints.  --full (one GPU) then also measures, on the same box and in the same process: the host-array call
+("host_path"), the strict float32 MFMA path ("strict_f32"), BASELINE configs 1 and 2 ("baseline_configs_1_2") and the CPU
+baseline ("cpu_baseline"); --no-host-path, --no-strict, --no-small-configs and --no-cpu-baseline drop one of them.
 
 N > 1: the box is sharded as bricks over the ranks (jax_nbody_emulator_with_dj_amd/sharding.py) -- z-slabs whenever a
 slab is at least 48 planes deep: per step each rank exchanges with its two z neighbours 4 planes of raw input, 6 planes of
@@ -105,7 +110,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--size", type=int, default=512, help="box side (debug; the headline is 512)")
     ap.add_argument("--ndiv", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the passes that take runs of their own (one GPU): host_path, "
+                         "strict_f32, baseline_configs_1_2 and cpu_baseline; a plain run is the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-vel", action="store_true")
     ap.add_argument("--max-tile", type=int, default=512,
                     help="cap on the internal tile edge: sub-boxes are merged into the largest tile that fits the "
@@ -115,9 +123,9 @@ def main():
                     help="f16x3 (default): float32-equivalent split-f16 MFMA, 3 MFMAs per product, f32 accumulate, "
                          "whole-network error vs the float64 oracle equal to or below the strict path's; "
                          "f32: strict float32 MFMA")
-    ap.add_argument("--no-strict", action="store_true", help="skip the strict-f32 reference pass")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the host-array (NumPy in / NumPy out) pass")
-    ap.add_argument("--no-small-configs", action="store_true", help="skip BASELINE configs 1 and 2 (128^3 cases) beside the headline")
+    ap.add_argument("--no-strict", action="store_true", help="with --full: skip the strict-f32 reference pass")
+    ap.add_argument("--no-host-path", action="store_true", help="with --full: skip the host-array (NumPy in / NumPy out) pass")
+    ap.add_argument("--no-small-configs", action="store_true", help="with --full: skip BASELINE configs 1 and 2 (128^3 cases)")
     ap.add_argument("--no-profile", action="store_true",
                     help="no per-kernel HIP events in the timed region (no roofline object): the tiles then replay from "
                          "captured hipGraphs, which profiling turns off -- for the graph A/B (NBE_GRAPH=0 / 1)")
@@ -335,11 +343,12 @@ def main():
                 "input": "pageable NumPy float32", "output": "NumPy float32 (pinned pool)", "finite": okh,
                 "equals_resident_result": same}
 
+    extras = args.full and world == 1              # a plain run stops at the headline
     host = None
-    if world == 1 and not args.no_host_path:
+    if extras and not args.no_host_path:
         host = measure_host_path(max(1, min(args.steps, 3)))
     strict = None
-    if args.precision != "f32" and world == 1 and not args.no_strict:
+    if extras and args.precision != "f32" and not args.no_strict:
         strict = measure("f32", 1, 1)             # the strict-float32 MFMA path on the same box, for reference
 
     def measure_small_configs(reps=5):
@@ -377,7 +386,7 @@ def main():
             eng.close()
         return out
 
-    small = measure_small_configs() if (world == 1 and not args.no_small_configs) else None
+    small = measure_small_configs() if (extras and not args.no_small_configs) else None
 
     if rank == 0:
         vox = float(N) ** 3
@@ -419,7 +428,7 @@ def main():
                                  "dtype": "f32", "finite": sok, "roofline": roofline(sprof, "f32") if sprof else None}
         if small is not None:
             out["baseline_configs_1_2"] = small
-        if world == 1 and not args.no_cpu_baseline:
+        if extras and not args.no_cpu_baseline:
             avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
             threads = min(avail, 16)        # the 1-GPU box's CPU share; more BLAS threads only oversubscribe
             out["cpu_baseline"] = cpu_baseline(threads)
