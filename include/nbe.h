@@ -263,6 +263,31 @@ int nbe_deconvolve_mas(void* field, const int64_t res[3], int worder, void* stre
  * 2^(e_s - 32).  Integer sums: reproducible bit for bit.  2 <= n <= 4096. */
 int nbe_power_spectrum(const void* a, const void* b, int64_t n, void* binmax, void* sums, void* stream);
 
+/* Minkowski functionals of an n^3 float32 field, replacing compute_minkowski_functionals and its
+ * cubical-complex counting (scripts/utils.py:652-763).  For a threshold t the excursion set is the set M of voxels with
+ * w >= t (indices mod n).  Voxel v owns the elements at its low corner: its cube, the face towards v - e_a and the edge
+ * along a through v, for each axis a, and its vertex.  Counts: n3 = |M|; n2 = sum over a of #{v : v or v - e_a in M};
+ * n1 = sum over a of #{v : v, v - e_b, v - e_c or v - e_b - e_c in M}, {b, c} the other two axes; n0 = #{v : some v - s in
+ * M, s in {0,1}^3}.  An element is in the set iff the largest w of its voxels is >= t, so one histogram of element maxima
+ * per functional, binned by upper_bound over the sorted thresholds, holds the counts of every threshold at once. */
+#define NBE_MF_MAX_N 2048
+#define NBE_MF_MAX_THRESHOLDS 1024
+#define NBE_MOMENTS_WORDS 2050
+/* replaces np.mean / np.std of compute_minkowski_functionals (scripts/utils.py:652-763): the mean and population standard
+ * deviation of the field in float64, by two passes (the sum, then the sum of squared deviations from that mean) over a
+ * partition of the voxels that depends on n only, reduced in a fixed order: bitwise reproducible.  moments =
+ * NBE_MOMENTS_WORDS float64: out [0] mean, [1] std; the rest is scratch.  1 <= n <= NBE_MF_MAX_N. */
+int nbe_field_moments(const void* field, int64_t n, void* moments, void* stream);
+/* replaces the per-threshold counting loop of compute_minkowski_functionals (scripts/utils.py:652-763): thresholds =
+ * nthresholds (T, 1 .. NBE_MF_MAX_THRESHOLDS) float32 sorted ascending; moments = NULL for w = x, else the output of
+ * nbe_field_moments, standardizing w = (x - float(mean)) / float(std) (float32, correctly rounded; w = 0 where
+ * float(std) = 0).  counts = 4 (T+1) + 1 int64, ZEROED by the caller.  Out: counts[f (T+1) + b] = the elements of kind f
+ * (0 vertices, 1 edges, 2 faces, 3 cubes) whose largest bin is b, bin(w) = #{thresholds <= w}; the count of f at sorted
+ * threshold k is the sum over b > k.  counts[4 (T+1)] = voxels whose x is not finite (their counts are meaningless).
+ * Integer sums: reproducible bit for bit.  1 <= n <= NBE_MF_MAX_N. */
+int nbe_minkowski_counts(const void* field, int64_t n, const void* thresholds, int nthresholds, const void* moments,
+                         void* counts, void* stream);
+
 /* ---- test / measurement hooks (not part of the reference surface) ------------------------------ */
 
 /* One layer through the production kernels, host NCDHW in / out.  kind: 0 conv3 (VALID 3x3x3),

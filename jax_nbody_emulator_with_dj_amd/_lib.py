@@ -80,6 +80,8 @@ SIGNATURES = {
     "nbe_mesh_to_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_void_p]),
     "nbe_deconvolve_mas": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
     "nbe_power_spectrum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nbe_field_moments": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nbe_minkowski_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nbe_growth_factor": (C.c_double, [C.c_double, C.c_double]),
     "nbe_vel_norm": (C.c_double, [C.c_double, C.c_double]),
     "nbe_test_layer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,

@@ -307,6 +307,230 @@ __global__ void pk_sum_kernel(const float2* __restrict__ a, const float2* __rest
         if (ssum[i]) atomicAdd(&sums[i], ssum[i]);
 }
 
+// ---- Minkowski functionals ------------------------------------------------------------------
+// Moments: two passes in float64 (the sum, then the sum of squared deviations from the mean), each over a fixed
+// partition of the n^3 voxels into kMomBlocks(n) * kMomThreads strided runs, reduced in a fixed order by one block.
+constexpr int kMomThreads = 256;
+constexpr int kMomMaxBlocks = NBE_MOMENTS_WORDS - 2;
+
+int mom_blocks(long long total) {
+    const long long b = (total + 8 * kMomThreads - 1) / (8 * kMomThreads);
+    return (int)(b < kMomMaxBlocks ? b : kMomMaxBlocks);
+}
+
+// the block's sum of v over its threads, in a fixed tree order; valid in thread 0
+__device__ inline double block_sum(double v, double* red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = kMomThreads / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// CENTRED = false: partial[b] = sum of x; true: partial[b] = sum of (x - mom[0])^2
+template <bool CENTRED>
+__global__ __launch_bounds__(kMomThreads) void moments_pass_kernel(const float* __restrict__ x, long long total,
+                                                                   double* __restrict__ mom) {
+    __shared__ double red[kMomThreads];
+    const double mean = CENTRED ? mom[0] : 0.0;
+    const long long stride = (long long)gridDim.x * kMomThreads;
+    double acc = 0.0;
+    long long i = (long long)blockIdx.x * kMomThreads + threadIdx.x;
+    for (; i + 3 * stride < total; i += 4 * stride) {        // four loads in flight, added in index order
+        const float a = x[i], b = x[i + stride], c = x[i + 2 * stride], d = x[i + 3 * stride];
+        if (CENTRED) {
+            const double da = a - mean, db = b - mean, dc = c - mean, dd = d - mean;
+            acc += da * da; acc += db * db; acc += dc * dc; acc += dd * dd;
+        } else {
+            acc += a; acc += b; acc += c; acc += d;
+        }
+    }
+    for (; i < total; i += stride) {
+        const double v = CENTRED ? (x[i] - mean) * (x[i] - mean) : (double)x[i];
+        acc += v;
+    }
+    const double s = block_sum(acc, red);
+    if (threadIdx.x == 0) mom[2 + blockIdx.x] = s;
+}
+
+// one block: mom[slot] = sum of the nb partials / total (slot 0: the mean; slot 1: the std, after a square root)
+__global__ __launch_bounds__(kMomThreads) void moments_finish_kernel(double* mom, int nb, long long total, int slot) {
+    __shared__ double red[kMomThreads];
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < nb; b += kMomThreads) acc += mom[2 + b];
+    const double s = block_sum(acc, red) / (double)total;
+    if (threadIdx.x == 0) mom[slot] = slot == 0 ? s : sqrt(s);
+}
+
+// Counts: one pass.  Each voxel v owns the 8 elements at its low corner (1 cube, 3 faces, 3 edges, 1 vertex); an element
+// is in the excursion set {w >= t} iff the largest w of its 1, 2, 4 or 8 voxels is >= t.  bin(w) = #{thresholds <= w}
+// (upper_bound over the sorted thresholds) is monotone, so an element's bin is the largest bin of its voxels, and one
+// histogram of element bins per functional holds the counts of every threshold: count(t_k) = sum of bins > k.
+//
+// A workgroup sweeps a column of kMfJ x kMfK voxels (j, k) along i, kMfI planes at a time.  Every plane is read once from
+// HBM with a one-voxel low-side halo in j and k (wrapped), standardized and binned as it is loaded, and stored as 16-bit
+// bins in LDS (double-buffered); the bins of the previous plane stay in registers.  A wave covers one row of 64 voxels
+// along k, 4 rows of j per wave.
+constexpr int kMfThreads = 256;
+constexpr int kMfJ = 16, kMfK = 64, kMfI = 32;
+constexpr int kMfRowLen = kMfK + 1, kMfPlane = (kMfJ + 1) * kMfRowLen;    // 17 x 65 bins with the halo
+constexpr int kMfLoads = (kMfPlane + kMfThreads - 1) / kMfThreads;        // 5 plane positions per thread
+constexpr int kMfBins = NBE_MF_MAX_THRESHOLDS + 1;
+#ifndef NBE_MF_UNIFORM
+#define NBE_MF_UNIFORM 1   // 0: every lane adds on its own (timing probes of the histogram layout only)
+#endif
+
+static_assert(kMfThreads == 4 * kMfK && kMfJ == 16, "a wave covers one row of k, four rows of j per wave");
+
+// Add w (1 .. 3) to h[b] for every active lane.  When every active lane of the wave has the same bin, their weights are
+// summed with two ballots into one LDS add; otherwise each lane adds its own.  A constant field, and the flat parts of a
+// smooth one, put a whole row of 64 lanes on one bin: one add instead of 64 same-address LDS atomics, for one compare
+// and one ballot on the other rows (DESIGN.md section 12.1 has the measurements).
+__device__ inline void hist_add(unsigned* h, int b, unsigned w) {
+#if NBE_MF_UNIFORM
+    const int lead = __builtin_amdgcn_readfirstlane(b);
+    if (__ballot(b != lead) == 0ull) {
+        const unsigned long long m1 = __ballot(w & 1u), m2 = __ballot(w & 2u);
+        if (__lane_id() == (unsigned)__builtin_amdgcn_readfirstlane((int)__lane_id()))
+            atomicAdd(&h[lead], (unsigned)(__popcll(m1) + 2 * __popcll(m2)));
+        return;
+    }
+#endif
+    atomicAdd(&h[b], w);
+}
+
+// the three bins of one functional's elements of a voxel (faces or edges): equal bins of one lane go in one add
+__device__ inline void hist_add3(unsigned* h, int a, int b, int c) {
+    hist_add(h, a, 1u + (b == a) + (c == a));
+    if (b != a) hist_add(h, b, 1u + (c == b));
+    if (c != a && c != b) hist_add(h, c, 1u);
+}
+
+struct MfArgs {
+    const float* x;
+    long long n;
+    const float* thr;              // sorted ascending, T values
+    int T;
+    const double* mom;             // NULL: w = x; else w = (x - float(mom[0])) / float(mom[1]) (0 where that std is 0)
+    unsigned long long* counts;    // 4 (T+1) histograms (vertices, edges, faces, cubes) + non-finite voxels
+    int nj, nk, ni;                // column / segment counts
+    long long items;
+};
+
+__global__ __launch_bounds__(kMfThreads) void minkowski_counts_kernel(MfArgs A) {
+    __shared__ float thr[NBE_MF_MAX_THRESHOLDS];
+    __shared__ unsigned hist[4 * kMfBins];
+    __shared__ unsigned short bins[2][kMfPlane];
+    __shared__ unsigned nonfinite;
+    const int tid = threadIdx.x, T = A.T, NB = 4 * (T + 1);
+    const int n = (int)A.n;
+    for (int i = tid; i < T; i += kMfThreads) thr[i] = A.thr[i];
+    for (int i = tid; i < NB; i += kMfThreads) hist[i] = 0u;
+    if (tid == 0) nonfinite = 0u;
+    int top = 1;
+    while (2 * top <= T) top *= 2;
+    const bool stdz = A.mom != nullptr;
+    float mf = 0.0f, sf = 0.0f;
+    if (stdz) { mf = (float)A.mom[0]; sf = (float)A.mom[1]; }
+    const long long plane = A.n * A.n;
+    __syncthreads();
+
+    // bin of one value: standardized with correctly rounded float32 subtraction and division (no reciprocal, nothing to
+    // contract), then the number of thresholds <= w by a fixed-step search (NaN: 0; the caller rejects the field)
+    auto bin_of = [&](float v) -> int {
+        float w = v;
+        if (stdz) w = sf == 0.0f ? 0.0f : __fdiv_rn(__fsub_rn(v, mf), sf);
+        int pos = 0;
+        for (int step = top; step > 0; step >>= 1)
+            if (pos + step <= T && thr[pos + step - 1] <= w) pos += step;
+        return pos;
+    };
+
+    const int wv = tid >> 6, kl = tid & 63;         // this thread's voxels: (j0 + 4 wv + r, k0 + kl), r = 0 .. 3
+    unsigned bad = 0;
+    int buf = 0;
+    for (long long item = blockIdx.x; item < A.items; item += gridDim.x) {
+        const int si = (int)(item % A.ni);
+        const long long rest = item / A.ni;
+        const int sk = (int)(rest % A.nk), sj = (int)(rest / A.nk);
+        const int j0 = sj * kMfJ, k0 = sk * kMfK, i0 = si * kMfI, i1 = min(i0 + kMfI, n);
+        // this thread's plane positions: in-plane offsets (< n^2 <= 2^22) and whether the position is a voxel of the column
+        int off[kMfLoads];
+        bool own[kMfLoads];
+#pragma unroll
+        for (int q = 0; q < kMfLoads; ++q) {
+            const int p = tid + q * kMfThreads;
+            const int jj = p / kMfRowLen, kk = p % kMfRowLen;
+            const int j = ((j0 - 1 + jj) % n + n) % n, k = ((k0 - 1 + kk) % n + n) % n;
+            off[q] = p < kMfPlane ? j * n + k : 0;
+            own[q] = p < kMfPlane && jj >= 1 && kk >= 1 && j0 + jj - 1 < n && k0 + kk - 1 < n;
+        }
+        float raw[kMfLoads];
+        auto load = [&](int i) {
+            const float* src = A.x + (long long)i * plane;
+#pragma unroll
+            for (int q = 0; q < kMfLoads; ++q) raw[q] = (tid + q * kMfThreads < kMfPlane) ? src[off[q]] : 0.0f;
+        };
+        auto store = [&](bool count) {
+#pragma unroll
+            for (int q = 0; q < kMfLoads; ++q) {
+                const int p = tid + q * kMfThreads;
+                if (p < kMfPlane) {
+                    bins[buf][p] = (unsigned short)bin_of(raw[q]);
+                    if (count && own[q] && !isfinite(raw[q])) ++bad;
+                }
+            }
+        };
+        // rows 4 wv .. 4 wv + 4 of the halo'd plane at columns kl (c = 0) and kl + 1 (c = 1)
+        int prev[5][2], cur[5][2];
+        auto read = [&](int (*dst)[2]) {
+#pragma unroll
+            for (int r = 0; r < 5; ++r) {
+                dst[r][0] = bins[buf][(4 * wv + r) * kMfRowLen + kl];
+                dst[r][1] = bins[buf][(4 * wv + r) * kMfRowLen + kl + 1];
+            }
+        };
+        load(i0 == 0 ? n - 1 : i0 - 1);               // the halo plane below the segment, wrapped
+        store(false);
+        __syncthreads();
+        read(prev);
+        buf ^= 1;
+        load(i0);
+        for (int i = i0; i < i1; ++i) {
+            store(true);
+            if (i + 1 < i1) load(i + 1);               // in flight while this plane is counted
+            __syncthreads();
+            read(cur);
+            buf ^= 1;
+            if (k0 + kl < n) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if (j0 + 4 * wv + r >= n) break;
+                    const int b000 = cur[r + 1][1], b001 = cur[r + 1][0], b010 = cur[r][1], b011 = cur[r][0];
+                    const int b100 = prev[r + 1][1], b101 = prev[r + 1][0], b110 = prev[r][1], b111 = prev[r][0];
+                    const int e0 = max(max(b000, b010), max(b001, b011));          // edge along i: v, v-e_j, v-e_k, v-e_j-e_k
+                    const int e1 = max(max(b000, b100), max(b001, b101));          // edge along j
+                    const int e2 = max(max(b000, b100), max(b010, b110));          // edge along k
+                    const int vx = max(max(e0, max(b100, b101)), max(b110, b111));
+                    hist_add(hist + 0 * (T + 1), vx, 1u);
+                    hist_add3(hist + 1 * (T + 1), e0, e1, e2);
+                    hist_add3(hist + 2 * (T + 1), max(b000, b100), max(b000, b010), max(b000, b001));
+                    hist_add(hist + 3 * (T + 1), b000, 1u);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 5; ++r) { prev[r][0] = cur[r][0]; prev[r][1] = cur[r][1]; }
+        }
+    }
+    if (bad) atomicAdd(&nonfinite, bad);
+    __syncthreads();
+    for (int i = tid; i < NB; i += kMfThreads)
+        if (hist[i]) atomicAdd(&A.counts[i], (unsigned long long)hist[i]);
+    if (tid == 0 && nonfinite) atomicAdd(&A.counts[NB], (unsigned long long)nonfinite);
+}
+
 int fail(const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -410,6 +634,50 @@ int nbe_power_spectrum(const void* a, const void* b, int64_t n, void* binmax, vo
     hipLaunchKernelGGL(pk_sum_kernel, g, blk, nb * (3 * sizeof(unsigned long long) + sizeof(int)), s, (const float2*)a,
                        (const float2*)b, (long long)n, (const unsigned*)binmax, (unsigned long long*)sums);
     return launched("nbe_power_spectrum (sum)");
+}
+
+int nbe_field_moments(const void* field, int64_t n, void* moments, void* stream) {
+    if (!field || !moments) return fail("nbe_field_moments: NULL argument");
+    if (n < 1 || n > NBE_MF_MAX_N) return fail("nbe_field_moments: mesh size %lld unsupported (1 .. %d)", (long long)n,
+                                               NBE_MF_MAX_N);
+    const long long total = (long long)n * n * n;
+    const int nb = mom_blocks(total);
+    hipStream_t s = (hipStream_t)stream;
+    const float* x = (const float*)field;
+    double* mom = (double*)moments;
+    hipLaunchKernelGGL(moments_pass_kernel<false>, dim3(nb), dim3(kMomThreads), 0, s, x, total, mom);
+    hipLaunchKernelGGL(moments_finish_kernel, dim3(1), dim3(kMomThreads), 0, s, mom, nb, total, 0);
+    hipLaunchKernelGGL(moments_pass_kernel<true>, dim3(nb), dim3(kMomThreads), 0, s, x, total, mom);
+    hipLaunchKernelGGL(moments_finish_kernel, dim3(1), dim3(kMomThreads), 0, s, mom, nb, total, 1);
+    return launched("nbe_field_moments");
+}
+
+int nbe_minkowski_counts(const void* field, int64_t n, const void* thresholds, int nthresholds, const void* moments,
+                         void* counts, void* stream) {
+    if (!field || !thresholds || !counts) return fail("nbe_minkowski_counts: NULL argument");
+    if (n < 1 || n > NBE_MF_MAX_N) return fail("nbe_minkowski_counts: mesh size %lld unsupported (1 .. %d)",
+                                               (long long)n, NBE_MF_MAX_N);
+    if (nthresholds < 1 || nthresholds > NBE_MF_MAX_THRESHOLDS)
+        return fail("nbe_minkowski_counts: %d thresholds unsupported (1 .. %d)", nthresholds, NBE_MF_MAX_THRESHOLDS);
+    MfArgs A;
+    A.x = (const float*)field;
+    A.n = n;
+    A.thr = (const float*)thresholds;
+    A.T = nthresholds;
+    A.mom = (const double*)moments;
+    A.counts = (unsigned long long*)counts;
+    A.nj = (int)((n + kMfJ - 1) / kMfJ);
+    A.nk = (int)((n + kMfK - 1) / kMfK);
+    A.ni = (int)((n + kMfI - 1) / kMfI);
+    A.items = (long long)A.nj * A.nk * A.ni;
+    // a few resident workgroups per CU loop over the columns: the 64-bit flush is one add per bin per workgroup
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
+                                                 hipSuccess || cus < 1)
+        cus = 256;
+    const long long grid = A.items < 4LL * cus ? A.items : 4LL * cus;
+    hipLaunchKernelGGL(minkowski_counts_kernel, dim3((unsigned)grid), dim3(kMfThreads), 0, (hipStream_t)stream, A);
+    return launched("nbe_minkowski_counts");
 }
 
 }  // extern "C"

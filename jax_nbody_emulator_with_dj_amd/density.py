@@ -10,6 +10,7 @@ assignment window (`scripts/utils.py:136-148`) and measures P(k) (`scripts/utils
     k, pk, nmodes = power_spectrum(delta, boxsize=1000.0)
     k, pk, nmodes = power_spectrum(delta_emu, boxsize=1000.0, other=delta_lpt)     # cross spectrum Re<a b*>
     delta_c = deconvolve_mas(delta, worder=2)
+    mf = minkowski_functionals(delta, boxsize=1000.0)    # v0 .. v3 at 41 thresholds of the standardized field
 
 Conventions (as DISCO-DJ / Pylians and the lattice of `scripts/halos.py:394-403`):
 
@@ -27,6 +28,8 @@ Conventions (as DISCO-DJ / Pylians and the lattice of `scripts/halos.py:394-403`
 - `power_spectrum` uses the unnormalised forward FFT: P = |delta_k|^2 L^3 / n^6.  Shell b = 1 .. n/2 holds the modes
   with b - 1/2 <= |k| / k_F < b + 1/2, k_F = 2 pi / L, counted over the full complex grid; it returns the mean |k|, the
   mean P and the number of modes per shell as float64 NumPy arrays.
+- `minkowski_functionals` (reference `scripts/utils.py:652-763`) counts the elements of the periodic cubical complex of
+  each excursion set {w >= t} in one pass over the field: see its docstring for the definition.
 
 Residency: NumPy in gives NumPy out; a CUDA torch tensor in gives a CUDA tensor on the same device, with no host copy,
 enqueued on torch's current stream of that device.  float16 displacements are read as half in the kernel.  There is no CPU
@@ -46,11 +49,15 @@ try:
 except Exception:  # pragma: no cover
     torch = None
 
-__all__ = ["paint_density", "deconvolve_mas", "power_spectrum"]
+__all__ = ["paint_density", "deconvolve_mas", "power_spectrum", "minkowski_functionals"]
 
 WORDERS = {1: "NGP", 2: "CIC", 3: "TSC", 4: "PCS"}
 _UNIT = 2.0 ** 22           # fixed-point units per particle mass (include/nbe.h, nbe_paint_mesh)
 _KUNIT = 2.0 ** -36         # units of the |k| sums of nbe_power_spectrum
+_MF_MAX_N = 2048            # include/nbe.h: NBE_MF_MAX_N, NBE_MF_MAX_THRESHOLDS, NBE_MOMENTS_WORDS
+_MF_MAX_T = 1024
+_MOMENT_WORDS = 2050
+MF_CONVENTION = "periodic_voxel_cubical_complex"
 
 
 def _is_torch(x):
@@ -249,3 +256,102 @@ def power_spectrum(delta, boxsize=1000.0, other=None):
         pk = np.ldexp(sm[2].astype(np.float64), e - 32) / cnt * (L[0] ** 3 / float(n) ** 6)
     pk = np.where(np.isfinite(bm), pk, np.nan)
     return k, pk, cnt
+
+
+def _mf_thresholds(thresholds):
+    if thresholds is None:
+        return np.linspace(-3.0, 3.0, 41, dtype=np.float32)
+    try:
+        t = np.asarray(thresholds, dtype=np.float64).ravel()
+    except (TypeError, ValueError):
+        raise ValueError("thresholds must be numbers, got %r" % (thresholds,))
+    with np.errstate(over="ignore"):
+        t = t.astype(np.float32)
+    if not 2 <= t.size <= _MF_MAX_T:
+        raise ValueError("thresholds must hold 2 .. %d values, got %d" % (_MF_MAX_T, t.size))
+    if not np.isfinite(t).all():
+        raise ValueError("thresholds must be finite in float32")
+    return t
+
+
+def _mf_validate(field, boxsize, thresholds):
+    f = _check_array(field, "field")
+    if f.ndim != 3 or len(set(f.shape)) != 1:
+        raise ValueError("minkowski_functionals needs a cubic (n, n, n) field, got shape %s" % (tuple(f.shape),))
+    n = int(f.shape[0])
+    if not 1 <= n <= _MF_MAX_N:
+        raise ValueError("minkowski_functionals: mesh size %d unsupported (1 .. %d)" % (n, _MF_MAX_N))
+    if _dtype_name(f) != "float32":
+        raise ValueError("field must be float32, got %s" % _dtype_name(f))
+    L = _triple(boxsize, "boxsize", "a length")
+    if len(set(L)) != 1:
+        raise ValueError("minkowski_functionals needs a cubic box, got boxsize %s" % (L,))
+    return f, n, L[0], _mf_thresholds(thresholds)
+
+
+def _mf_values(counts, n, boxsize):
+    """(v0, v1, v2, v3) float64 from (T, 4) element counts (n0, n1, n2, n3) of an n^3 mesh in a box of side boxsize."""
+    c = np.asarray(counts, dtype=np.float64)
+    n0, n1, n2, n3 = c[:, 0], c[:, 1], c[:, 2], c[:, 3]
+    h = float(boxsize) / float(n)
+    vol = float(boxsize) ** 3
+    m0 = h ** 3 * n3
+    m1 = h ** 2 * ((-2.0 / 3.0) * n3 + (2.0 / 9.0) * n2)
+    m2 = h * ((2.0 / 3.0) * n3 - (4.0 / 9.0) * n2 + (2.0 / 9.0) * n1)
+    m3 = n0 - n1 + n2 - n3
+    return m0 / vol, m1 / vol, m2 / vol, m3 / vol
+
+
+def minkowski_functionals(field, boxsize=1000.0, thresholds=None, standardize=True):
+    """Minkowski functionals of the excursion sets of a periodic density field (reference scripts/utils.py:652-763,
+    compute_minkowski_functionals; the driver scripts call it for every field they paint).
+
+    field: (n, n, n) float32, NumPy array or CUDA torch tensor (read where it lives, on torch's current stream of its
+    device), 1 <= n <= 2048.  Other dtypes raise ValueError (the reference casts to float32).  boxsize: L (scalar, or a
+    3-tuple of equal values).  thresholds: default np.linspace(-3, 3, 41, dtype=float32); otherwise flattened and cast to
+    float32, 2 .. 1024 finite values in any order, duplicates allowed; results come in the caller's order.
+
+    Definition.  w is the field, standardized by default: w = (x - float32(mean)) / float32(std) in float32 (w = 0 where
+    float32(std) is 0), where mean and the population std are taken on the device in float64, reproducibly.  For a
+    threshold t, M = {voxels with w >= t}, indices mod n.  With e_a the unit step along axis a:
+      n3 = |M|                                                    (cubes)
+      n2 = sum over a of #{v : v or v - e_a in M}                 (faces between v and v - e_a)
+      n1 = sum over a of #{v : v, v - e_b, v - e_c or v - e_b - e_c in M}, {b, c} the other axes   (edges along a)
+      n0 = #{v : v - s in M for some s in {0, 1}^3}              (vertices)
+    and with h = L / n: M0 = h^3 n3, M1 = h^2 (-2/3 n3 + 2/9 n2), M2 = h (2/3 n3 - 4/9 n2 + 2/9 n1),
+    M3 = n0 - n1 + n2 - n3 (the Euler characteristic); v_i = M_i / L^3.
+
+    Returns a dict of host objects: thresholds (float64 copies of the float32 values), v0 .. v3 (float64), mean and std
+    (floats), standardize (bool), convention ("periodic_voxel_cubical_complex") and counts, an int64 (T, 4) array of
+    (n0, n1, n2, n3).  A non-finite value anywhere in the field raises NBEError.
+
+    Difference from the reference: it takes np.mean and np.std in float32; here they are float64.  A voxel whose
+    standardized value is within a float32 rounding of a threshold can therefore fall on the other side of it than in the
+    reference's own run.  The counts are computed in one pass over the field for all thresholds (DESIGN.md section
+    12.1)."""
+    f, n, L, thr = _mf_validate(field, boxsize, thresholds)
+    standardize = bool(standardize)
+    host = not _is_torch(f)
+    dev = _device() if host else f.device
+    l = _lib.lib()
+    T = int(thr.size)
+    order = np.argsort(thr, kind="stable")
+    with torch.cuda.device(dev):
+        s = _stream(dev)
+        x = _to_device(f, dev, (torch.float32,))
+        thr_d = torch.from_numpy(np.ascontiguousarray(thr[order])).to(dev)
+        mom = torch.empty(_MOMENT_WORDS, dtype=torch.float64, device=dev)
+        hist = torch.zeros(4 * (T + 1) + 1, dtype=torch.int64, device=dev)
+        _lib.check(l.nbe_field_moments(_ptr(x), n, _ptr(mom), s))
+        _lib.check(l.nbe_minkowski_counts(_ptr(x), n, _ptr(thr_d), T, _ptr(mom) if standardize else None, _ptr(hist), s))
+        h = hist.cpu().numpy()
+        mean, std = (float(v) for v in mom[:2].cpu().numpy())
+    bad = int(h[-1])
+    if bad:
+        raise NBEError("minkowski_functionals: %d voxel(s) of the field are not finite" % bad)
+    tail = np.cumsum(h[:-1].reshape(4, T + 1)[:, ::-1], axis=1)[:, ::-1]     # tail[f, b] = elements with bin >= b
+    counts = np.empty((T, 4), np.int64)
+    counts[order] = tail[:, 1:].T                                              # sorted threshold k: bins > k
+    v0, v1, v2, v3 = _mf_values(counts, n, L)
+    return {"thresholds": thr.astype(np.float64), "v0": v0, "v1": v1, "v2": v2, "v3": v3, "mean": mean, "std": std,
+            "standardize": standardize, "convention": MF_CONVENTION, "counts": counts}

@@ -18,8 +18,10 @@ Same command line, file formats, range checks and output names as the reference'
 Density fields (the fork's DISCO-DJ step, scripts/core.py:447-458): with `--density_res N` every box also writes
 <output_dir>/emu_delta.npy, the emulated displacement painted onto an N^3 mesh on the GPU (density.py; `--mas_worder`
 1-4 = NGP/CIC/TSC/PCS, default 2; `--no-deconvolve` keeps the assignment window; `--boxsize` in Mpc/h, default 1000),
-and with `--pk` <output_dir>/emu_pk.npz (k, pk, nmodes).  Painting reads the float32 displacement on the device; the
-saved emu_dis.npy is rounded to --output-precision afterwards.
+with `--pk` <output_dir>/emu_pk.npz (k, pk, nmodes), and with `--minkowski` <output_dir>/emu_minkowski.npz
+(thresholds, v0, v1, v2, v3, counts, mean, std: the Minkowski functionals of the painted delta at the 41 default
+thresholds of the standardized field, computed on the device by density.minkowski_functionals).  Painting reads the
+float32 displacement on the device; the saved emu_dis.npy is rounded to --output-precision afterwards.
 
 What differs from the reference: the engine, its weights and its ~100 GB workspace stay resident on the
 GPU for the whole batch, and disk I/O overlaps compute -- the next displacement file is read and the
@@ -160,6 +162,9 @@ def build_parser():
                     help='Deconvolve the mass assignment window (default: True)')
     ap.add_argument('--pk', action='store_true', default=argparse.SUPPRESS,
                     help='With --density_res: also write the power spectrum to <output_dir>/emu_pk.npz (k, pk, nmodes)')
+    ap.add_argument('--minkowski', action='store_true', default=argparse.SUPPRESS,
+                    help='With --density_res: also write the Minkowski functionals of the density field (standardized, '
+                         '41 thresholds in [-3, 3]) to <output_dir>/emu_minkowski.npz')
     return ap
 
 
@@ -183,6 +188,14 @@ def density_options(args):
         _die(f'--boxsize must be positive, got {boxsize}')
     return dict(res=int(res), boxsize=boxsize, worder=int(getattr(args, 'mas_worder', 2)),
                 deconvolve=bool(getattr(args, 'deconvolve', True)), pk=bool(getattr(args, 'pk', False)))
+
+
+def minkowski_option(args):
+    """Whether --minkowski was given (read apart from density_options, whose dict it leaves as it was)."""
+    on = bool(getattr(args, 'minkowski', False))
+    if on and getattr(args, 'density_res', None) is None:
+        _die('--minkowski needs --density_res')
+    return on
 
 
 def load_params(path):
@@ -210,9 +223,10 @@ def run(args):
     print(f'  Style modulation: {args.style}')
     print(f'  Subbox divisions: {args.ndiv}')
     dens = density_options(args)
+    mink = minkowski_option(args)
     if dens is not None:
         print(f"  Density: {dens['res']}^3 mesh, worder {dens['worder']}, deconvolve {dens['deconvolve']}, "
-              f"boxsize {dens['boxsize']}, P(k) {dens['pk']}")
+              f"boxsize {dens['boxsize']}, P(k) {dens['pk']}" + (", Minkowski functionals" if mink else ""))
     print()
 
     shape = None
@@ -243,11 +257,15 @@ def run(args):
             if 'pk' in extra:
                 k, pk, nmodes = extra['pk']
                 np.savez(out_dir / 'emu_pk.npz', k=k, pk=pk, nmodes=nmodes)
+            if 'mf' in extra:
+                mf = extra['mf']
+                np.savez(out_dir / 'emu_minkowski.npz', **{key: mf[key] for key in
+                         ('thresholds', 'v0', 'v1', 'v2', 'v3', 'counts', 'mean', 'std')})
 
     def with_density(dis_in, z, Om):
         """process_box on the device, the density field of its float32 displacement, host copies of the fields."""
         import torch
-        from .density import paint_density, power_spectrum
+        from .density import minkowski_functionals, paint_density, power_spectrum
         box_t = torch.from_numpy(np.ascontiguousarray(dis_in)).to('cuda')
         result = emu.process_box(box_t, z=z, Om=Om, show_progress=not args.quiet)
         disp = result[0] if args.vel else result
@@ -256,6 +274,8 @@ def run(args):
         extra = {'delta': delta.cpu().numpy()}
         if dens['pk']:
             extra['pk'] = power_spectrum(delta, boxsize=dens['boxsize'])
+        if mink:
+            extra['mf'] = minkowski_functionals(delta, boxsize=dens['boxsize'])
         out_dt = np.dtype(args.output_precision)
         host = tuple(t.cpu().numpy().astype(out_dt, copy=False) for t in (result if args.vel else (result,)))
         return (host if args.vel else host[0]), extra
