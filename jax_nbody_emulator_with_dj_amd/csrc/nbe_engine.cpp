@@ -262,7 +262,6 @@ struct nbe_ctx {
         std::vector<Slot> slots;
         unsigned* bits = nullptr; int64_t words = 0;
         unsigned* count = nullptr;                // per slot: words written
-        int zr[3] = {0, 0, 0};                    // set by the schedule around a block: planes [lo, hi) of its result exist, period (0: no wrap)
     } probe;
     // profiling
     bool prof = false;
@@ -575,12 +574,16 @@ static const Layer* find_layer(nbe_ctx* c, const char* block, const char* layer)
 // StyleResNetBlock3DVel (style_blocks_vel.py:96-166): skip 1x1x1 cropped by 2, conv-act-conv, add, [act].
 // Periodic-yx mode (x.pad = 1): y and x do not shrink -- every 3x3x3 convolution reads its input's wrap-around halo
 // and writes the interior of a tensor of the same padded size, whose halo is filled afterwards; z shrinks as always.
-// (dst: write the block's result there -- a view with the result's geometry -- instead of allocating it)
 // (has_dx false: conv_l00, whose skip reads the input field -- fused with F_SKIP_NODX)
 // (displacement only: conv_h3w_kernel<SKIP, NOVEL> is the one kernel that runs a fused skip without a tangent)
 // (the float16 model: as displacement only -- the Winograd-z kernel is the one kernel with a fused skip)
 static bool wino_only_fuse(const nbe_ctx* c) { return !c->vel || c->prec == PREC_F16; }
-static bool block_fused(nbe_ctx* c, const Layer* L1, bool) { return c->fuse && L1->fskip != nullptr && (!wino_only_fuse(c) || !wino_env_off()); }
+// Does the block of conv_1 layer L1 run its skip fused, on `nres` result planes?  (displacement only and float16: the fused
+// skip exists in conv_h3w_kernel alone, which pairs planes -- an odd number of result planes, the 5 planes of conv_c behind
+// a 104-voxel input, takes the unfused path; slabs always have an even number)
+static bool block_fused(const nbe_ctx* c, const Layer* L1, int nres) {
+    return c->fuse && L1->fskip != nullptr && (!wino_only_fuse(c) || (!wino_env_off() && (nres & 1) == 0));
+}
 
 // hidden tensor of a block whose input x has `pad`: interior (Hi - sy) x (Wi - sy).  A fused block gives it the row
 // and plane pitch of x (conv_h3g_kernel fetches the skip's patches of x with the offsets of its own input's).
@@ -590,70 +593,27 @@ static Tensor alloc_hidden(nbe_ctx* c, int cmid, int nz, const Tensor& x, bool f
     return tallocp(c, cmid, nz, x.p.H - 2 * pad - sy, x.p.W - 2 * pad - sy, pad);
 }
 
-static int resblock(nbe_ctx* c, const char* name, const Tensor& x, bool has_dx, bool final_act,
-                    int cout, int cmid, Tensor* out, const Tensor* dst = nullptr) {
-    const Layer *Ls = find_layer(c, name, "skip"), *L0 = find_layer(c, name, "conv_0"), *L1 = find_layer(c, name, "conv_1");
-    if (!Ls || !L0 || !L1) return fail("missing layers of block %s", name);
-    const int D = x.p.D, H = x.p.H, W = x.p.W, pad = x.pad;
-    const int Hi = H - 2 * pad, Wi = W - 2 * pad;                 // interior of x (pad = 0: all of it)
-    const int sy = pad ? 0 : 2;                                  // what one 3x3x3 convolution takes off y and x
-    // (displacement only: the fused skip exists in conv_h3w_kernel alone, which pairs planes -- an odd number of result planes,
-    // the 5 planes of conv_c behind a 104-voxel input, takes the unfused path)
-    const bool fused = block_fused(c, L1, has_dx) && (!wino_only_fuse(c) || (D & 1) == 0);
-    // Unfused: the second convolution adds the skip as a residual and writes its result over it (every lane reads its
-    // residual elements before it stores the same elements): one full-resolution tensor pair less at the workspace peak.
-    // Fused (gauged f16x3): conv_1 computes the skip itself from x -- no skip launch, no residual round trip.
-    Tensor s = dst ? *dst : tallocp(c, cout, D - 4, Hi - 2 * sy, Wi - 2 * sy, pad);
-    Tensor h = alloc_hidden(c, cmid, D - 2, x, fused);
-    if ((!dst && s.off < 0) || h.off < 0) return fail("workspace exhausted in block %s", name);
-    if (dst && (s.p.D != D - 4 || s.p.H != Hi - 2 * sy + 2 * pad || s.p.W != Wi - 2 * sy + 2 * pad || s.pad != pad))
-        return fail("internal: destination geometry mismatch in block %s", name);
-    const int64_t sk_off = (2L * H + (pad ? pad : 2)) * W + (pad ? pad : 2);   // skip: centre crop of x by the two convolutions
-    if (!fused) {
-        ConvLaunch cl; cl.in = x.p; cl.in_off = sk_off;
-        cl.Dv = D - 4; cl.Hv = Hi - 2 * sy; cl.Wv = Wi - 2 * sy; cl.out = inner(s); cl.flags = 0;
-        if (run_conv(c, *Ls, cl, has_dx)) return 1;
-    }
-    int og[3];
-    {
-        ConvLaunch cl; cl.in = x.p; cl.Dv = D - 2; cl.Hv = H - 2; cl.Wv = W - 2; cl.out = inner(h); cl.flags = F_ACT;
-        if (run_conv(c, *L0, cl, has_dx)) return 1;
-        org_conv(x, 1, og);
-        probe_act(c, *L0, cl.out, 0, og, cl.Dv, cl.Hv, cl.Wv, pad != 0);
-    }
-    fill_halo(c, h);
-    org_conv(x, 2, og);
-    {
-        ConvLaunch cl; cl.in = h.p; cl.Dv = D - 4; cl.Hv = s.p.H - 2 * pad; cl.Wv = s.p.W - 2 * pad; cl.out = inner(s);
-        if (fused) { cl.sk = x.p; cl.sk_off = sk_off; cl.skw = L1->pwn.w ? &Ls->pwn : &Ls->pw; cl.flags = (final_act ? F_ACT : 0) | (has_dx ? 0 : F_SKIP_NODX); }
-        else { cl.res = inner(s); cl.flags = F_RES | (final_act ? F_ACT : 0); }
-        if (run_conv(c, *L1, cl, true)) return 1;
-        if (final_act) probe_act(c, *L1, cl.out, 0, og, cl.Dv, cl.Hv, cl.Wv, pad != 0);
-    }
-    fill_halo(c, s);
-    tfree(c, h);
-    set_org(s, og[0], og[1], og[2]);
-    *out = s;
-    return 0;
-}
-
-// The z-slab schedule's residual block: the same three launches as resblock() on plane ranges of persistent tensors.
-// Plane indices are in block-input coordinates (result plane j is centred on input plane j + 2): hidden planes
-// [jh, jh + nh) and result planes [js, js + ns) are computed; what precedes them was carried over from the slab
-// before.  h and s have the geometry resblock() would give them (s also serves as the skip / residual, in place).
+// The residual block's three launches on plane ranges of persistent tensors (the z-slab schedule; resblock() runs it over
+// whole tensors).  Plane indices are in block-input coordinates (result plane j is centred on input plane j + 2): hidden
+// planes [jh, jh + nh) and result planes [js, js + ns) are computed; what precedes them was carried over from the slab
+// before.  h and s have the geometry resblock() gives them (s also serves as the skip / residual, in place).
+// zr = {lo, hi, period} (branch probe): planes [lo, hi) of the block's result exist in a box periodic along z (nullptr: no wrap).
 // x2: the block input is concat([x, x2]) along the channels (mid channels each, same geometry) without a concat tensor:
 // the gauged f16x3 kernel reads its K chunks from two tensors (fused blocks only)
 static int resblock_part(nbe_ctx* c, const char* name, const Tensor& x, const Tensor& h, const Tensor& s,
-                         int js, int ns, int jh, int nh, bool has_dx, bool final_act, const Tensor* x2 = nullptr) {
+                         int js, int ns, int jh, int nh, bool has_dx, bool final_act, const int* zr, const Tensor* x2 = nullptr) {
     const Layer *Ls = find_layer(c, name, "skip"), *L0 = find_layer(c, name, "conv_0"), *L1 = find_layer(c, name, "conv_1");
     if (!Ls || !L0 || !L1) return fail("missing layers of block %s", name);
     const int H = x.p.H, W = x.p.W, pad = x.pad;
-    const bool fused = block_fused(c, L1, has_dx);
+    const bool fused = block_fused(c, L1, ns);
     if (fused && (h.p.H != H || h.p.W != W)) return fail("internal: hidden tensor of fused block %s lacks the input's pitch", name);
     if (x2 && (!fused || x2->p.H != H || x2->p.W != W || x2->pad != pad)) return fail("internal: two-source input of block %s", name);
     const Tensor sv = zview(s, js, ns), hv = zview(h, jh, nh);
     const Tensor xs = zview(x, js, ns + 4);                      // what the skip of result planes [js, js + ns) reads
-    const int64_t sk_off = (2L * H + (pad ? pad : 2)) * W + (pad ? pad : 2);
+    const int64_t sk_off = (2L * H + (pad ? pad : 2)) * W + (pad ? pad : 2);   // skip: centre crop of x by the two convolutions
+    // Unfused: the second convolution adds the skip as a residual and writes its result over it (every lane reads its
+    // residual elements before it stores the same elements): one full-resolution tensor pair less at the workspace peak.
+    // Fused (gauged f16x3): conv_1 computes the skip itself from x -- no skip launch, no residual round trip.
     if (!fused) {
         ConvLaunch cl; cl.in = xs.p; cl.in_off = sk_off;
         cl.Dv = ns; cl.Hv = s.p.H - 2 * pad; cl.Wv = s.p.W - 2 * pad; cl.out = inner(sv); cl.flags = 0;
@@ -665,8 +625,8 @@ static int resblock_part(nbe_ctx* c, const char* name, const Tensor& x, const Te
         if (x2) { cl.in2 = zview(*x2, jh, nh + 2).p; cl.csplit_ch = c->mid; }
         if (run_conv(c, *L0, cl, has_dx)) return 1;
         org_conv(x, 1, og); og[0] += jh;                         // hidden plane j is centred on plane j + 1 of x
-        const int zh[3] = {c->probe.zr[0], c->probe.zr[1] + 2, c->probe.zr[2]};
-        probe_act(c, *L0, cl.out, 0, og, cl.Dv, cl.Hv, cl.Wv, pad != 0, zh);
+        const int zh[3] = {zr ? zr[0] : 0, zr ? zr[1] + 2 : 0, zr ? zr[2] : 0};
+        probe_act(c, *L0, cl.out, 0, og, cl.Dv, cl.Hv, cl.Wv, pad != 0, zr ? zh : nullptr);
     }
     fill_halo(c, hv);
     {
@@ -676,9 +636,27 @@ static int resblock_part(nbe_ctx* c, const char* name, const Tensor& x, const Te
         else { cl.res = inner(sv); cl.flags = F_RES | (final_act ? F_ACT : 0); }
         if (run_conv(c, *L1, cl, true)) return 1;
         org_conv(x, 2, og); og[0] += js;
-        if (final_act) probe_act(c, *L1, cl.out, 0, og, cl.Dv, cl.Hv, cl.Wv, pad != 0, c->probe.zr);
+        if (final_act) probe_act(c, *L1, cl.out, 0, og, cl.Dv, cl.Hv, cl.Wv, pad != 0, zr);
     }
     fill_halo(c, sv);
+    return 0;
+}
+
+// the block on whole tensors: its result is allocated (cout channels), the hidden tensor (cmid channels) lives meanwhile
+static int resblock(nbe_ctx* c, const char* name, const Tensor& x, bool has_dx, bool final_act, int cout, int cmid, Tensor* out) {
+    const Layer* L1 = find_layer(c, name, "conv_1");
+    if (!L1) return fail("missing layers of block %s", name);
+    const int D = x.p.D, pad = x.pad;
+    const int sy = pad ? 0 : 2;                                  // what one 3x3x3 convolution takes off y and x
+    Tensor s = tallocp(c, cout, D - 4, x.p.H - 2 * pad - 2 * sy, x.p.W - 2 * pad - 2 * sy, pad);
+    Tensor h = alloc_hidden(c, cmid, D - 2, x, block_fused(c, L1, D - 4));
+    if (s.off < 0 || h.off < 0) return fail("workspace exhausted in block %s", name);
+    if (resblock_part(c, name, x, h, s, 0, D - 4, 0, D - 2, has_dx, final_act, nullptr)) return 1;
+    tfree(c, h);
+    int og[3];
+    org_conv(x, 2, og);
+    set_org(s, og[0], og[1], og[2]);
+    *out = s;
     return 0;
 }
 
@@ -688,18 +666,29 @@ static void carry_planes(nbe_ctx* c, const Tensor& t, int src, int dst, int n) {
     launch_crop(zview(t, src, n).p, 0, zview(t, dst, n).p, 0, c->vel, c->stream, 0);
 }
 
+// down-sampling layer L (stride 2) of x's interior into o, which takes x's frame halved; probe: record its branches
+static int down_conv(nbe_ctx* c, const Layer& L, const Tensor& x, Tensor& o, bool probe) {
+    ConvLaunch cl; cl.in = inner(x); cl.Dv = o.p.D; cl.Hv = o.p.H; cl.Wv = o.p.W; cl.out = o.p; cl.flags = F_ACT;
+    if (run_conv(c, L, cl, true)) return 1;
+    set_org(o, x.org[0] / 2, x.org[1] / 2, x.org[2] / 2);
+    // (periodic-yx: the interior only; its periodic images are copies)
+    if (probe) probe_act(c, L, cl.out, 0, o.org, cl.Dv, cl.Hv, cl.Wv, x.pad != 0);
+    return 0;
+}
+
 static int downblock(nbe_ctx* c, const char* name, const Tensor& x, Tensor* out) {
     const Layer* L = find_layer(c, name, "conv_0");
     if (!L) return fail("missing layer %s/conv_0", name);
     Tensor o = talloc(c, c->mid, x.p.D / 2, x.p.H / 2, x.p.W / 2);
     if (o.off < 0) return fail("workspace exhausted in %s", name);
-    ConvLaunch cl; cl.in = x.p; cl.Dv = o.p.D; cl.Hv = o.p.H; cl.Wv = o.p.W; cl.out = o.p; cl.flags = F_ACT;
-    if (run_conv(c, *L, cl, true)) return 1;
-    set_org(o, x.org[0] / 2, x.org[1] / 2, x.org[2] / 2);
-    probe_act(c, *L, cl.out, 0, o.org, cl.Dv, cl.Hv, cl.Wv, false);
+    if (down_conv(c, *L, x, o, true)) return 1;
     *out = o;
     return 0;
 }
+
+// channel planes of the first mid channels: the skip half of a concat tensor (not planes_for, which rounds up to 16
+// channels -- narrow models store the up-sampled half right behind mid channels)
+static int mid_planes(const nbe_ctx* c) { return c->mid / (c->prec == PREC_F16 ? 8 : 4); }
 
 // up-sample into planes [mid/4, 2*mid/4) of the concat tensor (core :166-169: concat([skip, up]))
 // (xcrop: centre crop of x in y and x before up-sampling; the result goes to the interior of cat)
@@ -712,7 +701,7 @@ static int upblock(nbe_ctx* c, const char* name, const Tensor& x, const Tensor& 
     if (cat.p.D != 2 * x.p.D || cat.p.H - 2 * cat.pad != 2 * Hx || cat.p.W - 2 * cat.pad != 2 * Wx)
         return fail("internal: concat geometry mismatch in %s", name);
     const bool up8 = up8_launch(c, *L, true);
-    const int out_g0 = g0 >= 0 ? g0 : c->mid / (c->prec == PREC_F16 ? 8 : 4);
+    const int out_g0 = g0 >= 0 ? g0 : mid_planes(c);
     for (int p = 0; p < (up8 ? 1 : 8); ++p) {
         ConvLaunch cl; cl.in = x.p; cl.in_off = ((int64_t)xcrop * x.p.W + xcrop);
         cl.Dv = x.p.D; cl.Hv = Hx; cl.Wv = Wx; cl.out = inner(cat);
@@ -727,10 +716,11 @@ static int upblock(nbe_ctx* c, const char* name, const Tensor& x, const Tensor& 
     return 0;
 }
 
-static void crop_into(nbe_ctx* c, const Tensor& src, int crop, const Tensor& cat) {
+// the first mid channels of src, centre-cropped by `crop` in y and x and by `cz` in z (-1: by `crop`), into dst
+static void crop_into(nbe_ctx* c, const Tensor& src, int crop, const Tensor& dst, int cz = -1) {
     if (c->dry) return;
-    Planes s = src.p; s.G = c->mid / (c->prec == PREC_F16 ? 8 : 4);
-    launch_crop(s, crop, cat.p, 0, c->vel, c->stream);
+    Planes s = src.p; s.G = mid_planes(c);
+    launch_crop(s, crop, dst.p, 0, c->vel, c->stream, cz);
 }
 
 static int check_dims(int D, int H, int W) {
@@ -739,58 +729,6 @@ static int check_dims(int D, int H, int W) {
         if (v[i] < 104 || v[i] % 8 != 0)
             return fail("input spatial size %d unsupported: each of (D,H,W) must be >= 104 and a multiple of 8 "
                         "(all-VALID U-Net with three 2x levels, receptive-field crop 48)", v[i]);
-    return 0;
-}
-
-// the network body on a resident input tensor; returns conv_r01's output tensor (out_chan channels)
-static int network(nbe_ctx* c, const Tensor& tin, Tensor* yout) {
-    const int m = c->mid;
-    Tensor a, y0, y1, y2, t, cat0, cat1, cat2, r;
-    if (resblock(c, "conv_l00", tin, false, true, m, m, &a)) return 1;
-    if (resblock(c, "conv_l01", a, true, true, m, m, &y0)) return 1;
-    tfree(c, a);
-    cat0 = talloc(c, 2 * m, y0.p.D - 80, y0.p.H - 80, y0.p.W - 80);
-    if (cat0.off < 0) return fail("workspace exhausted (cat0)");
-    crop_into(c, y0, 40, cat0);
-    if (downblock(c, "down_l0", y0, &t)) return 1;
-    tfree(c, y0);
-
-    if (resblock(c, "conv_l1", t, true, true, m, m, &y1)) return 1;
-    tfree(c, t);
-    cat1 = talloc(c, 2 * m, y1.p.D - 32, y1.p.H - 32, y1.p.W - 32);
-    if (cat1.off < 0) return fail("workspace exhausted (cat1)");
-    crop_into(c, y1, 16, cat1);
-    if (downblock(c, "down_l1", y1, &t)) return 1;
-    tfree(c, y1);
-
-    if (resblock(c, "conv_l2", t, true, true, m, m, &y2)) return 1;
-    tfree(c, t);
-    cat2 = talloc(c, 2 * m, y2.p.D - 8, y2.p.H - 8, y2.p.W - 8);
-    if (cat2.off < 0) return fail("workspace exhausted (cat2)");
-    crop_into(c, y2, 4, cat2);
-    if (downblock(c, "down_l2", y2, &t)) return 1;
-    tfree(c, y2);
-
-    if (resblock(c, "conv_c", t, true, true, m, m, &r)) return 1;
-    tfree(c, t);
-
-    if (upblock(c, "up_r2", r, cat2)) return 1;
-    tfree(c, r);
-    if (resblock(c, "conv_r2", cat2, true, true, m, 2 * m, &r)) return 1;
-    tfree(c, cat2);
-
-    if (upblock(c, "up_r1", r, cat1)) return 1;
-    tfree(c, r);
-    if (resblock(c, "conv_r1", cat1, true, true, m, 2 * m, &r)) return 1;
-    tfree(c, cat1);
-
-    if (upblock(c, "up_r0", r, cat0)) return 1;
-    tfree(c, r);
-    if (resblock(c, "conv_r00", cat0, true, true, m, 2 * m, &r)) return 1;
-    tfree(c, cat0);
-
-    if (resblock(c, "conv_r01", r, true, false, c->out_chan, m, yout)) return 1;
-    tfree(c, r);
     return 0;
 }
 
@@ -1010,12 +948,14 @@ static int stream_encode(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S
     const int sy = pad ? 0 : 2;
     const Layer* L00 = find_layer(c, "conv_l00", "conv_1");
     if (!L00) return fail("missing layer conv_l00/conv_1");
-    Tensor h0 = alloc_hidden(c, m, S + 6, tin, block_fused(c, L00, false)), a = tallocp(c, m, S + 4, Hi - 2 * sy, Wi - 2 * sy, pad);
+    Tensor h0 = alloc_hidden(c, m, S + 6, tin, block_fused(c, L00, S + 4)), a = tallocp(c, m, S + 4, Hi - 2 * sy, Wi - 2 * sy, pad);
     const Layer *L01 = find_layer(c, "conv_l01", "conv_1"), *Lr00 = find_layer(c, "conv_r00", "conv_1"), *Lr01 = find_layer(c, "conv_r01", "conv_1");
     if (!L01 || !Lr00 || !Lr01) return fail("missing conv_1 layers of the level-0 blocks");
-    Tensor h1 = alloc_hidden(c, m, S + 2, a, block_fused(c, L01, true));
+    Tensor h1 = alloc_hidden(c, m, S + 2, a, block_fused(c, L01, S));
     Tensor y0r = pz ? Tensor() : tallocp(c, m, S, Hi - 4 * sy, Wi - 4 * sy, pad);
     if (h0.off < 0 || a.off < 0 || h1.off < 0 || (!pz && y0r.off < 0)) return fail("workspace exhausted (level-0 encoder slabs)");
+    // (branch probe: periodic in z, the planes [zlo, zhi + 4) of conv_l00's result and [zlo, zhi) of conv_l01's exist)
+    const int zr00[3] = {zlo, zhi + 4, pz ? D - 96 : 0}, zr01[3] = {zlo, zhi, pz ? D - 96 : 0};
     // Pipelined host path: the first slab is short (PIPE_EDGE planes), so that the kernels start as soon as a small first
     // upload has landed; the decoder's last slab is short for the same reason at the other end (its copy to the host is
     // the only one nothing hides).  Slabs start on even planes either way, so the fields do not change.
@@ -1029,26 +969,20 @@ static int stream_encode(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S
         // frames (branch probe): plane j of the persistent slab tensors is plane z + j of the layer's whole tensor
         { int og[3]; org_conv(zview(tin, z, n + 8), 2, og); set_org(a, og[0], og[1], og[2]);
           org_conv(a, 2, og); set_org(y0, og[0], og[1], og[2]); }
-        // (branch probe: periodic in z, the planes [zlo, zhi + 4) of conv_l00's result and [zlo, zhi) of conv_l01's exist)
-        auto zr = [&](int extra) { c->probe.zr[0] = zlo; c->probe.zr[1] = zhi + extra; c->probe.zr[2] = pz ? D - 96 : 0; };
         if (first) {
-            zr(4); if (resblock_part(c, "conv_l00", zview(tin, z, n + 8), h0, a, 0, n + 4, 0, n + 6, false, true)) return 1;
-            zr(0); if (resblock_part(c, "conv_l01", a, h1, y0, 0, n, 0, n + 2, true, true)) return 1;
+            if (resblock_part(c, "conv_l00", zview(tin, z, n + 8), h0, a, 0, n + 4, 0, n + 6, false, true, zr00)) return 1;
+            if (resblock_part(c, "conv_l01", a, h1, y0, 0, n, 0, n + 2, true, true, zr01)) return 1;
         } else {
-            zr(4); if (resblock_part(c, "conv_l00", zview(tin, z, n + 8), h0, a, 4, n, 6, n, false, true)) return 1;
-            zr(0); if (resblock_part(c, "conv_l01", a, h1, y0, 0, n, 2, n, true, true)) return 1;
+            if (resblock_part(c, "conv_l00", zview(tin, z, n + 8), h0, a, 4, n, 6, n, false, true, zr00)) return 1;
+            if (resblock_part(c, "conv_l01", a, h1, y0, 0, n, 2, n, true, true, zr01)) return 1;
         }
-        c->probe.zr[2] = 0;
         if (z + n < zhi) {                                       // what the next slab will not recompute
             carry_planes(c, h0, n, 0, 6);
             carry_planes(c, a, n, 0, 4);
             carry_planes(c, h1, n, 0, 2);
         }
         const int i0 = std::max(0, 40 - z), i1 = std::min(n, Y - 40 - z);      // planes of this slab inside the crop
-        if (!pz && i1 > i0 && !c->dry) {
-            Planes sp = y0.p; sp.G = c->mid / (c->prec == PREC_F16 ? 8 : 4);
-            launch_crop(sp, pad ? 0 : 40, zview(skip0, z + i0 - 40, i1 - i0).p, 0, c->vel, c->stream, i0);
-        }
+        if (!pz && i1 > i0) crop_into(c, y0, pad ? 0 : 40, zview(skip0, z + i0 - 40, i1 - i0), i0);
         {
             // planes [d0, d1) of this slab go through down_l0 (periodic in z: only the box's own planes, 44 .. Y - 44)
             const int d0 = pz ? std::max(z, 44) : z, d1 = pz ? std::min(z + n, Y - 44) : z + n;
@@ -1074,8 +1008,8 @@ static int stream_encode(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S
     return 0;
 }
 
-// Level 1 of the encoder outside brick mode: the down_l0 output td -> the level-1 skip connection cat1 (first half of the
-// decoder's concat) and the level-2 input t.
+// Level 1 of the encoder (whole tensors, and the z-slab schedule outside brick mode): the down_l0 output td -> the level-1
+// skip connection cat1 (first half of the decoder's concat) and the level-2 input t.
 // Periodic-yx: level 1 runs periodic in y and x as well -- its input is the interior result of down_l0 with a 1-voxel
 // wrap-around halo (and, periodic in z, 22 planes of periodic context); level 2 and below keep the padded scheme: down_l1
 // runs on the interior and is extended periodically by the 10 voxels those levels consume.
@@ -1096,18 +1030,12 @@ static int stream_level1(nbe_ctx* c, int pad, bool pz, Tensor td, Tensor* cat1_o
     if (pad) {
         cat1 = tallocp(c, 2 * m, y1.p.D - 32, y1.p.H - 2, y1.p.W - 2, 1);
         if (cat1.off < 0) return fail("workspace exhausted (cat1)");
-        if (!c->dry) {
-            Planes sp = y1.p; sp.G = c->mid / (c->prec == PREC_F16 ? 8 : 4);
-            launch_crop(sp, 0, cat1.p, 0, c->vel, c->stream, 16);
-        }
+        crop_into(c, y1, 0, cat1, 16);
         set_org(cat1, y1.org[0], y1.org[1] - 16, y1.org[2] - 16);    // cropped by 16 in z only; the frame moves by 16 on every axis
         Tensor t2 = talloc(c, m, y1.p.D / 2, (y1.p.H - 2) / 2, (y1.p.W - 2) / 2);
         const Layer* Ld1 = find_layer(c, "down_l1", "conv_0");
         if (t2.off < 0 || !Ld1) return fail("workspace exhausted or missing layer (down_l1)");
-        ConvLaunch cl; cl.in = inner(y1); cl.Dv = t2.p.D; cl.Hv = t2.p.H; cl.Wv = t2.p.W; cl.out = t2.p; cl.flags = F_ACT;
-        if (run_conv(c, *Ld1, cl, true)) return 1;
-        set_org(t2, y1.org[0] / 2, y1.org[1] / 2, y1.org[2] / 2);
-        probe_act(c, *Ld1, cl.out, 0, t2.org, cl.Dv, cl.Hv, cl.Wv, true);   // the interior; its periodic images are copies (wrap_pad below)
+        if (down_conv(c, *Ld1, y1, t2, true)) return 1;
         t = talloc(c, m, t2.p.D, t2.p.H + 20, t2.p.W + 20);
         if (t.off < 0) return fail("workspace exhausted (level 2 input)");
         if (!c->dry) launch_wrap_pad(t2.p, t.p, 10, c->vel, c->stream, 0);
@@ -1121,6 +1049,63 @@ static int stream_level1(nbe_ctx* c, int pad, bool pz, Tensor td, Tensor* cat1_o
     }
     tfree(c, y1);
     *cat1_out = cat1; *t_out = t;
+    return 0;
+}
+
+// Levels 2 and 3 and the level-1 decoder: the level-2 input t and the level-1 skip connection cat1 -> the level-1 decoder
+// output (conv_r1) in *r_out
+static int lower_levels(nbe_ctx* c, Tensor t, Tensor cat1, Tensor* r_out) {
+    const int m = c->mid;
+    Tensor y2, cat2, r;
+    if (resblock(c, "conv_l2", t, true, true, m, m, &y2)) return 1;
+    tfree(c, t);
+    cat2 = talloc(c, 2 * m, y2.p.D - 8, y2.p.H - 8, y2.p.W - 8);
+    if (cat2.off < 0) return fail("workspace exhausted (cat2)");
+    crop_into(c, y2, 4, cat2);
+    if (downblock(c, "down_l2", y2, &t)) return 1;
+    tfree(c, y2);
+
+    if (resblock(c, "conv_c", t, true, true, m, m, &r)) return 1;
+    tfree(c, t);
+
+    if (upblock(c, "up_r2", r, cat2)) return 1;
+    tfree(c, r);
+    if (resblock(c, "conv_r2", cat2, true, true, m, 2 * m, &r)) return 1;
+    tfree(c, cat2);
+
+    // periodic-yx (cat1.pad = 1): the level-2 result carries 2 voxels of y/x context that the periodic level 1 does not need
+    if (upblock(c, "up_r1", r, cat1, cat1.pad ? 2 : 0)) return 1;
+    fill_halo(c, cat1);
+    tfree(c, r);
+    if (resblock(c, "conv_r1", cat1, true, true, m, 2 * m, r_out)) return 1;
+    tfree(c, cat1);
+    return 0;
+}
+
+// the network body on whole tensors of a resident input tensor; returns conv_r01's output tensor (out_chan channels).  Only
+// the level-0 encoder and decoder differ from the z-slab schedule (network_stream).
+static int network(nbe_ctx* c, const Tensor& tin, Tensor* yout) {
+    const int m = c->mid;
+    Tensor a, y0, t, cat0, cat1, r;
+    if (resblock(c, "conv_l00", tin, false, true, m, m, &a)) return 1;
+    if (resblock(c, "conv_l01", a, true, true, m, m, &y0)) return 1;
+    tfree(c, a);
+    cat0 = talloc(c, 2 * m, y0.p.D - 80, y0.p.H - 80, y0.p.W - 80);
+    if (cat0.off < 0) return fail("workspace exhausted (cat0)");
+    crop_into(c, y0, 40, cat0);
+    if (downblock(c, "down_l0", y0, &t)) return 1;
+    tfree(c, y0);
+
+    if (stream_level1(c, 0, false, t, &cat1, &t)) return 1;
+    if (lower_levels(c, t, cat1, &r)) return 1;
+
+    if (upblock(c, "up_r0", r, cat0)) return 1;
+    tfree(c, r);
+    if (resblock(c, "conv_r00", cat0, true, true, m, 2 * m, &r)) return 1;
+    tfree(c, cat0);
+
+    if (resblock(c, "conv_r01", r, true, false, c->out_chan, m, yout)) return 1;
+    tfree(c, r);
     return 0;
 }
 
@@ -1142,6 +1127,22 @@ static Planes brick_planes(nbe_ctx* c, const Tensor& like, const void* buf, int 
     p.dx = c->vel ? (float*)buf + (int64_t)p.G * p.pstride * 4 : nullptr;
     return p;
 }
+// faces for the neighbours: planes [in, in + n) of t -> lo, the mirror planes [D - in - n, D - in) -> hi
+static void brick_send(nbe_ctx* c, const Tensor& t, int in, int n, void* lo, void* hi) {
+    if (c->dry) return;
+    for (int s = 0; s < 2; ++s)
+        launch_crop(zview(t, s ? t.p.D - in - n : in, n).p, 0, brick_planes(c, t, s ? hi : lo, n), 0, c->vel, c->stream, 0);
+}
+// the neighbours' faces (n planes shaped like `like`) -> the first (lo) and the last (hi) n planes of dst: wrap > 0 extends
+// them periodically by that many voxels in y and x (a level input), 0 copies them as they are (the skip connection)
+static void brick_recv(nbe_ctx* c, const Tensor& like, const void* lo, const void* hi, int n, const Tensor& dst, int wrap) {
+    if (c->dry) return;
+    for (int s = 0; s < 2; ++s) {
+        const Planes face = brick_planes(c, like, s ? hi : lo, n), to = zview(dst, s ? dst.p.D - n : 0, n).p;
+        if (wrap) launch_wrap_pad(face, to, wrap, c->vel, c->stream, 0);
+        else launch_crop(face, 0, to, 0, c->vel, c->stream, 0);
+    }
+}
 static int64_t brick_halo_bytes(nbe_ctx* c, int nplanes, int Hd, int Wd) {
     Planes p; p.G = planes_for(c->mid, c->prec); p.D = nplanes; p.H = Hd; p.W = Wd;
     p.pstride = (p.vox() + 63) & ~int64_t(63);
@@ -1152,9 +1153,9 @@ static int64_t brick_halo_bytes(nbe_ctx* c, int nplanes, int Hd, int Wd) {
 // part 1 = the planes next to the low face, part 2 = next to the high face
 static int brick_conv_l1(nbe_ctx* c, const Tensor& t, const Tensor& h, const Tensor& y1, int part) {
     const int B = t.p.D - 2 * BRICK_H1;
-    if (part == 0) return resblock_part(c, "conv_l1", t, h, y1, BRICK_H1, B - 4, BRICK_H1, B - 2, true, true);
-    if (part == 1) return resblock_part(c, "conv_l1", t, h, y1, 0, BRICK_H1, 0, BRICK_H1, true, true);
-    return resblock_part(c, "conv_l1", t, h, y1, B + 2, BRICK_H1, B + 4, BRICK_H1, true, true);
+    if (part == 0) return resblock_part(c, "conv_l1", t, h, y1, BRICK_H1, B - 4, BRICK_H1, B - 2, true, true, nullptr);
+    if (part == 1) return resblock_part(c, "conv_l1", t, h, y1, 0, BRICK_H1, 0, BRICK_H1, true, true, nullptr);
+    return resblock_part(c, "conv_l1", t, h, y1, B + 2, BRICK_H1, B + 4, BRICK_H1, true, true, nullptr);
 }
 
 // After the encoder: the level-1 tensors, the brick's own planes of the level-1 input, and the part of conv_l1 that needs
@@ -1166,7 +1167,7 @@ static int brick_interior(nbe_ctx* c, nbe_ctx::StreamState& st) {
     if (!L1) return fail("missing layer conv_l1/conv_1");
     st.t = tallocp(c, m, td.p.D + 2 * BRICK_H1, td.p.H, td.p.W, 1);
     if (st.t.off < 0) return fail("workspace exhausted (level 1 input)");
-    st.h = alloc_hidden(c, m, st.t.p.D - 2, st.t, block_fused(c, L1, true));
+    st.h = alloc_hidden(c, m, st.t.p.D - 2, st.t, block_fused(c, L1, st.t.p.D - 4));
     st.y1 = tallocp(c, m, st.t.p.D - 4, td.p.H, td.p.W, 1);
     if (st.h.off < 0 || st.y1.off < 0) return fail("workspace exhausted (level 1)");
     if (!c->dry) launch_wrap_pad(td.p, zview(st.t, BRICK_H1, td.p.D).p, 1, c->vel, c->stream, 0);
@@ -1179,29 +1180,19 @@ static int brick_edges(nbe_ctx* c, nbe_ctx::StreamState& st) {
     const int m = c->mid;
     Tensor& td = st.td;
     const int B = td.p.D;
-    if (!c->dry) {
-        launch_wrap_pad(brick_planes(c, td, c->bio.recv_lo, BRICK_H1), zview(st.t, 0, BRICK_H1).p, 1, c->vel, c->stream, 0);
-        launch_wrap_pad(brick_planes(c, td, c->bio.recv_hi, BRICK_H1), zview(st.t, BRICK_H1 + B, BRICK_H1).p, 1, c->vel, c->stream, 0);
-    }
+    brick_recv(c, td, c->bio.recv_lo, c->bio.recv_hi, BRICK_H1, st.t, 1);
     if (brick_conv_l1(c, st.t, st.h, st.y1, 1) || brick_conv_l1(c, st.t, st.h, st.y1, 2)) return 1;
     tfree(c, st.h); tfree(c, st.t); tfree(c, td);
     Tensor& y1 = st.y1;                                           // planes [-4, B + 4) of the brick's level-1 encoder output
     st.cat1 = tallocp(c, 2 * m, y1.p.D, y1.p.H - 2, y1.p.W - 2, 1);
     if (st.cat1.off < 0) return fail("workspace exhausted (cat1)");
-    if (!c->dry) {
-        Planes sp = y1.p; sp.G = c->mid / (c->prec == PREC_F16 ? 8 : 4);
-        launch_crop(sp, 0, st.cat1.p, 0, c->vel, c->stream, 0);
-    }
+    crop_into(c, y1, 0, st.cat1, 0);
     st.t2 = talloc(c, m, B / 2, (y1.p.H - 2) / 2, (y1.p.W - 2) / 2);
     const Layer* Ld1 = find_layer(c, "down_l1", "conv_0");
     if (st.t2.off < 0 || !Ld1) return fail("workspace exhausted or missing layer (down_l1)");
-    ConvLaunch cl; cl.in = inner(zview(y1, 4, B)); cl.Dv = st.t2.p.D; cl.Hv = st.t2.p.H; cl.Wv = st.t2.p.W; cl.out = st.t2.p; cl.flags = F_ACT;
-    if (run_conv(c, *Ld1, cl, true)) return 1;
+    if (down_conv(c, *Ld1, zview(y1, 4, B), st.t2, false)) return 1;
     tfree(c, y1);
-    if (!c->dry && c->bio.send_lo) {
-        launch_crop(zview(st.t2, 0, BRICK_H2).p, 0, brick_planes(c, st.t2, c->bio.send_lo, BRICK_H2), 0, c->vel, c->stream, 0);
-        launch_crop(zview(st.t2, st.t2.p.D - BRICK_H2, BRICK_H2).p, 0, brick_planes(c, st.t2, c->bio.send_hi, BRICK_H2), 0, c->vel, c->stream, 0);
-    }
+    if (c->bio.send_lo) brick_send(c, st.t2, 0, BRICK_H2, c->bio.send_lo, c->bio.send_hi);
     return 0;
 }
 
@@ -1211,11 +1202,8 @@ static int brick_level2(nbe_ctx* c, nbe_ctx::StreamState& st, Tensor* t_out) {
     Tensor& t2 = st.t2;
     Tensor t = talloc(c, c->mid, t2.p.D + 2 * BRICK_H2, t2.p.H + 20, t2.p.W + 20);
     if (t.off < 0) return fail("workspace exhausted (level 2 input)");
-    if (!c->dry) {
-        launch_wrap_pad(t2.p, zview(t, BRICK_H2, t2.p.D).p, 10, c->vel, c->stream, 0);
-        launch_wrap_pad(brick_planes(c, t2, c->bio.recv_lo, BRICK_H2), zview(t, 0, BRICK_H2).p, 10, c->vel, c->stream, 0);
-        launch_wrap_pad(brick_planes(c, t2, c->bio.recv_hi, BRICK_H2), zview(t, BRICK_H2 + t2.p.D, BRICK_H2).p, 10, c->vel, c->stream, 0);
-    }
+    if (!c->dry) launch_wrap_pad(t2.p, zview(t, BRICK_H2, t2.p.D).p, 10, c->vel, c->stream, 0);
+    brick_recv(c, t2, c->bio.recv_lo, c->bio.recv_hi, BRICK_H2, t, 10);
     tfree(c, t2);
     *t_out = t;
     return 0;
@@ -1227,27 +1215,8 @@ static int stream_tail(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S, 
     const int sy = pad ? 0 : 2;
     const Layer *Lr00 = find_layer(c, "conv_r00", "conv_1"), *Lr01 = find_layer(c, "conv_r01", "conv_1");
     if (!Lr00 || !Lr01) return fail("missing conv_1 layers of the level-0 blocks");
-    Tensor y2, cat2, r;
-    if (resblock(c, "conv_l2", t, true, true, m, m, &y2)) return 1;
-    tfree(c, t);
-    cat2 = talloc(c, 2 * m, y2.p.D - 8, y2.p.H - 8, y2.p.W - 8);
-    if (cat2.off < 0) return fail("workspace exhausted (cat2)");
-    crop_into(c, y2, 4, cat2);
-    if (downblock(c, "down_l2", y2, &t)) return 1;
-    tfree(c, y2);
-    if (resblock(c, "conv_c", t, true, true, m, m, &r)) return 1;
-    tfree(c, t);
-    if (upblock(c, "up_r2", r, cat2)) return 1;
-    tfree(c, r);
-    if (resblock(c, "conv_r2", cat2, true, true, m, 2 * m, &r)) return 1;
-    tfree(c, cat2);
-    // periodic-yx: the level-2 result carries 2 voxels of y/x context that the periodic level 1 does not need
-    if (upblock(c, "up_r1", r, cat1, pad ? 2 : 0)) return 1;
-    fill_halo(c, cat1);
-    tfree(c, r);
-    if (resblock(c, "conv_r1", cat1, true, true, m, 2 * m, &r)) return 1;      // r: level-1 decoder output
-    tfree(c, cat1);
-    const int rcrop = 0;
+    Tensor r;                                                    // the level-1 decoder output
+    if (lower_levels(c, t, cat1, &r)) return 1;
     if (2 * r.p.D != skip0.p.D || 2 * (r.p.H - 2 * r.pad) != skip0.p.H - 2 * pad || 2 * (r.p.W - 2 * r.pad) != skip0.p.W - 2 * pad)
         return fail("internal: level-0 concat geometry mismatch");
 
@@ -1255,8 +1224,7 @@ static int stream_tail(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S, 
         // brick mode: the neighbours' planes of the skip connection, below and above the brick's own -- the last of the four
         // exchanges to be needed; it travelled while levels 1-3 ran, and only now does the stream wait for it
         if (c->bio.skip_ready) HIPCHK(hipStreamWaitEvent(c->stream, c->bio.skip_ready, 0));
-        launch_crop(brick_planes(c, skip0, c->bio.skip_recv_lo, BRICK_H0), 0, zview(skip0, 0, BRICK_H0).p, 0, c->vel, c->stream, 0);
-        launch_crop(brick_planes(c, skip0, c->bio.skip_recv_hi, BRICK_H0), 0, zview(skip0, skip0.p.D - BRICK_H0, BRICK_H0).p, 0, c->vel, c->stream, 0);
+        brick_recv(c, skip0, c->bio.skip_recv_lo, c->bio.skip_recv_hi, BRICK_H0, skip0, 0);
     }
     const int Yo = skip0.p.D - 8;                                 // output planes (= D - 96)
     // Persistent slab tensors of the level-0 decoder, with the same carry-over of the overlaps (8 / 6 / 4 / 2 planes of
@@ -1264,9 +1232,9 @@ static int stream_tail(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S, 
     const int Hs = skip0.p.H - 2 * pad, Ws = skip0.p.W - 2 * pad;
     // Fused blocks on the gauged f16x3 kernel read concat([skip, up]) from two tensors (core :168-169 without the concat):
     // the slab's planes of the skip connection where they are, the up-sampled half in a mid-channel tensor of its own.
-    const bool two = block_fused(c, Lr00, true) && c->mid % 16 == 0;   // the kernel switches sources between 16-channel chunks
-    Tensor cat = tallocp(c, two ? m : 2 * m, S + 8, Hs, Ws, pad), hq = alloc_hidden(c, 2 * m, S + 6, cat, block_fused(c, Lr00, true));
-    Tensor q = tallocp(c, m, S + 4, Hs - 2 * sy, Ws - 2 * sy, pad), hy = alloc_hidden(c, m, S + 2, q, block_fused(c, Lr01, true));
+    const bool two = block_fused(c, Lr00, S + 4) && c->mid % 16 == 0;   // the kernel switches sources between 16-channel chunks
+    Tensor cat = tallocp(c, two ? m : 2 * m, S + 8, Hs, Ws, pad), hq = alloc_hidden(c, 2 * m, S + 6, cat, block_fused(c, Lr00, S + 4));
+    Tensor q = tallocp(c, m, S + 4, Hs - 2 * sy, Ws - 2 * sy, pad), hy = alloc_hidden(c, m, S + 2, q, block_fused(c, Lr01, S));
     Tensor y = tallocp(c, c->out_chan, S, Hs - 4 * sy, Ws - 4 * sy, pad);
     if (cat.off < 0 || hq.off < 0 || q.off < 0 || hy.off < 0 || y.off < 0) return fail("workspace exhausted (level-0 decoder slabs)");
     for (int z = 0, n = 0; z < Yo; z += n) {
@@ -1278,17 +1246,17 @@ static int stream_tail(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S, 
         set_org(cat, skip0.org[0] + z, skip0.org[1], skip0.org[2]);  // slab-local plane j of the concat is plane z + j of the skip connection
         { int og[3]; org_conv(cat, 2, og); set_org(q, og[0], og[1], og[2]); }
         if (!two && !c->dry) launch_crop(zview(skip0, z + c0, cn).p, 0, zview(cat, c0, cn).p, 0, c->vel, c->stream, 0);
-        if (upblock(c, "up_r0", zview(r, (z + c0) / 2, cn / 2), zview(cat, c0, cn), rcrop, two ? 0 : -1)) return 1;
+        if (upblock(c, "up_r0", zview(r, (z + c0) / 2, cn / 2), zview(cat, c0, cn), 0, two ? 0 : -1)) return 1;
         fill_halo(c, zview(cat, c0, cn));
         // two sources: slab-local plane j of the concat is plane z + j of the skip connection
         const Tensor sk = two ? zview(skip0, z, std::min(S + 8, skip0.p.D - z)) : cat;
         const Tensor* up2 = two ? &cat : nullptr;
         if (first) {
-            if (resblock_part(c, "conv_r00", sk, hq, q, 0, n + 4, 0, n + 6, true, true, up2)) return 1;
-            if (resblock_part(c, "conv_r01", q, hy, y, 0, n, 0, n + 2, true, false)) return 1;
+            if (resblock_part(c, "conv_r00", sk, hq, q, 0, n + 4, 0, n + 6, true, true, nullptr, up2)) return 1;
+            if (resblock_part(c, "conv_r01", q, hy, y, 0, n, 0, n + 2, true, false, nullptr)) return 1;
         } else {
-            if (resblock_part(c, "conv_r00", sk, hq, q, 4, n, 6, n, true, true, up2)) return 1;
-            if (resblock_part(c, "conv_r01", q, hy, y, 0, n, 2, n, true, false)) return 1;
+            if (resblock_part(c, "conv_r00", sk, hq, q, 4, n, 6, n, true, true, nullptr, up2)) return 1;
+            if (resblock_part(c, "conv_r01", q, hy, y, 0, n, 2, n, true, false, nullptr)) return 1;
         }
         if (z + n < Yo) {
             carry_planes(c, cat, n, 0, 8);
@@ -1325,14 +1293,9 @@ static int network_stream(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int 
         st.tin = tin; st.S = S;
         if (c->phase == 1) {
             // the boundary planes of the down_l0 output for the neighbours
-            if (!c->dry) {
-                launch_crop(zview(st.td, 0, BRICK_H1).p, 0, brick_planes(c, st.td, c->bio.send_lo, BRICK_H1), 0, c->vel, c->stream, 0);
-                launch_crop(zview(st.td, st.td.p.D - BRICK_H1, BRICK_H1).p, 0, brick_planes(c, st.td, c->bio.send_hi, BRICK_H1), 0, c->vel, c->stream, 0);
-                // ... and the first / last four of the brick's own planes of the skip connection (planes 4 .. D - 4 of the tensor)
-                const int own = st.skip0.p.D - 2 * BRICK_H0;
-                launch_crop(zview(st.skip0, BRICK_H0, BRICK_H0).p, 0, brick_planes(c, st.skip0, c->bio.skip_send_lo, BRICK_H0), 0, c->vel, c->stream, 0);
-                launch_crop(zview(st.skip0, own, BRICK_H0).p, 0, brick_planes(c, st.skip0, c->bio.skip_send_hi, BRICK_H0), 0, c->vel, c->stream, 0);
-            }
+            brick_send(c, st.td, 0, BRICK_H1, c->bio.send_lo, c->bio.send_hi);
+            // ... and the first / last four of the brick's own planes of the skip connection (planes 4 .. D - 4 of the tensor)
+            brick_send(c, st.skip0, BRICK_H0, BRICK_H0, c->bio.skip_send_lo, c->bio.skip_send_hi);
             st.valid = true; st.stage = 1; stash_arena(c);
             return 0;
         }
@@ -1366,9 +1329,11 @@ static int check_dims_pyx(int D, int H, int W) {
     return 0;
 }
 
-// bytes of workspace a (D,H,W) input needs with the current schedule (c->slab): a dry run of the network through
-// the arena (no launches); < 0 on error
-static int64_t workspace_need(nbe_ctx* c, int D, int H, int W) {
+// bytes of workspace a (D,H,W) input needs with the schedule (slab, pyx, pz): a dry run of the network through the arena
+// (no launches) with that schedule in place of the current one, which it leaves as it was; < 0 on error
+static int64_t workspace_need(nbe_ctx* c, int D, int H, int W, int slab, bool pyx, bool pz) {
+    const int keep_slab = c->slab; const bool keep_pyx = c->pyx, keep_pz = c->pz;
+    c->slab = slab; c->pyx = pyx; c->pz = pz;
     c->dry = true;
     c->arena.reset();
     Tensor tin = talloc(c, c->in_chan, D, H, W), y;
@@ -1376,12 +1341,13 @@ static int64_t workspace_need(nbe_ctx* c, int D, int H, int W) {
     HeadOut ho{};
     const int rc = c->slab > 0 ? network_stream(c, tin, ho, c->slab) : network(c, tin, &y);
     c->dry = false;
+    c->slab = keep_slab; c->pyx = keep_pyx; c->pz = keep_pz;
     return rc ? -1 : c->arena.high;
 }
 
-// size the workspace for a (D,H,W) input with a dry run, then (re)allocate it
+// size the workspace for a (D,H,W) input with a dry run of the current schedule, then (re)allocate it
 static int ensure_workspace(nbe_ctx* c, int D, int H, int W) {
-    const int64_t need = workspace_need(c, D, H, W);
+    const int64_t need = workspace_need(c, D, H, W, c->slab, c->pyx, c->pz);
     if (need < 0) return 1;
     if (need > c->ws_bytes) {
         c->sst.valid = false;
@@ -2055,10 +2021,7 @@ int nbe_plan_tiles(const int64_t region[3], const int ndiv[3], int max_tile, int
 static int choose_slab(nbe_ctx* c, int D, int H, int W, int64_t budget, int64_t* need_out, bool pyx = false,
                        bool pz = false) {
     const int forced = c->slab_forced;
-    const int keep = c->slab;
-    const bool keep_p = c->pyx, keep_z = c->pz;
     int result = -1;
-    c->pyx = pyx; c->pz = pyx && pz;
     // deeper slabs than 128 planes buy < 1 % (the 2-plane overlaps are already < 5 % there) for tens of GB of workspace
     const int cand[4] = {0, 128, 64, 32};
     for (int i = 0; i < 4 && result < 0; ++i) {
@@ -2067,13 +2030,28 @@ static int choose_slab(nbe_ctx* c, int D, int H, int W, int64_t budget, int64_t*
         if (forced == 0 && S != 0) break;
         if (forced > 0) { if (i > (pyx ? 1 : 0)) break; S = forced & ~1; }
         if (!pyx && S > 0 && D - 8 <= S) continue;                // a single slab is the whole-tensor schedule
-        c->slab = S;
-        const int64_t need = workspace_need(c, D, H, W);
+        const int64_t need = workspace_need(c, D, H, W, S, pyx, pyx && pz);
         if (need >= 0 && need <= budget) { result = S; if (need_out) *need_out = need; }
     }
-    c->slab = keep;
-    c->pyx = keep_p; c->pz = keep_z;
     return result;
+}
+
+// The schedule of a tile of e0 x e1 x e2 output voxels under a memory budget, installed in c (c->slab, c->pyx, c->pz):
+// periodic-yx when the tile spans the periodic box in y and x (spans_yx), then also periodic in z when it is the box's
+// whole z extent (whole_z); padded otherwise.  false: nothing fits, c is left as it was -- unless fallback32 (nothing fits
+// the budget: the padded schedule in 32-plane slabs, the smallest footprint, when the slab depth is not forced).
+static bool choose_schedule(nbe_ctx* c, int e0, int e1, int e2, bool spans_yx, bool whole_z, int64_t budget, bool fallback32) {
+    const int D = e0 + 96;                                       // input depth: the 48 planes of context on either side
+    if (spans_yx && !check_dims_pyx(D, e1 + 2, e2 + 2)) {
+        const int sl = choose_slab(c, D, e1 + 2, e2 + 2, budget, nullptr, true, whole_z);
+        if (sl > 0) { c->slab = sl; c->pyx = true; c->pz = whole_z; return true; }
+    }
+    if (check_dims(D, e1 + 96, e2 + 96)) return false;
+    int sl = choose_slab(c, D, e1 + 96, e2 + 96, budget, nullptr);
+    if (sl < 0 && fallback32 && c->slab_forced < 0 && D - 8 > 32) sl = 32;
+    if (sl < 0) return false;
+    c->slab = sl; c->pyx = false; c->pz = false;
+    return true;
 }
 
 // The grid process_region will run: among all merges of the caller's sub-boxes (exact only when crop % 8 == 0 on
@@ -2099,25 +2077,10 @@ static int plan_tiles_mem(nbe_ctx* c, const int64_t region[3], const int ndiv[3]
     full_yx = full_yx && c->pyx_allowed;
     const int64_t budget = plan_budget(c, reserve);
     if (budget < 0) return 0;
-    // schedule of a tile of e0 x e1 x e2 output voxels: periodic-yx when it spans the box in y and x, else padded
-    auto schedule = [&](int64_t e0, int64_t e1, int64_t e2, bool spans, int* slab, bool* pyx) -> bool {
-        if (spans && full_yx && !check_dims_pyx((int)e0 + 96, (int)e1 + 2, (int)e2 + 2)) {
-            const int sl = choose_slab(c, (int)e0 + 96, (int)e1 + 2, (int)e2 + 2, budget, nullptr, true, full_z && e0 == region[0]);
-            if (sl > 0) { *slab = sl; *pyx = true; return true; }
-        }
-        if (check_dims((int)e0 + 96, (int)e1 + 96, (int)e2 + 96)) return false;
-        const int sl = choose_slab(c, (int)e0 + 96, (int)e1 + 96, (int)e2 + 96, budget, nullptr, false);
-        if (sl < 0) return false;
-        *slab = sl; *pyx = false;
-        return true;
-    };
-    int best_slab = 0;
-    bool best_pyx = false;
-    schedule(region[0] / ndiv[0], region[1] / ndiv[1], region[2] / ndiv[2], ndiv[1] == 1 && ndiv[2] == 1 &&
-             region[1] % ndiv[1] == 0 && region[2] % ndiv[2] == 0, &best_slab, &best_pyx);       // the caller's own grid
+    // the caller's own grid; from here on c holds the schedule of the best tile so far
+    choose_schedule(c, (int)(region[0] / ndiv[0]), (int)(region[1] / ndiv[1]), (int)(region[2] / ndiv[2]),
+                    full_yx && ndiv[1] == 1 && ndiv[2] == 1, full_z && ndiv[0] == 1, budget, false);
     (void)nbe_last_error();
-    c->slab = best_slab; c->pyx = best_pyx;
-    c->pz = best_pyx && full_z && ndiv[0] == 1;
     if (c->max_tile <= 0) return 0;
     int64_t crop[3];
     for (int a = 0; a < 3; ++a) {
@@ -2135,28 +2098,22 @@ static int plan_tiles_mem(nbe_ctx* c, const int64_t region[3], const int ndiv[3]
                 const int64_t e0 = crop[0] * m0, e1 = crop[1] * m1, e2 = crop[2] * m2, vol = e0 * e1 * e2;
                 const int64_t w = e2 * 1000000 + e1 * 1000 + e0;               // tie-break: long last axis
                 if (vol < best_vol || (vol == best_vol && w <= best_w)) continue;
-                int sl = 0; bool px = false;
-                if (!schedule(e0, e1, e2, m1 == ndiv[1] && m2 == ndiv[2], &sl, &px)) {
+                const bool spans = full_yx && m1 == ndiv[1] && m2 == ndiv[2], whole_z = full_z && e0 == region[0];
+                if (!choose_schedule(c, (int)e0, (int)e1, (int)e2, spans, whole_z, budget, false)) {
                     (void)nbe_last_error();
                     if (vol > miss_vol) {                        // what the largest merge that did not fit would have needed
-                        const bool spans = m1 == ndiv[1] && m2 == ndiv[2] && full_yx;
-                        const bool kp = c->pyx, kz = c->pz; const int ks_ = c->slab;
-                        c->pyx = spans; c->pz = spans && full_z && e0 == region[0]; c->slab = 32;
                         const int ext = spans ? 2 : 96;
-                        const int64_t need = workspace_need(c, (int)e0 + 96, (int)e1 + ext, (int)e2 + ext);
-                        c->pyx = kp; c->pz = kz; c->slab = ks_;
+                        const int64_t need = workspace_need(c, (int)e0 + 96, (int)e1 + ext, (int)e2 + ext, 32, spans, spans && whole_z);
                         (void)nbe_last_error();
                         if (need > 0) { miss_vol = vol; miss_need = need; }
                     }
                     continue;
                 }
-                best_vol = vol; best_w = w; best_slab = sl; best_pyx = px;
+                best_vol = vol; best_w = w;
                 out_ndiv[0] = ndiv[0] / m0; out_ndiv[1] = ndiv[1] / m1; out_ndiv[2] = ndiv[2] / m2;
             }
         }
     }
-    c->slab = best_slab; c->pyx = best_pyx;
-    c->pz = best_pyx && full_z && out_ndiv[0] == 1;
     c->plan_tiles = out_ndiv[0] * out_ndiv[1] * out_ndiv[2];
     c->plan_short_gb = 0.0;
     if (miss_vol > best_vol) {                                   // a larger exact merge exists and only memory kept the planner from it
@@ -2245,19 +2202,9 @@ static int process_region(nbe_ctx* c, const void* box, const int64_t bsize[3], c
             c->slab = 0; c->pyx = false; c->pz = false;
             const int64_t budget = plan_budget(c, reserve);
             if (budget < 0 || !c->have_weights) return;
-            const int e0 = (int)(region[0] / ndiv_eff[0]), e1 = (int)(region[1] / ndiv_eff[1]), e2 = (int)(region[2] / ndiv_eff[2]);
-            if (full_yx && ndiv_eff[1] == 1 && ndiv_eff[2] == 1 && !check_dims_pyx(e0 + 96, e1 + 2, e2 + 2)) {
-                const bool z1 = full_z && ndiv_eff[0] == 1;
-                const int sl = choose_slab(c, e0 + 96, e1 + 2, e2 + 2, budget, nullptr, true, z1);
-                if (sl > 0) { c->slab = sl; c->pyx = true; c->pz = z1; return; }
-            }
+            choose_schedule(c, (int)(region[0] / ndiv_eff[0]), (int)(region[1] / ndiv_eff[1]), (int)(region[2] / ndiv_eff[2]),
+                            full_yx && ndiv_eff[1] == 1 && ndiv_eff[2] == 1, full_z && ndiv_eff[0] == 1, budget, true);
             (void)nbe_last_error();
-            const int d = e0 + 96, h = e1 + 96, w = e2 + 96;
-            if (d >= 104 && h >= 104 && w >= 104 && !(d % 8) && !(h % 8) && !(w % 8)) {
-                const int sl = choose_slab(c, d, h, w, budget, nullptr);
-                if (sl > 0) c->slab = sl;
-                else if (sl < 0 && c->slab_forced < 0 && d - 8 > 32) c->slab = 32;   // nothing fits the budget: smallest footprint
-            }
         };
         if (order) schedule_for_grid();                          // explicit sub-box list: the caller's grid as given
         else if (plan_tiles_mem(c, region, ndiv_in, reserve, full_yx, full_z, ndiv_eff)) return 1;
@@ -2517,7 +2464,7 @@ static int brick_setup(nbe_ctx* c, const int64_t bsize[3], int* D, int* H, int* 
     int64_t need = 0;
     const int sl = choose_slab(c, *D, *H, *W, budget < 0 ? INT64_MAX / 4 : budget, &need, true, false);
     if (sl <= 0) { c->zx = false; return fail("brick of %lld x %lld x %lld does not fit the device memory that is free", (long long)b0, (long long)S1, (long long)S2); }
-    c->slab = sl; c->pyx = true; c->pz = false;
+    c->slab = sl;
     c->bp_size[0] = b0; c->bp_size[1] = S1; c->bp_size[2] = S2; c->bp_slab = sl; c->bp_need = need;
     if (need_out) *need_out = need;
     return 0;
@@ -2535,7 +2482,7 @@ int64_t nbe_brick_halo_bytes(nbe_ctx* c, const int64_t bsize[3], int which) {
 int nbe_brick_plan(nbe_ctx* c, const int64_t bsize[3]) {
     if (!c || !bsize) return 0;
     int D, H, W;
-    const int keep_slab = c->slab; const bool kp = c->pyx, kz = c->pz;
+    const int keep_slab = c->slab; const bool kp = c->pyx, kz = c->pz;   // the caller's plan survives a brick plan
     int rc = brick_setup(c, bsize, &D, &H, &W);
     // take the workspace now: what is free when the first brick is encoded may be less (other ranks of a shared card, the
     // caller's exchange buffers), and the ranks must not part ways after they have agreed on brick mode
