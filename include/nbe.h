@@ -308,6 +308,41 @@ int nbe_test_layer_gauged(nbe_ctx* ctx, int flags, const float* x, const float* 
 int nbe_test_layer_gauged_res(nbe_ctx* ctx, int flags, const float* x, const float* dx, int cin, int D, int H, int W,
                               const float* w, const float* beta, const float* bias, int cout, const float* res,
                               const float* dres, float* y, float* dy);
+/* One BLOCK of the loaded, modulated network (style_blocks_vel.py:40-85, :96-166) through the production schedule functions
+ * -- the same calls a box makes, so skip fusion, two-source reads, Winograd-z, the hidden tensor's pitch, the narrow tile,
+ * the output gauges and the one-launch up-sampling are chosen exactly as in a box.  Host NCDHW float32 in and out.
+ *   block      "conv_l00" ... "conv_r01" (residual blocks), "down_l0" ... "down_l2", "up_r2" ... "up_r0"
+ *   pad        0: VALID (y and x shrink); 1: periodic-yx -- x, x2, y, h hold interiors, the engine's tensors carry a 1-voxel
+ *              wrap-around halo that the hook fills with the schedule's own halo fill
+ *   x, dx      (cin, D, H, W); dx = NULL for conv_l00 (the input field has no tangent) and for displacement-only contexts
+ *   x2, dx2    decoder blocks conv_r2 / conv_r1 / conv_r00: NULL -> x is the materialised concat([skip, up]) of 2 mid channels;
+ *              else x = the skip half and x2 = the up-sampled half, mid channels each, and two_source selects whether the
+ *              block reads them as two tensors (the first-slab call of the z-slab schedule: fused blocks, mid a multiple
+ *              of 16, of 32 in the float16 model) or from a concat tensor.  up_r*: the skip half (mid, 2D, 2H, 2W) of the concat tensor the layer writes
+ *              its result into -- y is then the whole (2 mid) concat tensor; NULL -> a mid-channel tensor of its own (the
+ *              two-source form of the z-slab schedule).  Other blocks: NULL.
+ *   y, dy      residual blocks (cout, D - 4, H - 4, W - 4) (pad = 1: (cout, D - 4, H, W)); down (mid, D/2, H/2, W/2); up
+ *              (mid or 2 mid, 2D, 2H, 2W)
+ *   h, dh      residual blocks: the hidden tensor between conv_0 and conv_1, (cmid, D - 2, H - 2, W - 2) (pad = 1: (cmid, D - 2, H, W));
+ *              may be NULL
+ *   gauges     3 * 2 * mid floats: the tangent gauges of the input [0, 2 mid), the hidden [2 mid, 4 mid) and the output
+ *              [4 mid, 6 mid) tensor as the device holds them (zero-filled beyond the tensor's channels, for gauge 0 and
+ *              when the context is not gauged).  Tangents cross this call AS STORED: dx + gauge (.) x on the way in, and
+ *              likewise dh, dy on the way out; the hook does no gauge arithmetic.
+ *   paths      which paths the launches took: see the enum
+ * The call's range shift is applied as a box applies it (max(max |x|, max |bias|) -> the power of two, biases scaled) and
+ * divided out of what is returned.  The workspace is sized by a dry run; a pending brick is invalidated.  Returns 1 with a
+ * message for a block, shape or form it cannot run.  Not to be called between nbe_probe_begin and nbe_probe_end. */
+enum { NBE_PATH_SKIP_FUSED = 1,        /* the block's 1x1x1 skip ran inside conv_1                                     */
+       NBE_PATH_TWO_SOURCE = 2,        /* conv_0 read concat([x, x2]) from two tensors                                  */
+       NBE_PATH_WINO_0 = 4,            /* conv_0 ran the Winograd-z kernel                                              */
+       NBE_PATH_WINO_1 = 8,            /* conv_1 ran the Winograd-z kernel                                              */
+       NBE_PATH_NARROW = 16,           /* a launch ran on the narrow 16-cout tile                                       */
+       NBE_PATH_UP8 = 32,              /* all eight parities of the up-sampling in one launch                           */
+       NBE_PATH_SKIP_NODX = 64,        /* the fused skip ran without an input tangent (conv_l00)                        */
+       NBE_PATH_TWO_SOURCE_SKIP = 128  /* the fused skip read its input from two tensors                                */ };
+int nbe_test_block(nbe_ctx* ctx, const char* block, int pad, int two_source, const float* x, const float* dx, int D, int H, int W,
+                   const float* x2, const float* dx2, float* y, float* dy, float* h, float* dh, float* gauges, int* paths);
 /* modulation kernel alone: OIDHW weight -> (w_n, dw_tot) */
 int nbe_test_modulate(nbe_ctx* ctx, const float* weight, const float* style_weight, const float* style_bias,
                       int cout, int cin, int k, float s0, float s1, float eps, int first_layer,

@@ -263,6 +263,7 @@ struct nbe_ctx {
         unsigned* bits = nullptr; int64_t words = 0;
         unsigned* count = nullptr;                // per slot: words written
     } probe;
+    int* paths = nullptr;                         // nbe_test_block: run_conv records which paths the launches took (NBE_PATH_*)
     // profiling
     bool prof = false;
     std::vector<ProfEntry> prof_entries;
@@ -533,6 +534,11 @@ static int run_conv(nbe_ctx* c, const Layer& L, const ConvLaunch& cl_in, bool ha
     // (the float16 model's form adds the residual in its epilogue: its blocks run their skips as launches of their own)
     cl.wino = (g6 || nov) && c->wino_ok && &pw == &L.pw && pw.ww && (!cl.skw || cl.skw->ww) && (c->prec == PREC_F16 || !(cl.flags & F_RES)) &&
               (cl.Dv & 1) == 0 && cl.in_off == 0 && cl.osz == 1 && !wino_env_off();
+    if (c->paths)
+        *c->paths |= (cl.skw ? NBE_PATH_SKIP_FUSED : 0) | (cl.skw && (cl.flags & F_SKIP_NODX) ? NBE_PATH_SKIP_NODX : 0) |
+                     (cl.csplit_ch ? NBE_PATH_TWO_SOURCE : 0) | (cl.skw && cl.sk_split_ch ? NBE_PATH_TWO_SOURCE_SKIP : 0) |
+                     (cl.wino ? (L.layer == "conv_1" ? NBE_PATH_WINO_1 : NBE_PATH_WINO_0) : 0) |
+                     (&pw == &L.pwn ? NBE_PATH_NARROW : 0) | (cl.set < 0 ? NBE_PATH_UP8 : 0);
     int pe = -1; hipEvent_t ea = nullptr, eb = nullptr;
     if (c->prof) {
         std::string pn = cl.wino ? std::string(c->prec == PREC_F16 ? "conv_h1w<FLAT3,vel,dx>" : c->vel ? "conv_h3w<FLAT3,vel,dx>" : "conv_h3w<FLAT3,novel>")
@@ -584,6 +590,10 @@ static bool wino_only_fuse(const nbe_ctx* c) { return !c->vel || c->prec == PREC
 static bool block_fused(const nbe_ctx* c, const Layer* L1, int nres) {
     return c->fuse && L1->fskip != nullptr && (!wino_only_fuse(c) || (!wino_env_off() && (nres & 1) == 0));
 }
+
+// Can a fused decoder block read concat([skip, up]) from two tensors?  The kernels switch sources between whole K chunks: 16
+// channels in conv_h3g_kernel / conv_h3w_kernel, 32 in the float16 model's Winograd-z form (the one kernel that fuses there).
+static bool two_source_width(const nbe_ctx* c) { return c->mid % (c->prec == PREC_F16 ? 32 : 16) == 0; }
 
 // hidden tensor of a block whose input x has `pad`: interior (Hi - sy) x (Wi - sy).  A fused block gives it the row
 // and plane pitch of x (conv_h3g_kernel fetches the skip's patches of x with the offsets of its own input's).
@@ -643,7 +653,9 @@ static int resblock_part(nbe_ctx* c, const char* name, const Tensor& x, const Te
 }
 
 // the block on whole tensors: its result is allocated (cout channels), the hidden tensor (cmid channels) lives meanwhile
-static int resblock(nbe_ctx* c, const char* name, const Tensor& x, bool has_dx, bool final_act, int cout, int cmid, Tensor* out) {
+// (hidden_out: a view of the released hidden tensor, whose planes stay as they are until the next allocation -- nbe_test_block)
+static int resblock(nbe_ctx* c, const char* name, const Tensor& x, bool has_dx, bool final_act, int cout, int cmid, Tensor* out,
+                    Tensor* hidden_out = nullptr) {
     const Layer* L1 = find_layer(c, name, "conv_1");
     if (!L1) return fail("missing layers of block %s", name);
     const int D = x.p.D, pad = x.pad;
@@ -653,6 +665,7 @@ static int resblock(nbe_ctx* c, const char* name, const Tensor& x, bool has_dx, 
     if (s.off < 0 || h.off < 0) return fail("workspace exhausted in block %s", name);
     if (resblock_part(c, name, x, h, s, 0, D - 4, 0, D - 2, has_dx, final_act, nullptr)) return 1;
     tfree(c, h);
+    if (hidden_out) *hidden_out = h;
     int og[3];
     org_conv(x, 2, og);
     set_org(s, og[0], og[1], og[2]);
@@ -1232,7 +1245,7 @@ static int stream_tail(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S, 
     const int Hs = skip0.p.H - 2 * pad, Ws = skip0.p.W - 2 * pad;
     // Fused blocks on the gauged f16x3 kernel read concat([skip, up]) from two tensors (core :168-169 without the concat):
     // the slab's planes of the skip connection where they are, the up-sampled half in a mid-channel tensor of its own.
-    const bool two = block_fused(c, Lr00, S + 4) && c->mid % 16 == 0;   // the kernel switches sources between 16-channel chunks
+    const bool two = block_fused(c, Lr00, S + 4) && two_source_width(c);
     Tensor cat = tallocp(c, two ? m : 2 * m, S + 8, Hs, Ws, pad), hq = alloc_hidden(c, 2 * m, S + 6, cat, block_fused(c, Lr00, S + 4));
     Tensor q = tallocp(c, m, S + 4, Hs - 2 * sy, Ws - 2 * sy, pad), hy = alloc_hidden(c, m, S + 2, q, block_fused(c, Lr01, S));
     Tensor y = tallocp(c, c->out_chan, S, Hs - 4 * sy, Ws - 4 * sy, pad);
@@ -2860,7 +2873,185 @@ static int test_layer(nbe_ctx* c, int kind, int crop, int flags, const float* x,
     return rc;
 }
 
+// ---- nbe_test_block: one block of the loaded network through resblock / resblock_part / upblock / downblock -----------
+namespace {
+struct BlockIO {                                                 // host <-> engine tensors of nbe_test_block
+    nbe_ctx* c; std::vector<void*> dev; float scale = 1.f;
+    ~BlockIO() { for (void* p : dev) (void)hipFree(p); }
+    float* stage(size_t n) { void* p = nullptr; if (hipMalloc(&p, n * 4) != hipSuccess) { (void)hipGetLastError(); return nullptr; } dev.push_back(p); return (float*)p; }
+    // dense (C, D, Hi, Wi) host arrays a (channels [0, Ca)) and b (channels [Ca, C), nullable) -> the interior of t, times scale
+    int put(const Tensor& t, int C, int Ca, int Hi, int Wi, const float* a, const float* b, bool tangent) {
+        const int D = t.p.D, H = t.p.H, W = t.p.W, pad = t.pad;
+        std::vector<float> hbuf((size_t)C * D * H * W, 0.f);
+        for (int ch = 0; ch < C; ++ch) {
+            const float* src = ch < Ca ? a + (size_t)ch * D * Hi * Wi : (b ? b + (size_t)(ch - Ca) * D * Hi * Wi : nullptr);
+            if (!src) continue;
+            for (int z = 0; z < D; ++z) for (int yy = 0; yy < Hi; ++yy)
+                memcpy(&hbuf[(((size_t)ch * D + z) * H + yy + pad) * W + pad], src + ((size_t)z * Hi + yy) * Wi, (size_t)Wi * 4);
+        }
+        float* d = stage(hbuf.size());
+        if (!d) return fail("nbe_test_block: out of device memory");
+        HIPCHK(hipMemcpy(d, hbuf.data(), hbuf.size() * 4, hipMemcpyHostToDevice));
+        launch_to_planes(d, C, t.p, tangent, scale, c->prec, c->stream);
+        return 0;
+    }
+    // the (C, D, Hi, Wi) voxels of t from (pad, pad) on -> dense host array, divided by scale
+    int get(const Tensor& t, int C, int Hi, int Wi, float* out, bool tangent) {
+        const int D = t.p.D, H = t.p.H, W = t.p.W, pad = t.pad;
+        const size_t n = (size_t)C * D * H * W;
+        float* d = stage(n);
+        if (!d) return fail("nbe_test_block: out of device memory");
+        launch_from_planes(t.p, tangent, C, d, c->prec, c->stream);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        std::vector<float> hbuf(n);
+        HIPCHK(hipMemcpy(hbuf.data(), d, n * 4, hipMemcpyDeviceToHost));
+        const float inv = 1.0f / scale;
+        for (int ch = 0; ch < C; ++ch) for (int z = 0; z < D; ++z) for (int yy = 0; yy < Hi; ++yy) {
+            const float* s = &hbuf[(((size_t)ch * D + z) * H + yy + pad) * W + pad];
+            float* o = out + (((size_t)ch * D + z) * Hi + yy) * Wi;
+            for (int xx = 0; xx < Wi; ++xx) o[xx] = s[xx] * inv;
+        }
+        return 0;
+    }
+};
+}  // namespace
+
+static int test_block(nbe_ctx* c, const char* block, int pad, int two_source, const float* x, const float* dx, int D, int H, int W,
+                      const float* x2, const float* dx2, float* y, float* dy, float* h, float* dh, float* gauges, int* paths) {
+    if (!c || !block || !x || !y || !gauges || !paths) return fail("null argument");
+    if (require_ready(c)) return 1;
+    if (pad != 0 && pad != 1) return fail("nbe_test_block: pad must be 0 or 1");
+    HIPCHK(hipSetDevice(c->device));
+    const int m = c->mid;
+    const std::string name = block;
+    const bool up = !name.compare(0, 3, "up_"), down = !name.compare(0, 5, "down_"), res = !up && !down;
+    const bool dec = name == "conv_r2" || name == "conv_r1" || name == "conv_r00";
+    const Layer *L0 = find_layer(c, block, "conv_0"), *L1 = find_layer(c, block, "conv_1");
+    if (!L0 || (res && (!L1 || !find_layer(c, block, "skip")))) return fail("nbe_test_block: unknown block %s", block);
+    const bool has_dx = name != "conv_l00", vel = c->vel;
+    if (vel && ((has_dx && !dx) || !dy || (x2 && !dx2) || (h && !dh))) return fail("nbe_test_block: a velocity context needs the tangents");
+    if (x2 && !dec && !up) return fail("nbe_test_block: block %s takes one input", block);
+    if (two_source && !(dec && x2)) return fail("nbe_test_block: the two-source form belongs to the decoder blocks, with x2");
+    const int lim = res ? 5 : 1;
+    if (D < lim || H < (pad && res ? 3 : lim) || W < (pad && res ? 3 : lim)) return fail("nbe_test_block: input (%d, %d, %d) too small for %s", D, H, W, block);
+    if (down && ((D | H | W) & 1)) return fail("nbe_test_block: down-sampling needs even extents");
+    const int cin = L0->cin, cmid = L0->cout, cout = res ? L1->cout : L0->cout;
+    const bool final_act = name != "conv_r01";
+    const int sy = pad ? 0 : 2;
+    if (two_source && !(block_fused(c, L1, D - 4) && two_source_width(c))) return fail("nbe_test_block: block %s does not run the two-source form here", block);
+
+    const float keep_preset = c->preset_absmax;
+    int* const keep_paths = c->paths;
+    c->sst.valid = false;                                        // the arena is reused: a pending brick's tensors are gone
+    // the call's range shift, as a box applies it: max |x| over what goes in (Dz / 6 = 1)
+    size_t n1 = (size_t)(x2 && dec ? m : cin) * D * H * W, n2 = x2 ? (size_t)m * D * H * W * (up ? 8 : 1) : 0;
+    unsigned bits = host_absmax_bits(x, (int64_t)n1);
+    if (x2) bits = std::max(bits, host_absmax_bits(x2, (int64_t)n2));
+    memcpy(&c->preset_absmax, &bits, 4);
+    int rc = prepare_range(c, nullptr, 0, 6.0f);
+    c->preset_absmax = keep_preset;
+    if (rc) return rc;
+
+    BlockIO io; io.c = c; io.scale = c->act_scale;
+    int word = 0;
+    Tensor ty, th;                                               // result and hidden tensor of the real pass
+    int yC = cout, yH = 0, yW = 0;
+    auto body = [&]() -> int {
+        c->arena.reset();
+        if (res) {
+            const bool cat = dec && x2 && !two_source;           // concat on the way in
+            Tensor tx = tallocp(c, two_source ? m : cin, D, H, W, pad), tx2;
+            if (two_source) tx2 = tallocp(c, m, D, H, W, pad);
+            if (tx.off < 0 || (two_source && tx2.off < 0)) return fail("workspace exhausted in nbe_test_block");
+            if (!c->dry) {
+                if (io.put(tx, two_source ? m : cin, cat ? m : cin, H, W, x, cat ? x2 : nullptr, false)) return 1;
+                if (vel && has_dx && io.put(tx, two_source ? m : cin, cat ? m : cin, H, W, dx, cat ? dx2 : nullptr, true)) return 1;
+                if (two_source && (io.put(tx2, m, m, H, W, x2, nullptr, false) || (vel && io.put(tx2, m, m, H, W, dx2, nullptr, true)))) return 1;
+            }
+            fill_halo(c, tx);
+            if (two_source) fill_halo(c, tx2);
+            if (!two_source) {
+                if (resblock(c, block, tx, has_dx, final_act, cout, cmid, &ty, &th)) return 1;
+            } else {
+                // the first-slab call of stream_tail: persistent hidden and result tensors, the up-sampled half as x2
+                th = alloc_hidden(c, cmid, D - 2, tx, block_fused(c, L1, D - 4));
+                ty = tallocp(c, cout, D - 4, H - 2 * sy, W - 2 * sy, pad);
+                if (th.off < 0 || ty.off < 0) return fail("workspace exhausted in nbe_test_block");
+                if (resblock_part(c, block, tx, th, ty, 0, D - 4, 0, D - 2, true, final_act, nullptr, &tx2)) return 1;
+            }
+            yH = H - 2 * sy; yW = W - 2 * sy;
+        } else if (down) {
+            Tensor tx = tallocp(c, m, D, H, W, pad);
+            if (tx.off < 0) return fail("workspace exhausted in nbe_test_block");
+            if (!c->dry && (io.put(tx, m, m, H, W, x, nullptr, false) || (vel && io.put(tx, m, m, H, W, dx, nullptr, true)))) return 1;
+            fill_halo(c, tx);
+            if (!pad) { if (downblock(c, block, tx, &ty)) return 1; }
+            else {                                               // periodic-yx: the interior only (stream_level1)
+                ty = talloc(c, m, D / 2, H / 2, W / 2);
+                if (ty.off < 0) return fail("workspace exhausted in nbe_test_block");
+                if (down_conv(c, *L0, tx, ty, false)) return 1;
+            }
+            yH = H / 2; yW = W / 2;
+        } else {
+            Tensor tx = tallocp(c, m, D, H, W, pad);
+            ty = tallocp(c, x2 ? 2 * m : m, 2 * D, 2 * H, 2 * W, pad);
+            if (tx.off < 0 || ty.off < 0) return fail("workspace exhausted in nbe_test_block");
+            if (!c->dry) {
+                if (io.put(tx, m, m, H, W, x, nullptr, false) || (vel && io.put(tx, m, m, H, W, dx, nullptr, true))) return 1;
+                if (x2 && (io.put(ty, 2 * m, m, 2 * H, 2 * W, x2, nullptr, false) || (vel && io.put(ty, 2 * m, m, 2 * H, 2 * W, dx2, nullptr, true)))) return 1;
+            }
+            fill_halo(c, tx);
+            if (upblock(c, block, tx, ty, 0, x2 ? -1 : 0)) return 1;
+            fill_halo(c, ty);
+            yC = x2 ? 2 * m : m; yH = 2 * H; yW = 2 * W;
+        }
+        return 0;
+    };
+    c->dry = true;
+    rc = body();
+    c->dry = false;
+    if (rc) return rc;
+    const int64_t need = c->arena.high;
+    if (need > c->ws_bytes) {
+        if (c->ws) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->ws)); c->ws = nullptr; c->ws_bytes = 0; }
+        HIPCHK(hipMalloc((void**)&c->ws, need));
+        HIPCHK(hipMemsetAsync(c->ws, 0, need, c->stream));
+        c->ws_bytes = need;
+    }
+    c->paths = &word;
+    rc = body();
+    c->paths = keep_paths;
+    if (!rc) rc = io.get(ty, yC, yH, yW, y, false);
+    if (!rc && vel) rc = io.get(ty, yC, yH, yW, dy, true);
+    if (!rc && res && h) {
+        // a fused block's hidden tensor borrows the input's pitch: its valid voxels start at (0, 0) (pad = 0) / (1, 1)
+        rc = io.get(th, cmid, H - sy, W - sy, h, false);
+        if (!rc && vel) rc = io.get(th, cmid, H - sy, W - sy, dh, true);
+    }
+    c->range_pending = false;                                    // no head ran: nothing to check
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipGetLastError());
+    // the gauges as the device holds them
+    memset(gauges, 0, (size_t)6 * m * 4);
+    if (c->gauge_active && vel) {
+        const float* gin = res ? (has_dx ? L0->alpha : nullptr) : L0->a_in;
+        const float* ghid = res ? L1->alpha : nullptr;
+        const float* gout = res ? L1->gout : L0->gout;
+        if (gin) HIPCHK(hipMemcpy(gauges, gin, (size_t)cin * 4, hipMemcpyDeviceToHost));
+        if (ghid) HIPCHK(hipMemcpy(gauges + 2 * m, ghid, (size_t)cmid * 4, hipMemcpyDeviceToHost));
+        if (gout) HIPCHK(hipMemcpy(gauges + 4 * m, gout, (size_t)cout * 4, hipMemcpyDeviceToHost));
+    }
+    *paths = word;
+    return 0;
+}
+
 extern "C" {
+
+int nbe_test_block(nbe_ctx* c, const char* block, int pad, int two_source, const float* x, const float* dx, int D, int H, int W,
+                   const float* x2, const float* dx2, float* y, float* dy, float* h, float* dh, float* gauges, int* paths) {
+    return test_block(c, block, pad, two_source, x, dx, D, H, W, x2, dx2, y, dy, h, dh, gauges, paths);
+}
 
 int nbe_test_layer(nbe_ctx* c, int kind, int crop, int flags, const float* x, const float* dx, int cin, int D, int H, int W,
                    const float* w, const float* dw, const float* bias, int cout, const float* res, const float* dres,

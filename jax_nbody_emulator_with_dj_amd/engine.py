@@ -386,6 +386,40 @@ class Engine:
                                             _ptr(bias), cout, _ptr(y), _ptr(dy)))
         return y, dy
 
+    PATHS = {"skip_fused": 1, "two_source": 2, "wino_0": 4, "wino_1": 8, "narrow": 16, "up8": 32, "skip_nodx": 64,
+             "two_source_skip": 128}
+
+    def test_block(self, block, x, dx=None, x2=None, dx2=None, pad=0, two_source=False):
+        """One block of the loaded, modulated network through the production schedule functions (nbe_test_block).
+        Tangents go in and come out as the engine stores them (dx + gauge * x).  Returns a dict: y, dy, h, dh (the hidden
+        tensor of a residual block, else None), gauge_in / gauge_hidden / gauge_out (float32, as the device holds them) and
+        paths (the set of PATHS names the launches took)."""
+        x = _f32(x)
+        dx, x2, dx2 = (None if a is None else _f32(a) for a in (dx, x2, dx2))
+        m, vel = self.mid_chan, self.compute_vel
+        _, D, H, W = x.shape
+        res = block.startswith('conv_')
+        if res:
+            cout = self.out_chan if block == 'conv_r01' else m
+            cmid = 2 * m if block in ('conv_r2', 'conv_r1', 'conv_r00') else m
+            sy = 0 if pad else 2
+            y = np.empty((cout, D - 4, H - 2 * sy, W - 2 * sy), np.float32)
+            h = np.empty((cmid, D - 2, H - sy, W - sy), np.float32)
+        elif block.startswith('down_'):
+            y, h = np.empty((m, D // 2, H // 2, W // 2), np.float32), None
+        else:
+            y, h = np.empty((m if x2 is None else 2 * m, 2 * D, 2 * H, 2 * W), np.float32), None
+        dy = np.empty_like(y) if vel else None
+        dh = np.empty_like(h) if (vel and h is not None) else None
+        g = np.zeros((3, 2 * m), np.float32)
+        word = C.c_int(0)
+        check(self._l.nbe_test_block(self._h, block.encode(), int(pad), 1 if two_source else 0, _ptr(x), _ptr(dx), D, H, W,
+                                     _ptr(x2), _ptr(dx2), _ptr(y), _ptr(dy), _ptr(h), _ptr(dh), _ptr(g), C.byref(word)))
+        cin = x.shape[0] if (x2 is None or not res) else 2 * m
+        return {"y": y, "dy": dy, "h": h, "dh": dh, "gauge_in": g[0, :cin], "gauge_hidden": None if h is None else g[1, :h.shape[0]],
+                "gauge_out": g[2, :(m if not res else y.shape[0])],
+                "paths": {k for k, b in self.PATHS.items() if word.value & b}}
+
     def test_modulate(self, weight, style_weight, style_bias, s, first_layer, eps=1e-8, vel=True):
         weight, sw, sb = _f32(weight), _f32(style_weight), _f32(style_bias)
         cout, cin, k = weight.shape[:3]

@@ -1,0 +1,405 @@
+"""GPU parity, block by block: every block of the U-Net through the production schedule functions (nbe_test_block:
+resblock / resblock_part with two sources / upblock / downblock) against the float64 oracle of tests/block_ref.py.
+
+What a box never shows below the whole network is checked here one layer deep: a residual block is compared in two
+stages -- hidden = act(conv_0(x)), then result = [act](conv_1(h_engine) + skip(crop(x))) on the hidden tensor the engine
+returned -- so every figure is held to the PER-LAYER tolerances of tests/layer_checks.py (K <= 27 * 128 + 128), never to
+a whole-network bound.  Tangents cross the hook as the engine stores them (dx + a (.) x); the gauges a come from the
+parameters alone (block_ref.GAUGE_IN / GAUGE_OUT) and the vectors the engine returns are compared with that table.
+Behind an activation the oracle's tangent takes the branch the engine took; the branches may differ from the oracle's
+own only where its pre-activation is zero to within the tensor's max tolerance.  No voxel is excluded.
+
+Shapes are the ones the network produces (block_ref.input_size for inputs of 8 k voxels, k = 13 .. 20, a different k per
+axis), with few planes along z so that a float64 case stays around a second."""
+
+import os
+import time
+import zlib
+
+import numpy as np
+import pytest
+
+import block_ref as B
+from conftest import rel_l2, max_over_rms
+from layer_checks import (RTOL_L2, RTOL_MAX, RTOL_L2_F16, RTOL_MAX_F16, RTOL_L2_F16W, RTOL_MAX_F16W, _chk, _chk_f16w, _h)
+from oracle import layers as L, params as P
+
+pytestmark = pytest.mark.gpu
+
+OM, DZ = 0.27, 0.7731811501855036
+MIDS = (8, 16, 24, 32, 64)
+PRECS = ("f32", "f16x3", "f16")
+RES = tuple(b for b in B.BLOCKS if b.startswith('conv_'))
+TOL = {"f32": (RTOL_L2, RTOL_MAX), "f16": (RTOL_L2_F16, RTOL_MAX_F16), "f16w": (RTOL_L2_F16W, RTOL_MAX_F16W)}
+
+_PARAMS = {}
+WORST = {}                                    # (stage, arithmetic, tolerance class) -> [rel-L2, max/RMS]
+T0 = [None]
+
+
+def params_of(mid):
+    if mid not in _PARAMS:
+        _PARAMS[mid] = P.synthetic_params(seed=100 + mid, mid_chan=mid)
+    return _PARAMS[mid]
+
+
+def s64():
+    return L.style_vector(np.float32(OM), np.float32(DZ))       # the engine's entry points take float32 scalars
+
+
+def _gauge_deviation():
+    """worst |alpha evaluated in float32 - alpha in float64| over every layer of the tested trees: the float32 formula is
+    the core's own, s = ((Om - 0.3) * 5, Dz - 1) in float32 (style_nbody_emulator_vel_core.py:126-128)"""
+    s32 = np.array([(np.float32(OM) - np.float32(0.3)) * np.float32(5.0), np.float32(DZ) - np.float32(1.0)], np.float32)
+    worst = 0.0
+    for mid in MIDS:
+        for bp in params_of(mid)['params'].values():
+            for lp in bp.values():
+                worst = max(worst, float(np.abs(B.alpha(lp, s32).astype(np.float64) - B.alpha(lp, s64())).max()))
+    return worst
+
+
+GAUGE_DEV = _gauge_deviation()
+
+
+@pytest.fixture(scope="module")
+def engines(engine_factory):
+    made = {}
+
+    def get(mid, prec, vel, gauge=True):
+        key = (mid, prec, vel, gauge)
+        if key not in made:
+            keep = os.environ.get("NBE_GAUGE")
+            if not gauge:
+                os.environ["NBE_GAUGE"] = "0"                    # read when the weights are loaded
+            try:
+                e = engine_factory(mid_chan=mid, precision=prec, compute_vel=vel)
+                e.load_params(params_of(mid), False)
+                e.set_cosmology(OM, DZ)
+            finally:
+                if not gauge:
+                    os.environ.pop("NBE_GAUGE")
+                    if keep is not None:
+                        os.environ["NBE_GAUGE"] = keep
+            assert bool(e.query("gauge_active")) == (vel and gauge)
+            made[key] = e
+        return made[key]
+    if T0[0] is None:
+        T0[0] = time.time()
+    return get
+
+
+# ---- shapes -------------------------------------------------------------------------------------------------------------
+
+def shapes(block, full=True):
+    """[(D, H, W, pad)]: y and x are sizes the network hands this block for inputs of 8 k voxels, a different k in 13 .. 20
+    per axis and case (seeded by the block's name); z is small.  Residual blocks: an odd and an even number of result
+    planes (D - 4), then the smallest legal y / x (k = 13) on the smallest z; level-0 blocks: the first case is wider than
+    one wave of workgroups (256 voxels per tile, 256 CUs) where the block's sizes allow it, and one periodic-yx case."""
+    rng = np.random.default_rng(zlib.crc32(block.encode()))
+    ks = [int(k) for k in rng.permutation(np.arange(13, 21))]
+    n = lambda k: B.input_size(block, k)
+    lvl0 = B.LEVEL[block] == 0
+    if block.startswith('down'):
+        out = [(6, n(ks[0]), n(ks[1]), 0), (4, n(ks[2]), n(ks[3]), 0), (2, n(13), n(13), 0)]
+        per = (4, 48, 56, 1)
+    elif block.startswith('up'):
+        out = [(3, n(ks[0]), n(ks[1]), 0), (4, n(ks[2]), n(ks[3]), 0), (1, n(13), n(13), 0)]
+        per = (3, 24, 32, 1)
+    else:
+        big = sorted(ks[:2])
+        if lvl0:
+            big = [max(big[0], 15), max(big[1], 16)]
+        zmin = n(13) if B.LEVEL[block] == 3 else 5
+        out = [(7, n(big[0]), n(big[1]), 0), (8, n(ks[2]), n(ks[3]), 0), (zmin, n(13), n(13), 0)]
+        per = (6, 48, 56, 1)
+    if not full:
+        out = out[:2]
+    return out + ([per] if lvl0 else [])
+
+
+# ---- what the engine is expected to run ---------------------------------------------------------------------------------
+
+def expect_fused(block, mid, prec, vel, gauge, nres, wino_on):
+    """block_fused() of the engine, restated from DESIGN.md section 4: f16x3 with velocity fuses every gauged block; the float16
+    model and displacement-only f16x3 fuse only inside the Winograd-z kernel (an even number of result planes, NBE_WINO not
+    0), float16 only where conv_1 and the skip are made of whole 32-channel stages and the skip has a tangent input;
+    float32 never."""
+    cin, cmid, _ = B.channels(block, mid)
+    if prec == "f16x3" and vel:
+        return gauge
+    if prec == "f16x3":
+        return wino_on and nres % 2 == 0
+    if prec == "f16" and vel and gauge:
+        pad16 = lambda c: -(-c // 16) * 16
+        return (wino_on and nres % 2 == 0 and block != 'conv_l00' and pad16(cmid) % 32 == 0 and pad16(cin) % 32 == 0)
+    return False
+
+
+# ---- checks -------------------------------------------------------------------------------------------------------------
+
+def _note(stage, arith, cls, e2, em):
+    w = WORST.setdefault((stage, arith, cls), [0.0, 0.0])
+    w[0], w[1] = max(w[0], e2), max(w[1], em)
+
+
+def check(got, want, what, cls, stage, arith):
+    e2, em = rel_l2(got, want), max_over_rms(got, want)
+    print("    %-34s rel-L2 %.2e (<= %.0e)  max/RMS %.2e (<= %.0e)  [%s]" % ((what, e2, TOL[cls][0], em, TOL[cls][1], cls)))
+    _note(stage, arith, cls, e2, em)
+    if cls == "f16w":
+        _chk_f16w(got, want, what)
+    else:
+        _chk(got, want, what, half=cls == "f16")
+
+
+def engine_result(S, y_eng, dy_eng, half, what):
+    """(y, dy~, branch): the stage's result with the tangent on the branches the engine took, engine_primal > 0.  The float16
+    engine decides on its float32 accumulator and then stores float16: a positive pre-activation below half the smallest
+    float16 number is stored as 0 behind the identity branch, so where the stored value is exactly 0 it does not tell the
+    branch -- there the branch is read from the engine's tangent (the nearer of the two)."""
+    br = y_eng > 0
+    y_o, d_o = S.result(branch=br)
+    if half and S.vel and S.act and (y_eng == 0).any():
+        z = y_eng == 0
+        _, d_alt = S.result(branch=br | z)
+        pick = z & (np.abs(dy_eng - d_alt) < np.abs(dy_eng - d_o))
+        print("    %-34s %d values stored as 0, %d of them behind the identity branch" % (what, int(z.sum()), int(pick.sum())))
+        d_o, br = np.where(pick, d_alt, d_o), br | pick
+    return y_o, d_o, br
+
+
+def check_branches(branch, pre, what, cls):
+    """the engine's branches differ from the oracle's own only where the oracle's pre-activation is zero to within the max
+    tolerance of the tensor, in units of its RMS"""
+    diff = branch != (pre > 0)
+    n = int(diff.sum())
+    print("    %-34s %d of %d branches differ from the oracle's own" % (what, n, diff.size))
+    if n:
+        worst = float(np.abs(pre[diff]).max()) / float(np.sqrt(np.mean(pre ** 2)))
+        assert worst <= TOL[cls][1], "%s: a branch differs where the pre-activation is %.2e RMS from zero" % (what, worst)
+
+
+def check_gauges(r, g, what):
+    for name, got, want in zip(("input", "hidden", "output"), (r["gauge_in"], r["gauge_hidden"], r["gauge_out"]), g):
+        if want is None:
+            continue
+        dev = float(np.abs(got.astype(np.float64) - want).max())
+        assert got.shape == want.shape and dev <= 4 * GAUGE_DEV, \
+            "%s: %s gauge deviates from the float64 table by %.2e (float32 evaluation: %.2e)" % (what, name, dev, GAUGE_DEV)
+    return max(float(np.abs(got.astype(np.float64) - want).max()) for got, want in
+               zip((r["gauge_in"], r["gauge_hidden"], r["gauge_out"]), g) if want is not None)
+
+
+def make_input(block, mid, prec, vel, shape, g_in):
+    """x and the stored input tangent dx~ = dx + g_in (.) x as float32, rounded as the engine stores them"""
+    D, H, W, pad = shape
+    cin = B.channels(block, mid)[0]
+    rng = np.random.default_rng(zlib.crc32(("%s %d %d %d %d" % (block, mid, D, H, W)).encode()))
+    half = prec == "f16"
+    x = _h(rng.standard_normal((cin, D, H, W)).astype(np.float32), half)
+    dxs = None
+    if vel and block != 'conv_l00':
+        dx = rng.standard_normal((cin, D, H, W))
+        dxs = _h((dx + g_in[:, None, None, None] * x).astype(np.float32), half)
+    return x, dxs
+
+
+def run_case(e, block, mid, prec, vel, shape, gauge=True, wino_on=True, forms=("cat", "two")):
+    """one block on one shape: stages, branches, gauges, paths; returns {form: engine result}"""
+    D, H, W, pad = shape
+    p, s = params_of(mid), s64()
+    half = prec == "f16"
+    table = B.gauges(p, s, block, mid)
+    g = table if (gauge and vel) else tuple(None if t is None else np.zeros_like(t) for t in table)
+    x, dxs = make_input(block, mid, prec, vel, shape, g[0])
+    x64, dxs64 = x.astype(np.float64), None if dxs is None else dxs.astype(np.float64)
+    arith = prec + ("" if vel else " disp")
+    res = block in RES
+    out = {}
+    print("  %s mid %d %s %s (D, H, W) = (%d, %d, %d) pad %d%s%s" % (block, mid, prec, "vel" if vel else "disp", D, H, W, pad,
+                                                                "" if gauge else " NBE_GAUGE=0", "" if wino_on else " NBE_WINO=0"))
+    if not res:
+        up = block.startswith('up')
+        S = B.stage1(p, s, block, x64, dxs64, mid, vel=vel, half=half, g=g, gauged=gauge)
+        runs = [("own", None, None)]
+        if up:                                                   # into the second half of a concat tensor: the skip half is a neighbour
+            rng = np.random.default_rng(7)
+            sk = (np.round(rng.standard_normal((mid, 2 * D, 2 * H, 2 * W)) * 64).clip(-256, 256) / 64).astype(np.float32)
+            dsk = (np.round(rng.standard_normal(sk.shape) * 64).clip(-256, 256) / 64).astype(np.float32)
+            runs.append(("cat", sk, dsk if vel else None))
+        for form, sk, dsk in runs:
+            if pad and not up and form != "own":
+                continue
+            r = e.test_block(block, x, dx=dxs, x2=sk, dx2=dsk, pad=pad)
+            y, dy = r["y"], r["dy"]
+            if sk is not None:
+                assert np.array_equal(y[:mid], sk) and (not vel or np.array_equal(dy[:mid], dsk)), "%s: the skip half of the concat tensor changed" % block
+                y, dy = y[mid:], (None if dy is None else dy[mid:])
+            cls = "f16" if half else "f32"
+            y_o, dys_o, br = engine_result(S, y, dy, half, "%s (%s)" % (block, form))
+            check(y, y_o, "%s (%s) primal" % (block, form), cls, "resample", arith)
+            if vel:
+                check(dy, dys_o, "%s (%s) tangent" % (block, form), cls, "resample", arith)
+                check_branches(br, S.p, "%s (%s)" % (block, form), cls)
+                print("    gauges: worst deviation from the float64 table %.2e (float32 evaluation %.2e)" % (check_gauges(r, g, block), GAUGE_DEV))
+            assert ("up8" in r["paths"]) == (up and prec != "f32"), r["paths"]
+            assert not r["paths"] & {"skip_fused", "two_source", "narrow"}, r["paths"]
+            out[form] = r
+        return out
+
+    nres = D - 4
+    fused = expect_fused(block, mid, prec, vel, gauge, nres, wino_on)
+    dec = block in B.DECODERS
+    todo = [("cat", False)]
+    if dec and "two" in forms and mid % (32 if half else 16) == 0 and fused:
+        todo.append(("two", True))
+    S1 = B.stage1(p, s, block, x64, dxs64, mid, pad=pad, vel=vel, half=half, g=g, gauged=gauge)
+    for form, two in todo:
+        if two:
+            r = e.test_block(block, x[:mid], dx=None if dxs is None else dxs[:mid], x2=x[mid:], dx2=None if dxs is None else dxs[mid:],
+                             pad=pad, two_source=True)
+        else:
+            r = e.test_block(block, x, dx=dxs, pad=pad)
+        out[form] = r
+        paths = r["paths"]
+        # -- paths
+        assert ("skip_fused" in paths) == fused, (block, paths, fused)
+        assert ("skip_nodx" in paths) == (fused and block == 'conv_l00'), (block, paths)
+        assert ("two_source" in paths) == two and ("two_source_skip" in paths) == two, (block, paths, two)
+        assert ("narrow" in paths) == (block == 'conv_r01' and prec == "f16x3" and vel and gauge), (block, paths)
+        assert "up8" not in paths
+        if prec == "f32" or not wino_on or (vel and not gauge):
+            assert not paths & {"wino_0", "wino_1"}, paths
+        if prec == "f16x3" and vel and gauge and wino_on:
+            assert ("wino_0" in paths) == (D % 2 == 0 and block != 'conv_l00'), (block, D, paths)
+            assert ("wino_1" in paths) == (D % 2 == 0 and block != 'conv_r01'), (block, D, paths)
+        if fused and prec == "f16":
+            assert "wino_1" in paths, paths                      # the float16 model's fused skip lives in the Winograd-z kernel
+        # -- stage 1: the hidden tensor
+        c1 = "f16w" if (half and "wino_0" in paths) else "f16" if half else "f32"
+        h_o, dhs_o, br = engine_result(S1, r["h"], r["dh"], half, "%s (%s) hidden" % (block, form))
+        check(r["h"], h_o, "%s (%s) hidden primal" % (block, form), c1, "conv_0", arith)
+        if vel:
+            check(r["dh"], dhs_o, "%s (%s) hidden tangent" % (block, form), c1, "conv_0", arith)
+            check_branches(br, S1.p, "%s (%s) hidden" % (block, form), c1)
+        # -- stage 2: conv_1 + skip on the engine's hidden tensor
+        c2 = "f16w" if (half and "wino_1" in paths) else "f16" if half else "f32"
+        st2 = "conv_1 + skip, " + ("fused" if fused else "unfused")
+        h64, dh64 = r["h"].astype(np.float64), (r["dh"].astype(np.float64) if vel else None)
+        S2 = B.stage2(p, s, block, x64, dxs64, h64, dh64, mid, pad=pad, vel=vel, half=half, g=g, gauged=gauge, fused=fused)
+        act = block != 'conv_r01'
+        y_o, dys_o, br = engine_result(S2, r["y"], r["dy"], half, "%s (%s) result" % (block, form))
+        check(r["y"], y_o, "%s (%s) result primal" % (block, form), c2, st2, arith)
+        if vel:
+            check(r["dy"], dys_o, "%s (%s) result tangent" % (block, form), c2, st2, arith)
+            if act:
+                check_branches(br, S2.p, "%s (%s) result" % (block, form), c2)
+            print("    gauges: worst deviation from the float64 table %.2e (float32 evaluation %.2e)" % (check_gauges(r, g, block), GAUGE_DEV))
+    if "two" in out:
+        # the two forms read the same numbers: they agree to the stage tolerance, and bit for bit on the direct f16x3 kernel
+        a, b = out["two"], out["cat"]
+        c2 = "f16w" if (half and "wino_1" in a["paths"]) else "f16" if half else "f32"
+        for k in ("h", "dh", "y", "dy"):
+            if a[k] is not None:
+                e2, em = rel_l2(a[k], b[k]), max_over_rms(a[k], b[k])
+                print("    two sources vs concat, %-2s          rel-L2 %.2e  max/RMS %.2e" % (k, e2, em))
+                assert e2 <= TOL[c2][0] and em <= TOL[c2][1], (block, k, e2, em)
+                if prec == "f16x3" and not wino_on:
+                    assert np.array_equal(a[k], b[k]), "%s: two sources and the concat tensor differ in %s on the direct kernel" % (block, k)
+    return out
+
+
+# ---- the matrix ---------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("vel", [True, False], ids=["vel", "disp"])
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("mid", MIDS)
+@pytest.mark.parametrize("block", B.BLOCKS)
+def test_block(engines, block, mid, prec, vel):
+    e = engines(mid, prec, vel)
+    with L.backend('torch'):
+        for shape in shapes(block, full=vel):
+            run_case(e, block, mid, prec, vel, shape)
+
+
+@pytest.mark.parametrize("prec,vel", [("f16x3", True), ("f16", True), ("f16x3", False)])
+@pytest.mark.parametrize("mid", [16, 64])
+@pytest.mark.parametrize("block", RES)
+def test_block_direct_kernels(engines, block, mid, prec, vel, monkeypatch):
+    """NBE_WINO=0: the direct kernels; the float16 model and displacement-only f16x3 run their blocks unfused"""
+    monkeypatch.setenv("NBE_WINO", "0")
+    e = engines(mid, prec, vel)
+    with L.backend('torch'):
+        for shape in shapes(block, full=False)[:2]:
+            run_case(e, block, mid, prec, vel, shape, wino_on=False)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("mid", [16, 64])
+@pytest.mark.parametrize("block", B.BLOCKS)
+def test_block_without_gauge(engines, block, mid, prec):
+    """NBE_GAUGE=0 at load time: plain tangents, three products per layer, no fused skip; every gauge vector is zero"""
+    e = engines(mid, prec, True, gauge=False)
+    with L.backend('torch'):
+        for shape in shapes(block, full=False)[:2]:
+            for r in run_case(e, block, mid, prec, True, shape, gauge=False).values():
+                assert not r["gauge_in"].any() and not r["gauge_out"].any() and (r["gauge_hidden"] is None or not r["gauge_hidden"].any())
+
+
+@pytest.mark.parametrize("mid,prec", [(8, "f16x3"), (24, "f16x3"), (16, "f16"), (24, "f16")])
+def test_two_source_form_needs_whole_chunks_per_source(engines, mid, prec):
+    """mid 8 and 24: a 16-channel chunk would straddle the two tensors -- the schedule never asks for two sources there.
+    The float16 model's fused kernel reads 32-channel chunks: mid 16, where its decoder blocks fuse, is such a width too
+    (the z-slab schedule used to ask for two sources there and found no kernel)."""
+    from jax_nbody_emulator_with_dj_amd.engine import NBEError
+    e = engines(mid, prec, True)
+    x = np.zeros((mid, 8, 10, 12), np.float32)
+    with pytest.raises(NBEError, match="two-source"):
+        e.test_block("conv_r00", x, dx=x, x2=x, dx2=x, two_source=True)
+
+
+def test_slab_schedule_of_the_float16_model_at_mid_16(engines):
+    """Regression: at mid 16 the float16 model fuses its decoder blocks (32-channel stages of conv_r00/conv_1), and the z-slab
+    schedule then asked conv_r00 for a two-source read at a 16-channel boundary, which its kernel does not have: the box
+    failed with "no kernel for layer conv_r00/conv_0".  The slab schedule must run and give the whole-tensor schedule's
+    fields: both are float16 evaluations of the same network that differ in how launches pair their planes, so they agree
+    within twice the float16 model's whole-network bounds (test_gpu_model.py::test_float16_mode: 2e-3 / 4e-2)."""
+    e = engines(16, "f16", True)
+    size = (32, 32, 32)
+    box = np.random.default_rng(12).standard_normal((3,) + size).astype(np.float32)
+    out = {}
+    try:
+        for S in (0, 16):
+            e.set_slab(S)
+            d, v = e.process_box(box, size, (1, 1, 1), ((48, 48),) * 3, 0.7, 0.5)
+            assert int(e.query("slab")) == S
+            out[S] = (np.array(d), np.array(v))
+    finally:
+        e.set_slab(-1)
+    ed, ev = rel_l2(out[16][0], out[0][0]), rel_l2(out[16][1], out[0][1])
+    print("  slab 16 vs whole tensors, mid 16 float16: disp rel-L2 %.2e, vel rel-L2 %.2e" % (ed, ev))
+    assert ed <= 2 * 2e-3 and ev <= 2 * 4e-2
+
+
+def test_hook_refuses_what_it_cannot_run(engines):
+    from jax_nbody_emulator_with_dj_amd.engine import NBEError
+    e = engines(8, "f16x3", True)
+    x = np.zeros((8, 8, 10, 12), np.float32)
+    for args in (dict(block="conv_x9"), dict(block="conv_l1", pad=2), dict(block="down_l1", x=x[:, :7]), dict(block="conv_l1", x=x[:, :4])):
+        a = dict(block="conv_l1", x=x, pad=0)
+        a.update(args)
+        with pytest.raises(NBEError):
+            e.test_block(a["block"], a["x"], dx=a["x"], pad=a["pad"])
+    r = e.test_block("conv_l1", x, dx=x)                          # and the context is as usable as before
+    assert np.all(np.isfinite(r["y"]))
+
+
+def test_zz_worst_cases():
+    """prints the worst figure per stage, arithmetic and tolerance class of this run (DESIGN.md section 2c records them)"""
+    print("\n  stage | arithmetic | class | worst rel-L2 (bound) | worst max/RMS (bound)")
+    for (stage, arith, cls), (e2, em) in sorted(WORST.items()):
+        print("  %-26s | %-10s | %-4s | %.2e (%.0e) | %.2e (%.0e)" % (stage, arith, cls, e2, TOL[cls][0], em, TOL[cls][1]))
+    print("  gauge vectors: float32 evaluation deviates from float64 by %.2e; bound 4x" % GAUGE_DEV)
+    if T0[0] is not None:
+        print("  wall time of this module so far: %.0f s" % (time.time() - T0[0]))
