@@ -288,6 +288,65 @@ int nbe_field_moments(const void* field, int64_t n, void* moments, void* stream)
 int nbe_minkowski_counts(const void* field, int64_t n, const void* thresholds, int nthresholds, const void* moments,
                          void* counts, void* stream);
 
+/* Reduced bispectrum Q(theta) of an n^3 float32 field by the FFT estimator (Scoccimarro 2000),
+ * replacing Pylians' Bk_library.Bk as the reference calls it (scripts/utils.py:1314-1399).  Definition.  Let kappa = k / k_F,
+ * k_F = 2 pi / L, let m in Z^3 run over the wave vectors of the full complex grid (each component in (-n/2, n/2]) and let
+ * delta_m be the unnormalised forward FFT.
+ *   kappa3(theta) = sqrt((kappa2 sin theta)^2 + (kappa2 cos theta + kappa1)^2): theta is the angle between the vectors k1
+ *     and k2, so theta = 0 gives kappa1 + kappa2.
+ *   Shell S(kappa) = { m != 0 : lo^2 <= |m|^2 < hi^2 }, lo = max(kappa - dk/2, 0), hi = kappa + dk/2; the squares are taken
+ *     in float64 and compared with the integer |m|^2.  The DC mode belongs to no shell.
+ *   N_tri(theta) = #{ (m1, m2, m3) : m1 in S(kappa1), m2 in S(kappa2), m3 in S(kappa3(theta)), m1 + m2 + m3 = 0 }.
+ *   B(theta) = L^6 / n^9 * sum over those triangles of Re(delta_m1 delta_m2 delta_m3) / N_tri(theta).
+ *   P_i = L^3 / n^6 * mean of |delta_m|^2 over shell i;  Q(theta) = B / (P1 P2 + P2 P3(theta) + P3(theta) P1).
+ * Closure is exact, not modulo n: the caller keeps 2 (kappa1 + kappa2) + 1.5 dk < n.  With F_S = irfftn(delta I_S) the sum
+ * over the voxels of F1 F2 F3 is n^-6 times the sum over the triangles; the transforms are the caller's (rocFFT). */
+#define NBE_BK_MIN_N 4
+#define NBE_BK_MAX_N 2048
+#define NBE_BK_MAX_SHELLS 258        /* shell 1, shell 2 and up to 256 third shells */
+#define NBE_BK_MAX_EDGES 512
+#define NBE_BK_PARTIALS 2048
+/* replaces the shell selection of Bk_library.Bk (scripts/utils.py:1314-1399): one pass over the rfft `spectrum`
+ * (n, n, n/2+1) complex64 for nshells (1 .. NBE_BK_MAX_SHELLS) shells.  shells = nshells x 4 int64 ON THE DEVICE:
+ * lo2 = max(ceil(lo^2), 1), hi2 = ceil(hi^2), koff, kexp.  filtered (or NULL) = nshells spectra of the same shape: shell s
+ * receives delta_m where lo2 <= |m|^2 < hi2 and 0 elsewhere (Hermitian, as the bounds are even in m).  binmax = nshells
+ * uint32 and sums = nshells x 3 int64, both zeroed by the caller, or both NULL.  Out, as nbe_power_spectrum: binmax[s] =
+ * float bits of the shell's largest |delta_m|^2 = m 2^e, m in [0.5, 1); sums[s] = { modes of the full grid, sum of
+ * (|m| - koff) in units of 2^-kexp, sum of |delta_m|^2 in units of 2^(e - 32) }.  Integer sums: reproducible bit for bit.
+ * NBE_BK_MIN_N <= n <= NBE_BK_MAX_N. */
+int nbe_shell_filter(const void* spectrum, int64_t n, const void* shells, int nshells, void* filtered, void* binmax,
+                     void* sums, void* stream);
+/* replaces the sum over the voxels of the three filtered fields in Bk_library.Bk (scripts/utils.py:1314-1399): out[j] =
+ * sum over the n^3 voxels of f1 f2 f3[j] in float64, j < nfields (1 .. NBE_BK_MAX_SHELLS); f3 = nfields contiguous float32
+ * fields.  The voxels are partitioned by n alone and every level is added in a fixed order, with no float atomics: out[j]
+ * is the same bits on every call, whichever other fields share the call.  partials = nfields x NBE_BK_PARTIALS float64 of
+ * scratch, out = nfields float64. */
+int nbe_triple_sums(const void* f1, const void* f2, const void* f3, int nfields, int64_t n, void* partials, void* out,
+                    void* stream);
+/* replaces the triangle counts of Bk_library.Bk (scripts/utils.py:1314-1399), which it takes from transforms of the shell
+ * indicators: here every pair of modes1 x modes2 (count x 4 int32: m_x, m_y, m_z, 0) closes with m3 = -(m1 + m2), and
+ * |m3|^2 is binned by upper_bound over `edges`, nedges (2 .. NBE_BK_MAX_EDGES) int32 sorted ascending and distinct.
+ * hist = nedges + 1 int64, zeroed by the caller: hist[b] = pairs with b = #{edges <= |m3|^2}; a shell [edges[a], edges[c])
+ * holds the sum of hist[a+1 .. c].  Integers: exact at every mesh size. */
+int nbe_triangle_counts(const void* modes1, int64_t count1, const void* modes2, int64_t count2, const void* edges,
+                        int nedges, void* hist, void* stream);
+
+/* One-point statistics of `count` float32 values (any shape; 1 <= count <= 2^40). */
+#define NBE_MOMENTS4_WORDS 6148
+#define NBE_PDF_MAX_BINS 4096
+#define NBE_ONEPOINT_MAX_VOXELS (1LL << 40)
+/* replaces _field_moments (scripts/utils.py:1164-1187): moments = NBE_MOMENTS4_WORDS float64: out [0] the mean, [1] the
+ * population standard deviation, [2] and [3] the third and fourth central moments (means of (x - mean)^3 and ^4); the
+ * rest is scratch.  Float64, two passes over the partition of nbe_field_moments, reduced in a fixed order: bitwise
+ * reproducible. */
+int nbe_field_moments4(const void* field, int64_t count, void* moments, void* stream);
+/* replaces np.histogram(x[isfinite(x)], bins=np.linspace(lo, hi, nbins + 1)) (scripts/utils.py:1248-1274): edges = nbins + 1
+ * float64 ascending with edges[0] = lo and edges[nbins] = hi, 2 <= nbins <= NBE_PDF_MAX_BINS.  A value x, widened to
+ * float64, falls into bin #{edges <= x} - 1, and x = hi into the last bin (NumPy's rule).  counts = nbins + 2 int64, zeroed
+ * by the caller: the bins, then the finite values outside [lo, hi], then the non-finite ones. */
+int nbe_field_histogram(const void* field, int64_t count, double lo, double hi, const void* edges, int nbins,
+                        void* counts, void* stream);
+
 /* ---- test / measurement hooks (not part of the reference surface) ------------------------------ */
 
 /* One layer through the production kernels, host NCDHW in / out.  kind: 0 conv3 (VALID 3x3x3),

@@ -1,7 +1,8 @@
 // Density fields from emulated displacements (include/nbe.h, "Density"): mass assignment of the displaced lattice onto
-// a periodic mesh (NGP / CIC / TSC / PCS), the inverse assignment window on the rfft of the mesh, and shell-binned power
-// spectra.  Replaces the DISCO-DJ / Pylians step of the reference's pipeline (scripts/core.py:447-458,
-// scripts/utils.py:136-148, :1083-1085).  No context: these entry points need no weights.
+// a periodic mesh (NGP / CIC / TSC / PCS), the inverse assignment window on the rfft of the mesh, shell-binned power
+// spectra, Minkowski functionals, the shell filter and triple sums of the bispectrum estimator and one-point statistics.
+// Replaces the DISCO-DJ / Pylians step of the reference's pipeline (scripts/core.py:447-458, scripts/utils.py:136-148,
+// :652-763, :1083-1085, :1164-1187, :1248-1274, :1314-1399).  No context: these entry points need no weights.
 //
 // Paint.  One workgroup per Lagrangian tile of 8^3 particles.  Pass 1 reads the tile's
 // displacements once and bounds its Eulerian footprint (the nodes its particles touch, from the tile's own positions).
@@ -531,6 +532,293 @@ __global__ __launch_bounds__(kMfThreads) void minkowski_counts_kernel(MfArgs A) 
     if (tid == 0 && nonfinite) atomicAdd(&A.counts[NB], (unsigned long long)nonfinite);
 }
 
+// ---- Bispectrum and one-point statistics ----------------------------------------------------
+// Shell filter: one pass over the half spectrum of an n^3 mesh serves a batch of S spherical shells.  Every mode forms its
+// integer |m|^2 once and tests it against the batch's [lo2, hi2) bounds (integers, prepared by the host); shell s receives
+// the mode or 0 in its own filtered spectrum.  The bounds are symmetric under m -> -m, so the filtered half spectra stay
+// Hermitian.  The per-shell sums use the integer scheme of nbe_power_spectrum: a first pass finds the largest |delta|^2
+// of each shell, the second adds the weights, |m| - koff in units of 2^-kexp and |delta|^2 in units of 2^(e - 32).
+constexpr int kBkThreads = 256;
+
+struct ShellArgs {
+    const float2* spec;
+    long long n;
+    const long long* par;          // device, S x 4: lo2, hi2, koff, kexp
+    int S;
+    float2* out;                   // S filtered half spectra, or NULL
+    unsigned* binmax;              // S, or NULL (no sums)
+    unsigned long long* sums;      // S x 3: weight, k, power
+};
+
+// |m|^2 of mode i of the half spectrum and its weight in the full grid
+__device__ inline long long mode_q(long long i, long long n, int* w) {
+    const long long h2 = n / 2 + 1;
+    const long long i2 = i % h2, r = i / h2, i1 = r % n, i0 = r / n;
+    const long long f0 = freq(i0, n), f1 = freq(i1, n);
+    *w = (i2 == 0 || (n % 2 == 0 && i2 == n / 2)) ? 1 : 2;
+    return f0 * f0 + f1 * f1 + i2 * i2;
+}
+
+__global__ __launch_bounds__(kBkThreads) void shell_max_kernel(ShellArgs A) {
+    __shared__ long long lo2[NBE_BK_MAX_SHELLS], hi2[NBE_BK_MAX_SHELLS];
+    __shared__ unsigned smax[NBE_BK_MAX_SHELLS];
+    __shared__ long long qmin, qmax;
+    const int S = A.S;
+    for (int s = threadIdx.x; s < S; s += kBkThreads) { lo2[s] = A.par[4 * s]; hi2[s] = A.par[4 * s + 1]; smax[s] = 0u; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long a = LLONG_MAX, b = 0;
+        for (int s = 0; s < S; ++s) { a = lo2[s] < a ? lo2[s] : a; b = hi2[s] > b ? hi2[s] : b; }
+        qmin = a; qmax = b;
+    }
+    __syncthreads();
+    const long long total = A.n * A.n * (A.n / 2 + 1), q0 = qmin, q1 = qmax;
+    for (long long i = blockIdx.x * (long long)kBkThreads + threadIdx.x; i < total; i += (long long)gridDim.x * kBkThreads) {
+        int w;
+        const long long q = mode_q(i, A.n, &w);
+        if (q < q0 || q >= q1) continue;
+        const float2 v = A.spec[i];
+        const unsigned bits = __float_as_uint((float)fabs((double)v.x * v.x + (double)v.y * v.y));
+        for (int s = 0; s < S; ++s)
+            if (q >= lo2[s] && q < hi2[s]) atomicMax(&smax[s], bits);
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < S; s += kBkThreads)
+        if (smax[s]) atomicMax(&A.binmax[s], smax[s]);
+}
+
+__global__ __launch_bounds__(kBkThreads) void shell_filter_kernel(ShellArgs A) {
+    __shared__ long long lo2[NBE_BK_MAX_SHELLS], hi2[NBE_BK_MAX_SHELLS];
+    __shared__ double koff[NBE_BK_MAX_SHELLS];
+    __shared__ int kexp[NBE_BK_MAX_SHELLS], pexp[NBE_BK_MAX_SHELLS];
+    __shared__ unsigned long long ssum[3 * NBE_BK_MAX_SHELLS];
+    const int S = A.S;
+    const bool sums = A.binmax != nullptr;
+    for (int s = threadIdx.x; s < S; s += kBkThreads) {
+        lo2[s] = A.par[4 * s]; hi2[s] = A.par[4 * s + 1];
+        koff[s] = (double)A.par[4 * s + 2]; kexp[s] = (int)A.par[4 * s + 3];
+        ssum[3 * s] = ssum[3 * s + 1] = ssum[3 * s + 2] = 0ull;
+        pexp[s] = INT_MIN;
+        if (sums) {
+            const float m = __uint_as_float(A.binmax[s]);
+            int e = 0;
+            if (isfinite(m) && m > 0.0f) frexp((double)m, &e);
+            pexp[s] = isfinite(m) ? 32 - e : INT_MIN;      // INT_MIN: non-finite shell, reported by the caller
+        }
+    }
+    __syncthreads();
+    const long long total = A.n * A.n * (A.n / 2 + 1);
+    for (long long i = blockIdx.x * (long long)kBkThreads + threadIdx.x; i < total; i += (long long)gridDim.x * kBkThreads) {
+        int w;
+        const long long q = mode_q(i, A.n, &w);
+        const float2 v = A.spec[i];
+        const float2 zero = make_float2(0.0f, 0.0f);
+        for (int s = 0; s < S; ++s) {
+            const bool in = q >= lo2[s] && q < hi2[s];
+            if (A.out) A.out[(long long)s * total + i] = in ? v : zero;
+            if (in && sums) {
+                const double p = (double)v.x * v.x + (double)v.y * v.y;
+                const long long kq = (long long)rint(ldexp(sqrt((double)q) - koff[s], kexp[s]));
+                const long long pq = pexp[s] == INT_MIN ? 0 : (long long)rint(ldexp(p, pexp[s]));
+                atomicAdd(&ssum[3 * s], (unsigned long long)w);
+                atomicAdd(&ssum[3 * s + 1], (unsigned long long)(w * kq));
+                atomicAdd(&ssum[3 * s + 2], (unsigned long long)(w * pq));
+            }
+        }
+    }
+    if (!sums) return;
+    __syncthreads();
+    for (int i = threadIdx.x; i < 3 * S; i += kBkThreads)
+        if (ssum[i]) atomicAdd(&A.sums[i], ssum[i]);
+}
+
+// Triple sums: out[j] = sum over the voxels of f1 f2 f3_j in float64.  The voxels are cut into mom_blocks(total) *
+// kMomThreads strided runs (a function of the mesh size only); every run is added in index order with one fused
+// multiply-add per voxel, the runs of a block in block_sum's tree and the blocks by one workgroup in a fixed order.  The
+// result of field j therefore does not depend on which other fields share its launch.
+constexpr int kTsFields = 8;
+
+struct TripleArgs {
+    const float* f1;
+    const float* f2;
+    const float* f3[kTsFields];
+    int nj;
+    long long total;
+    double* partial;               // kTsFields rows of NBE_BK_PARTIALS
+};
+
+__global__ __launch_bounds__(kMomThreads) void triple_sums_kernel(TripleArgs A) {
+    __shared__ double red[kMomThreads];
+    double acc[kTsFields];
+#pragma unroll
+    for (int j = 0; j < kTsFields; ++j) acc[j] = 0.0;
+    const long long stride = (long long)gridDim.x * kMomThreads;
+    for (long long i = (long long)blockIdx.x * kMomThreads + threadIdx.x; i < A.total; i += stride) {
+        const double p = (double)A.f1[i] * (double)A.f2[i];           // exact: 48 bits
+#pragma unroll
+        for (int j = 0; j < kTsFields; ++j)
+            if (j < A.nj) acc[j] = fma(p, (double)A.f3[j][i], acc[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < kTsFields; ++j) {
+        if (j >= A.nj) break;
+        const double s = block_sum(acc[j], red);
+        if (threadIdx.x == 0) A.partial[(long long)j * NBE_BK_PARTIALS + blockIdx.x] = s;
+        __syncthreads();
+    }
+}
+
+// block j: out[j] = sum of partial[j][0 .. nb) in a fixed order
+__global__ __launch_bounds__(kMomThreads) void triple_finish_kernel(const double* __restrict__ partial, int nb,
+                                                                    double* __restrict__ out) {
+    __shared__ double red[kMomThreads];
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < nb; b += kMomThreads) acc += partial[(long long)blockIdx.x * NBE_BK_PARTIALS + b];
+    const double s = block_sum(acc, red);
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
+// Triangle counts: every pair (m1, m2) of the modes of shells 1 and 2 closes with m3 = -(m1 + m2); |m3|^2 is binned by
+// upper_bound over the K sorted distinct bounds of the third shells, and the count of a shell [lo2, hi2) is the sum of
+// the bins between its two bounds.  Integers throughout: exact at every mesh size.
+constexpr int kPcChunk = 1024;
+
+struct PairArgs {
+    const int4* m1; long long c1;
+    const int4* m2; long long c2;
+    const int* edges; int K;
+    unsigned long long* hist;      // K + 1
+    long long tiles2;
+};
+
+__global__ __launch_bounds__(kBkThreads) void pair_count_kernel(PairArgs A) {
+    __shared__ int4 chunk[kPcChunk];
+    __shared__ int edges[NBE_BK_MAX_EDGES];
+    __shared__ unsigned hist[NBE_BK_MAX_EDGES + 1];
+    const int K = A.K, tid = threadIdx.x;
+    const long long t2 = blockIdx.x % A.tiles2, t1 = blockIdx.x / A.tiles2;
+    const long long j0 = t2 * kPcChunk;
+    const int cn = (int)(A.c2 - j0 < kPcChunk ? A.c2 - j0 : kPcChunk);
+    for (int i = tid; i < cn; i += kBkThreads) chunk[i] = A.m2[j0 + i];
+    for (int i = tid; i < K; i += kBkThreads) edges[i] = A.edges[i];
+    for (int i = tid; i <= K; i += kBkThreads) hist[i] = 0u;
+    __syncthreads();
+    int top = 1;
+    while (2 * top <= K) top *= 2;
+    const long long i1 = t1 * kBkThreads + tid;
+    if (i1 < A.c1) {
+        const int4 a = A.m1[i1];
+        const int e0 = edges[0], e1 = edges[K - 1];
+        for (int j = 0; j < cn; ++j) {
+            const int4 b = chunk[j];
+            const int x = a.x + b.x, y = a.y + b.y, z = a.z + b.z;
+            const int q = x * x + y * y + z * z;
+            if (q < e0 || q >= e1) continue;
+            int pos = 0;
+            for (int step = top; step > 0; step >>= 1)
+                if (pos + step <= K && edges[pos + step - 1] <= q) pos += step;
+            atomicAdd(&hist[pos], 1u);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i <= K; i += kBkThreads)
+        if (hist[i]) atomicAdd(&A.hist[i], (unsigned long long)hist[i]);
+}
+
+// Central moments to the fourth: the sum, then the sums of d^2, d^3 and d^4 about the mean, over the partition and in the
+// order of nbe_field_moments.  mom[0..3] = mean, std, m3, m4; partials from mom[4], three rows of kMomMaxBlocks.
+template <bool CENTRED>
+__global__ __launch_bounds__(kMomThreads) void moments4_pass_kernel(const float* __restrict__ x, long long total,
+                                                                    double* __restrict__ mom) {
+    __shared__ double red[kMomThreads];
+    const double mean = CENTRED ? mom[0] : 0.0;
+    const long long stride = (long long)gridDim.x * kMomThreads;
+    double a2 = 0.0, a3 = 0.0, a4 = 0.0;
+    auto add = [&](float v) {
+        if (CENTRED) {
+            const double d = v - mean, d2 = d * d;
+            a2 += d2; a3 += d2 * d; a4 += d2 * d2;
+        } else {
+            a2 += v;
+        }
+    };
+    long long i = (long long)blockIdx.x * kMomThreads + threadIdx.x;
+    for (; i + 3 * stride < total; i += 4 * stride) {        // four loads in flight, added in index order
+        const float a = x[i], b = x[i + stride], c = x[i + 2 * stride], d = x[i + 3 * stride];
+        add(a); add(b); add(c); add(d);
+    }
+    for (; i < total; i += stride) add(x[i]);
+    const double s2 = block_sum(a2, red);
+    if (threadIdx.x == 0) mom[4 + blockIdx.x] = s2;
+    if (!CENTRED) return;
+    __syncthreads();
+    const double s3 = block_sum(a3, red);
+    if (threadIdx.x == 0) mom[4 + kMomMaxBlocks + blockIdx.x] = s3;
+    __syncthreads();
+    const double s4 = block_sum(a4, red);
+    if (threadIdx.x == 0) mom[4 + 2 * kMomMaxBlocks + blockIdx.x] = s4;
+}
+
+// one block: mom[slot] = sum of row `row` of the partials / total (slot 1: its square root)
+__global__ __launch_bounds__(kMomThreads) void moments4_finish_kernel(double* mom, int nb, long long total, int row,
+                                                                      int slot) {
+    __shared__ double red[kMomThreads];
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < nb; b += kMomThreads) acc += mom[4 + (long long)row * kMomMaxBlocks + b];
+    const double s = block_sum(acc, red) / (double)total;
+    if (threadIdx.x == 0) mom[slot] = slot == 1 ? sqrt(s) : s;
+}
+
+// One-point histogram over nbins uniform bins with float64 edges (np.linspace): voxel x, widened to float64, falls into
+// bin searchsorted(edges, x, "right") - 1, and x == edges[nbins] into the last bin.  The bin is estimated from the uniform
+// spacing and then moved against the edges themselves, so the rule is the edges' and not the estimate's.  LDS histograms
+// per workgroup, flushed with 64-bit integer atomics; counts[nbins] = finite voxels outside, counts[nbins + 1] = non-finite.
+// A density field puts half of its voxels into one or two bins, and lanes of one instruction that add to one LDS word
+// are served one after the other: the workgroup keeps as many copies of the histogram as fit the space of 4096 bins (16
+// at most), lane l adds to copy l mod copies, and the flush sums them (DESIGN.md section 12.2 has the measurements).
+struct PdfArgs {
+    const float* x;
+    long long total;
+    double lo, hi, scale;
+    int nbins;
+    const double* edges;
+    unsigned long long* counts;
+};
+
+__global__ __launch_bounds__(kBkThreads) void field_histogram_kernel(PdfArgs A) {
+    __shared__ double edges[NBE_PDF_MAX_BINS + 1];
+    __shared__ unsigned hist[NBE_PDF_MAX_BINS + 2];
+    const int nb = A.nbins;
+    int copies = 1;
+    while (copies < 16 && 2 * copies * (nb + 2) <= NBE_PDF_MAX_BINS + 2) copies *= 2;
+    unsigned* mine = hist + (threadIdx.x & (copies - 1)) * (nb + 2);
+    for (int i = threadIdx.x; i <= nb; i += kBkThreads) edges[i] = A.edges[i];
+    for (int i = threadIdx.x; i < copies * (nb + 2); i += kBkThreads) hist[i] = 0u;
+    __syncthreads();
+    for (long long i = blockIdx.x * (long long)kBkThreads + threadIdx.x; i < A.total; i += (long long)gridDim.x * kBkThreads) {
+        const float xf = A.x[i];
+        const double x = (double)xf;
+        int b;
+        if (!isfinite(xf)) {
+            b = nb + 1;
+        } else if (x < A.lo || x > A.hi) {
+            b = nb;
+        } else {
+            b = (int)((x - A.lo) * A.scale);
+            b = b < 0 ? 0 : b > nb - 1 ? nb - 1 : b;
+            while (b > 0 && x < edges[b]) --b;
+            while (b < nb - 1 && x >= edges[b + 1]) ++b;
+        }
+        atomicAdd(&mine[b], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nb + 2; i += kBkThreads) {
+        unsigned v = 0u;                                  // a workgroup sees fewer than 2^32 voxels
+        for (int c = 0; c < copies; ++c) v += hist[c * (nb + 2) + i];
+        if (v) atomicAdd(&A.counts[i], (unsigned long long)v);
+    }
+}
+
 int fail(const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -678,6 +966,121 @@ int nbe_minkowski_counts(const void* field, int64_t n, const void* thresholds, i
     const long long grid = A.items < 4LL * cus ? A.items : 4LL * cus;
     hipLaunchKernelGGL(minkowski_counts_kernel, dim3((unsigned)grid), dim3(kMfThreads), 0, (hipStream_t)stream, A);
     return launched("nbe_minkowski_counts");
+}
+
+int nbe_shell_filter(const void* spectrum, int64_t n, const void* shells, int nshells, void* filtered, void* binmax,
+                     void* sums, void* stream) {
+    if (!spectrum || !shells) return fail("nbe_shell_filter: NULL argument");
+    if (n < NBE_BK_MIN_N || n > NBE_BK_MAX_N)
+        return fail("nbe_shell_filter: mesh size %lld unsupported (%d .. %d)", (long long)n, NBE_BK_MIN_N, NBE_BK_MAX_N);
+    if (nshells < 1 || nshells > NBE_BK_MAX_SHELLS)
+        return fail("nbe_shell_filter: %d shells unsupported (1 .. %d)", nshells, NBE_BK_MAX_SHELLS);
+    if (!filtered && !sums) return fail("nbe_shell_filter: nothing to do (filtered and sums are both NULL)");
+    if ((binmax == nullptr) != (sums == nullptr)) return fail("nbe_shell_filter: binmax and sums go together");
+    ShellArgs A;
+    A.spec = (const float2*)spectrum;
+    A.n = n;
+    A.par = (const long long*)shells;
+    A.S = nshells;
+    A.out = (float2*)filtered;
+    A.binmax = (unsigned*)binmax;
+    A.sums = (unsigned long long*)sums;
+    const long long total = n * n * (n / 2 + 1);
+    const int grid = grid_for(total, 4 * kBkThreads);
+    hipStream_t s = (hipStream_t)stream;
+    if (sums) {
+        hipLaunchKernelGGL(shell_max_kernel, dim3(grid < 2048 ? grid : 2048), dim3(kBkThreads), 0, s, A);
+        if (int rc = launched("nbe_shell_filter (max)")) return rc;
+    }
+    hipLaunchKernelGGL(shell_filter_kernel, dim3(grid < 4096 ? grid : 4096), dim3(kBkThreads), 0, s, A);
+    return launched("nbe_shell_filter");
+}
+
+int nbe_triple_sums(const void* f1, const void* f2, const void* f3, int nfields, int64_t n, void* partials, void* out,
+                    void* stream) {
+    if (!f1 || !f2 || !f3 || !partials || !out) return fail("nbe_triple_sums: NULL argument");
+    if (n < 1 || n > NBE_BK_MAX_N) return fail("nbe_triple_sums: mesh size %lld unsupported (1 .. %d)", (long long)n,
+                                               NBE_BK_MAX_N);
+    if (nfields < 1 || nfields > NBE_BK_MAX_SHELLS)
+        return fail("nbe_triple_sums: %d fields unsupported (1 .. %d)", nfields, NBE_BK_MAX_SHELLS);
+    const long long total = (long long)n * n * n;
+    const int nb = mom_blocks(total);
+    hipStream_t s = (hipStream_t)stream;
+    for (int j0 = 0; j0 < nfields; j0 += kTsFields) {
+        TripleArgs A;
+        A.f1 = (const float*)f1;
+        A.f2 = (const float*)f2;
+        A.nj = nfields - j0 < kTsFields ? nfields - j0 : kTsFields;
+        for (int j = 0; j < kTsFields; ++j) A.f3[j] = (const float*)f3 + (long long)(j0 + (j < A.nj ? j : 0)) * total;
+        A.total = total;
+        A.partial = (double*)partials + (long long)j0 * NBE_BK_PARTIALS;
+        hipLaunchKernelGGL(triple_sums_kernel, dim3(nb), dim3(kMomThreads), 0, s, A);
+        if (int rc = launched("nbe_triple_sums")) return rc;
+    }
+    hipLaunchKernelGGL(triple_finish_kernel, dim3(nfields), dim3(kMomThreads), 0, s, (const double*)partials, nb,
+                       (double*)out);
+    return launched("nbe_triple_sums (finish)");
+}
+
+int nbe_triangle_counts(const void* modes1, int64_t count1, const void* modes2, int64_t count2, const void* edges,
+                        int nedges, void* hist, void* stream) {
+    if (!modes1 || !modes2 || !edges || !hist) return fail("nbe_triangle_counts: NULL argument");
+    if (count1 < 1 || count2 < 1) return fail("nbe_triangle_counts: empty mode list");
+    if (nedges < 2 || nedges > NBE_BK_MAX_EDGES)
+        return fail("nbe_triangle_counts: %d bounds unsupported (2 .. %d)", nedges, NBE_BK_MAX_EDGES);
+    PairArgs A;
+    A.m1 = (const int4*)modes1; A.c1 = count1;
+    A.m2 = (const int4*)modes2; A.c2 = count2;
+    A.edges = (const int*)edges; A.K = nedges;
+    A.hist = (unsigned long long*)hist;
+    A.tiles2 = (count2 + kPcChunk - 1) / kPcChunk;
+    const long long blocks = ((count1 + kBkThreads - 1) / kBkThreads) * A.tiles2;
+    if (blocks > INT_MAX) return fail("nbe_triangle_counts: %lld x %lld pairs exceed one launch", (long long)count1,
+                                      (long long)count2);
+    hipLaunchKernelGGL(pair_count_kernel, dim3((unsigned)blocks), dim3(kBkThreads), 0, (hipStream_t)stream, A);
+    return launched("nbe_triangle_counts");
+}
+
+int nbe_field_moments4(const void* field, int64_t count, void* moments, void* stream) {
+    if (!field || !moments) return fail("nbe_field_moments4: NULL argument");
+    if (count < 1 || count > NBE_ONEPOINT_MAX_VOXELS)
+        return fail("nbe_field_moments4: %lld voxels unsupported (1 .. 2^40)", (long long)count);
+    const int nb = mom_blocks(count);
+    hipStream_t s = (hipStream_t)stream;
+    const float* x = (const float*)field;
+    double* mom = (double*)moments;
+    hipLaunchKernelGGL(moments4_pass_kernel<false>, dim3(nb), dim3(kMomThreads), 0, s, x, (long long)count, mom);
+    hipLaunchKernelGGL(moments4_finish_kernel, dim3(1), dim3(kMomThreads), 0, s, mom, nb, (long long)count, 0, 0);
+    hipLaunchKernelGGL(moments4_pass_kernel<true>, dim3(nb), dim3(kMomThreads), 0, s, x, (long long)count, mom);
+    hipLaunchKernelGGL(moments4_finish_kernel, dim3(1), dim3(kMomThreads), 0, s, mom, nb, (long long)count, 0, 1);
+    hipLaunchKernelGGL(moments4_finish_kernel, dim3(1), dim3(kMomThreads), 0, s, mom, nb, (long long)count, 1, 2);
+    hipLaunchKernelGGL(moments4_finish_kernel, dim3(1), dim3(kMomThreads), 0, s, mom, nb, (long long)count, 2, 3);
+    return launched("nbe_field_moments4");
+}
+
+int nbe_field_histogram(const void* field, int64_t count, double lo, double hi, const void* edges, int nbins,
+                        void* counts, void* stream) {
+    if (!field || !edges || !counts) return fail("nbe_field_histogram: NULL argument");
+    if (count < 1 || count > NBE_ONEPOINT_MAX_VOXELS)
+        return fail("nbe_field_histogram: %lld voxels unsupported (1 .. 2^40)", (long long)count);
+    if (nbins < 2 || nbins > NBE_PDF_MAX_BINS)
+        return fail("nbe_field_histogram: %d bins unsupported (2 .. %d)", nbins, NBE_PDF_MAX_BINS);
+    if (!(hi > lo) || !std::isfinite(lo) || !std::isfinite(hi))
+        return fail("nbe_field_histogram: edges %g .. %g are not an interval", lo, hi);
+    hipStream_t s = (hipStream_t)stream;
+    PdfArgs A;
+    A.x = (const float*)field;
+    A.total = count;
+    A.lo = lo; A.hi = hi;
+    A.scale = (double)nbins / (hi - lo);
+    A.nbins = nbins;
+    A.edges = (const double*)edges;
+    A.counts = (unsigned long long*)counts;
+    // a workgroup's 32-bit LDS bins hold at most count / grid voxels: at least count / 2^31 workgroups
+    long long grid = (count + 8LL * kBkThreads - 1) / (8LL * kBkThreads);
+    grid = grid > 2048 ? 2048 : grid;
+    hipLaunchKernelGGL(field_histogram_kernel, dim3((unsigned)grid), dim3(kBkThreads), 0, s, A);
+    return launched("nbe_field_histogram");
 }
 
 }  // extern "C"

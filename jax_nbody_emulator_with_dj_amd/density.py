@@ -11,6 +11,9 @@ assignment window (`scripts/utils.py:136-148`) and measures P(k) (`scripts/utils
     k, pk, nmodes = power_spectrum(delta_emu, boxsize=1000.0, other=delta_lpt)     # cross spectrum Re<a b*>
     delta_c = deconvolve_mas(delta, worder=2)
     mf = minkowski_functionals(delta, boxsize=1000.0)    # v0 .. v3 at 41 thresholds of the standardized field
+    bk = bispectrum(delta, boxsize=1000.0, k1=0.1, k2=0.1, theta=np.linspace(0, np.pi, 25))    # B, Q, ntriangles, ...
+    st = field_statistics(delta)                         # mean, std, skewness, kurtosis_excess
+    pdf = field_pdf(delta, lo=-1.0, hi=8.0, nbins=120)   # np.histogram's counts and density
 
 Conventions (as DISCO-DJ / Pylians and the lattice of `scripts/halos.py:394-403`):
 
@@ -30,6 +33,9 @@ Conventions (as DISCO-DJ / Pylians and the lattice of `scripts/halos.py:394-403`
   mean P and the number of modes per shell as float64 NumPy arrays.
 - `minkowski_functionals` (reference `scripts/utils.py:652-763`) counts the elements of the periodic cubical complex of
   each excursion set {w >= t} in one pass over the field: see its docstring for the definition.
+- `bispectrum` (reference `scripts/utils.py:1314-1399`, Pylians `Bk`) is the FFT estimator of B(k1, k2, theta) and of the
+  reduced Q(theta); `field_statistics` and `field_pdf` (`scripts/utils.py:1164-1187`, `:1248-1274`) are the one-point
+  moments and histogram.  Their docstrings hold the definitions; all three return small host objects.
 
 Residency: NumPy in gives NumPy out; a CUDA torch tensor in gives a CUDA tensor on the same device, with no host copy,
 enqueued on torch's current stream of that device.  float16 displacements are read as half in the kernel.  There is no CPU
@@ -49,7 +55,8 @@ try:
 except Exception:  # pragma: no cover
     torch = None
 
-__all__ = ["paint_density", "deconvolve_mas", "power_spectrum", "minkowski_functionals"]
+__all__ = ["paint_density", "deconvolve_mas", "power_spectrum", "minkowski_functionals", "bispectrum",
+           "field_statistics", "field_pdf"]
 
 WORDERS = {1: "NGP", 2: "CIC", 3: "TSC", 4: "PCS"}
 _UNIT = 2.0 ** 22           # fixed-point units per particle mass (include/nbe.h, nbe_paint_mesh)
@@ -58,6 +65,12 @@ _MF_MAX_N = 2048            # include/nbe.h: NBE_MF_MAX_N, NBE_MF_MAX_THRESHOLDS
 _MF_MAX_T = 1024
 _MOMENT_WORDS = 2050
 MF_CONVENTION = "periodic_voxel_cubical_complex"
+_BK_MIN_N, _BK_MAX_N = 4, 2048   # include/nbe.h: NBE_BK_MIN_N, NBE_BK_MAX_N, NBE_BK_MAX_SHELLS - 2, NBE_BK_PARTIALS
+_BK_MAX_T = 256
+_BK_PARTIALS = 2048
+_MOMENT4_WORDS = 6148           # include/nbe.h: NBE_MOMENTS4_WORDS, NBE_PDF_MAX_BINS, NBE_ONEPOINT_MAX_VOXELS
+_PDF_MAX_BINS = 4096
+_ONEPOINT_MAX = 1 << 40
 
 
 def _is_torch(x):
@@ -355,3 +368,335 @@ def minkowski_functionals(field, boxsize=1000.0, thresholds=None, standardize=Tr
     v0, v1, v2, v3 = _mf_values(counts, n, L)
     return {"thresholds": thr.astype(np.float64), "v0": v0, "v1": v1, "v2": v2, "v3": v3, "mean": mean, "std": std,
             "standardize": standardize, "convention": MF_CONVENTION, "counts": counts}
+
+
+# ---- bispectrum -----------------------------------------------------------------------------
+
+def bispectrum_kappa3(kappa1, kappa2, theta):
+    """|k1 + k2| / k_F for the angle theta between the vectors k1 and k2 (theta = 0: kappa1 + kappa2)."""
+    th = np.asarray(theta, dtype=np.float64)
+    return np.sqrt((kappa2 * np.sin(th)) ** 2 + (kappa2 * np.cos(th) + kappa1) ** 2)
+
+
+def bispectrum_shell_bounds(kappa, dk):
+    """Integer bounds [lo2, hi2) on |m|^2 of the shell lo^2 <= |m|^2 < hi^2, lo = max(kappa - dk/2, 0), hi = kappa + dk/2:
+    the squares in float64, their ceilings as integers, and lo2 >= 1 because the DC mode belongs to no shell."""
+    kappa = np.asarray(kappa, dtype=np.float64)
+    lo = np.maximum(kappa - 0.5 * dk, 0.0)
+    hi = kappa + 0.5 * dk
+    lo2 = np.maximum(np.ceil(lo * lo), 1.0).astype(np.int64)
+    hi2 = np.ceil(hi * hi).astype(np.int64)
+    return lo2, hi2
+
+
+def _shell_modes(lo2, hi2):
+    """The wave vectors m of the full grid with lo2 <= |m|^2 < hi2 as (count, 4) int32 rows (m_x, m_y, m_z, 0)."""
+    if hi2 <= lo2:
+        return np.zeros((0, 4), np.int32)
+    r = int(np.floor(np.sqrt(float(hi2 - 1))))
+    while (r + 1) ** 2 < hi2:
+        r += 1
+    while r * r >= hi2:
+        r -= 1
+    a = np.arange(-r, r + 1, dtype=np.int64)
+    plane = a[:, None] ** 2 + a[None, :] ** 2
+    rows = []
+    for mx in a:
+        q = plane + mx * mx
+        jy, jz = np.nonzero((q >= lo2) & (q < hi2))
+        if jy.size:
+            m = np.zeros((jy.size, 4), np.int32)
+            m[:, 0] = mx
+            m[:, 1] = a[jy]
+            m[:, 2] = a[jz]
+            rows.append(m)
+    return np.concatenate(rows) if rows else np.zeros((0, 4), np.int32)
+
+
+def _bk_validate(delta, boxsize, k1, k2, theta, dk, mas_worder):
+    d = _check_array(delta, "delta")
+    if d.ndim != 3 or len(set(d.shape)) != 1:
+        raise ValueError("bispectrum needs a cubic (n, n, n) field, got shape %s" % (tuple(d.shape),))
+    n = int(d.shape[0])
+    if not _BK_MIN_N <= n <= _BK_MAX_N:
+        raise ValueError("bispectrum: mesh size %d unsupported (%d .. %d)" % (n, _BK_MIN_N, _BK_MAX_N))
+    if _dtype_name(d) != "float32":
+        raise ValueError("delta must be float32, got %s" % _dtype_name(d))
+    L = _triple(boxsize, "boxsize", "a length")
+    if len(set(L)) != 1:
+        raise ValueError("bispectrum needs a cubic box, got boxsize %s" % (L,))
+    vals = {}
+    for name, v in (("k1", k1), ("k2", k2), ("dk", dk)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Real) or not np.isfinite(float(v)) or float(v) <= 0:
+            raise ValueError("%s must be a positive finite number, got %r" % (name, v))
+        vals[name] = float(v)
+    try:
+        th = np.asarray(theta, dtype=np.float64).ravel()
+    except (TypeError, ValueError):
+        raise ValueError("theta must be numbers, got %r" % (theta,))
+    if not 1 <= th.size <= _BK_MAX_T:
+        raise ValueError("theta must hold 1 .. %d angles, got %d" % (_BK_MAX_T, th.size))
+    if not np.isfinite(th).all() or (th < 0).any() or (th > np.pi).any():
+        raise ValueError("theta must be finite angles in [0, pi]")
+    if mas_worder is not None:
+        mas_worder = _check_worder(mas_worder)
+    kF = 2.0 * np.pi / L[0]
+    ka1, ka2, dk = vals["k1"] / kF, vals["k2"] / kF, vals["dk"]
+    if 2.0 * (ka1 + ka2) + 1.5 * dk >= n:
+        raise ValueError("bispectrum: 2 (k1 + k2) / k_F + 1.5 dk = %.6g reaches the mesh size %d: triangles would close "
+                         "modulo n only" % (2.0 * (ka1 + ka2) + 1.5 * dk, n))
+    kappa = np.concatenate([[ka1, ka2], bispectrum_kappa3(ka1, ka2, th)])
+    lo2, hi2 = bispectrum_shell_bounds(kappa, dk)
+    modes = [_shell_modes(int(lo2[i]), int(hi2[i])) for i in (0, 1)]
+    for i in (0, 1):
+        if not len(modes[i]):
+            raise ValueError("bispectrum: shell %d (k%d = %g, |m| in [%g, %g)) holds no mode of the mesh"
+                             % (i + 1, i + 1, vals["k%d" % (i + 1)], max(kappa[i] - dk / 2, 0.0), kappa[i] + dk / 2))
+    return d, n, L[0], th, kappa, lo2, hi2, modes, mas_worder
+
+
+def _bk_shell_params(n, lo2, hi2):
+    """(S, 4) int64 rows (lo2, hi2, koff, kexp) of nbe_shell_filter: |m| - koff is summed in units of 2^-kexp, chosen so
+    that the sum over every mode the shell can hold stays below 2^62."""
+    par = np.zeros((len(lo2), 4), np.int64)
+    par[:, 0], par[:, 1] = lo2, hi2
+    koff = np.floor(np.sqrt(lo2.astype(np.float64))).astype(np.int64)
+    koff = np.where(koff * koff > lo2, koff - 1, koff)
+    top = np.sqrt(np.maximum(hi2, 1).astype(np.float64)) + 1.0
+    cap = np.minimum(float(n) ** 3, (2.0 * top + 1.0) ** 3)
+    kexp = np.floor(60.0 - np.log2(cap * (top - koff + 1.0))).astype(np.int64)
+    par[:, 2], par[:, 3] = koff, np.clip(kexp, 0, 36)
+    return par
+
+
+def _bk_batch(dev, n, want, max_batch):
+    """How many third shells are filtered and transformed at once: from the free memory of the device.  A shell in flight
+    costs its half spectrum, the copy the complex-to-real transform works on, its real field and the transform's
+    workspace: four fields of 4 n^3 bytes are reserved for each."""
+    if max_batch is not None:
+        return max(1, min(int(max_batch), want))
+    free, _ = torch.cuda.mem_get_info(dev)
+    free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)      # cached blocks are reusable
+    per_shell = 16 * (n ** 3 + 2 * n * n)
+    return max(1, min(want, int(0.7 * free) // per_shell))
+
+
+def bispectrum(delta, boxsize=1000.0, k1=0.1, k2=0.1, theta=None, dk=1.0, mas_worder=None, _max_batch=None,
+               _timings=None):
+    """Bispectrum B(k1, k2, theta) and reduced bispectrum Q(theta) of a periodic density field (reference
+    scripts/utils.py:1314-1399: Pylians Bk_library.Bk with threads=1, for k1 = k2 = 0.1 and k1 = 0.05, k2 = 0.1 h/Mpc at
+    25 angles).
+
+    delta: cubic (n, n, n) float32, NumPy array or CUDA tensor (read where it lives, on torch's current stream of its
+    device), 4 <= n <= 2048.  boxsize: L (scalar, or a 3-tuple of equal values).  k1, k2: positive, in the units in which
+    power_spectrum returns k (h/Mpc for a box in Mpc/h).  theta: 1 .. 256 finite angles in [0, pi], any order, duplicates
+    allowed (default np.linspace(0, pi, 25)); results come in the caller's order.  dk: full shell width in units of
+    k_F = 2 pi / L, positive.  mas_worder: None, or 1-4 to divide the spectrum by the assignment window first
+    (deconvolve_mas's kernel; Pylians' MAS= argument).
+
+    Definition.  Let kappa = k / k_F, let m in Z^3 run over the wave vectors of the full complex grid (each component in
+    (-n/2, n/2]), and let delta_m be the unnormalised forward FFT.
+    - kappa3(theta) = sqrt((kappa2 sin theta)^2 + (kappa2 cos theta + kappa1)^2).  theta is the angle between the vectors
+      k1 and k2, so theta = 0 gives kappa1 + kappa2.
+    - Shell S(kappa) = { m != 0 : lo^2 <= |m|^2 < hi^2 } with lo = max(kappa - dk/2, 0) and hi = kappa + dk/2.  The squares
+      are taken in float64 and compared with the integer |m|^2.  The DC mode belongs to no shell.  Shells of neighbouring
+      theta may overlap or leave gaps.
+    - N_tri(theta) = #{ (m1, m2, m3) : m1 in S(kappa1), m2 in S(kappa2), m3 in S(kappa3(theta)), m1 + m2 + m3 = 0 }, an
+      int64.
+    - B(theta) = L^6 / n^9 * sum over those triangles of Re(delta_m1 delta_m2 delta_m3), divided by N_tri(theta).
+    - P_i = L^3 / n^6 * mean of |delta_m|^2 over shell i.  Q(theta) = B / (P1 P2 + P2 P3(theta) + P3(theta) P1).
+    - pk, k, nmodes have 2 + T entries: shell 1, shell 2, then one per theta.  They hold the mean power, the mean |k| and
+      the mode count of each shell, computed by the integer-sum scheme of power_spectrum.
+    - A theta whose N_tri is 0 returns ntriangles = 0 and NaN in B and Q.  An empty third shell gives NaN in its pk and k.
+      (For k1 = k2 and theta = pi the third shell is empty.)  No warning, no exception.
+    - Closure is exact, not modulo n: if 2 (kappa1 + kappa2) + 1.5 dk >= n the three outer radii can sum to n, and the
+      call raises ValueError.
+
+    Returns a dict of host arrays: theta, k3 (= kappa3 k_F), B, Q (float64, T entries), ntriangles (int64, T), pk, k
+    (float64, 2 + T) and nmodes (int64, 2 + T).  ValueError before any device work for: an empty shell 1 or shell 2, a
+    non-cubic or non-float32 field, a non-cubic box, theta outside [0, pi], n outside 4 .. 2048, and the closure condition
+    above.  A non-finite voxel raises NBEError.
+
+    This is the standard FFT estimator (Scoccimarro 2000), which is what Pylians' Bk computes: with I_S the indicator of a
+    shell and F_S = irfftn(delta I_S), the sum over the voxels of F1 F2 F3 is n^-6 times the sum over the triangles.  The
+    sums go through float32 transforms and a float64 reduction in a fixed order: the arrays are the same bits on every
+    call and for every batch size.  N_tri is not taken from transforms of the indicators but counted in integers over the
+    pairs (m1, m2), so it is exact at every mesh size (at the cost of |S1| |S2| integer operations).
+
+    Difference from the reference: Pylians is not available where this library is developed, so its exact bin edges
+    cannot be pinned; the shells are the ones defined above, and dk is a parameter so that a caller can match the width
+    their Pylians uses.  Matching Pylians' numbers bit for bit is not claimed."""
+    if theta is None:
+        theta = np.linspace(0.0, np.pi, 25)
+    d, n, L, th, kappa, lo2, hi2, modes, mas_worder = _bk_validate(delta, boxsize, k1, k2, theta, dk, mas_worder)
+    host = not _is_torch(d)
+    dev = _device() if host else d.device
+    l = _lib.lib()
+    T, S = int(th.size), int(th.size) + 2
+    kF = 2.0 * np.pi / L
+    par = _bk_shell_params(n, lo2, hi2)
+    edges = np.unique(np.concatenate([lo2[2:], hi2[2:]])).astype(np.int32)
+    h = n // 2 + 1
+    ev = []
+
+    def mark(name):
+        if _timings is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record(torch.cuda.current_stream(dev))
+            ev.append((name, e))
+
+    with torch.cuda.device(dev):
+        s = _stream(dev)
+        mark("start")
+        x = _to_device(d, dev, (torch.float32,))
+        spec = torch.fft.rfftn(x).contiguous()            # the kernels index the half spectrum row-major
+        del x
+        if mas_worder is not None:
+            _lib.check(l.nbe_deconvolve_mas(_ptr(spec), _i64((n, n, n)), mas_worder, s))
+        mark("rfftn")
+        par_d = torch.from_numpy(par).to(dev)
+        binmax = torch.zeros(S, dtype=torch.int32, device=dev)
+        sums = torch.zeros((S, 3), dtype=torch.int64, device=dev)
+        out = torch.zeros(T, dtype=torch.float64, device=dev)
+
+        def fields(s0, cnt):
+            """The real fields of shells s0 .. s0 + cnt - 1: filter (with the shells' sums), then one batched irfftn."""
+            filt = torch.empty((cnt, n, n, h), dtype=torch.complex64, device=dev)
+            mark("other")
+            _lib.check(l.nbe_shell_filter(_ptr(spec), n, C.c_void_p(par_d.data_ptr() + 32 * s0), cnt, _ptr(filt),
+                                          C.c_void_p(binmax.data_ptr() + 4 * s0), C.c_void_p(sums.data_ptr() + 24 * s0), s))
+            mark("shell_filter")
+            f = torch.fft.irfftn(filt, s=(n, n, n), dim=(1, 2, 3)).contiguous()
+            mark("irfftn")
+            return f
+
+        f12 = fields(0, 2)
+        batch = _bk_batch(dev, n, T, _max_batch)
+        partials = torch.empty((min(batch, T), _BK_PARTIALS), dtype=torch.float64, device=dev)
+        for t0 in range(0, T, batch):
+            cnt = min(batch, T - t0)
+            f3 = fields(2 + t0, cnt)
+            _lib.check(l.nbe_triple_sums(_ptr(f12[0]), _ptr(f12[1]), _ptr(f3), cnt, n, _ptr(partials),
+                                         C.c_void_p(out.data_ptr() + 8 * t0), s))
+            mark("triple_sums")
+            del f3
+        del f12, spec
+        hist = None
+        if edges.size >= 2:
+            m1 = torch.from_numpy(modes[0]).to(dev)
+            m2 = torch.from_numpy(modes[1]).to(dev)
+            ed = torch.from_numpy(edges).to(dev)
+            hist_d = torch.zeros(edges.size + 1, dtype=torch.int64, device=dev)
+            mark("other")
+            _lib.check(l.nbe_triangle_counts(_ptr(m1), len(modes[0]), _ptr(m2), len(modes[1]), _ptr(ed), int(edges.size),
+                                             _ptr(hist_d), s))
+            mark("triangle_counts")
+            hist = hist_d.cpu().numpy()
+        tri = out.cpu().numpy()
+        bm = binmax.cpu().numpy().view(np.float32).astype(np.float64)
+        sm = sums.cpu().numpy()
+        if _timings is not None:
+            torch.cuda.synchronize(dev)
+            for (_, a), (name, b) in zip(ev[:-1], ev[1:]):
+                _timings[name] = _timings.get(name, 0.0) + a.elapsed_time(b)
+            _timings["batch"] = batch
+    if not np.isfinite(bm).all() or not np.isfinite(tri).all():
+        raise NBEError("bispectrum: the field has voxels that are not finite")
+    ntri = np.zeros(T, np.int64)
+    if hist is not None:
+        cum = np.cumsum(hist)
+        ntri = cum[np.searchsorted(edges, hi2[2:])] - cum[np.searchsorted(edges, lo2[2:])]
+        ntri = np.where(hi2[2:] > lo2[2:], ntri, 0).astype(np.int64)
+    cnt = sm[:, 0].astype(np.float64)
+    _, e = np.frexp(bm)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        k = (par[:, 2] + np.ldexp(sm[:, 1].astype(np.float64), -par[:, 3].astype(np.int64)) / cnt) * kF
+        pk = np.ldexp(sm[:, 2].astype(np.float64), e - 32) / cnt * (L ** 3 / float(n) ** 6)
+        B = np.where(ntri > 0, tri * (L ** 6 / float(n) ** 3) / ntri, np.nan)
+        Q = B / (pk[0] * pk[1] + pk[1] * pk[2:] + pk[2:] * pk[0])
+    return {"theta": th.copy(), "k3": kappa[2:] * kF, "B": B, "Q": Q, "ntriangles": ntri, "pk": pk, "k": k,
+            "nmodes": sm[:, 0].astype(np.int64)}
+
+
+# ---- one-point statistics --------------------------------------------------------------------------------------------
+
+def _onepoint_validate(field, what):
+    f = _check_array(field, "field")
+    if f.ndim != 3 or min(f.shape) < 1:
+        raise ValueError("%s needs a 3-D field, got shape %s" % (what, tuple(f.shape)))
+    if _dtype_name(f) != "float32":
+        raise ValueError("field must be float32, got %s" % _dtype_name(f))
+    count = int(f.shape[0]) * int(f.shape[1]) * int(f.shape[2])
+    if count > _ONEPOINT_MAX:
+        raise ValueError("%s: %d voxels unsupported (1 .. 2^40)" % (what, count))
+    return f, count
+
+
+def field_statistics(field):
+    """Mean, population standard deviation, skewness m3 / sigma^3 and excess kurtosis m4 / sigma^4 - 3 of a field
+    (reference scripts/utils.py:1164-1187, _field_moments), with m_p the mean of (x - mean)^p.
+
+    field: any 3-D float32 NumPy array or CUDA tensor.  The sums are float64 on the device, over a partition of the
+    voxels that depends on their number only and in a fixed order: the same bits on every call.  Returns a dict of Python
+    floats: mean, std, skewness, kurtosis_excess; the last two are 0.0 when std <= 0, as in the reference."""
+    f, count = _onepoint_validate(field, "field_statistics")
+    host = not _is_torch(f)
+    dev = _device() if host else f.device
+    l = _lib.lib()
+    with torch.cuda.device(dev):
+        x = _to_device(f, dev, (torch.float32,))
+        mom = torch.empty(_MOMENT4_WORDS, dtype=torch.float64, device=dev)
+        _lib.check(l.nbe_field_moments4(_ptr(x), count, _ptr(mom), _stream(dev)))
+        mean, std, m3, m4 = (float(v) for v in mom[:4].cpu().numpy())
+    skew = m3 / std ** 3 if std > 0 else 0.0
+    kurt = m4 / std ** 4 - 3.0 if std > 0 else 0.0
+    return {"mean": mean, "std": std, "skewness": skew, "kurtosis_excess": kurt}
+
+
+def pdf_edges(lo, hi, nbins):
+    """The float64 edges np.linspace(lo, hi, nbins + 1) of field_pdf, validated."""
+    for name, v in (("lo", lo), ("hi", hi)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Real) or not np.isfinite(float(v)):
+            raise ValueError("%s must be a finite number, got %r" % (name, v))
+    if isinstance(nbins, (bool, np.bool_)) or not isinstance(nbins, numbers.Integral) or not 2 <= int(nbins) <= _PDF_MAX_BINS:
+        raise ValueError("nbins must be an int in 2 .. %d, got %r" % (_PDF_MAX_BINS, nbins))
+    if not float(hi) > float(lo):
+        raise ValueError("hi must exceed lo, got lo %r, hi %r" % (lo, hi))
+    edges = np.linspace(float(lo), float(hi), int(nbins) + 1)
+    if not (np.diff(edges) > 0).all():
+        raise ValueError("lo %r and hi %r are too close for %d distinct float64 edges" % (lo, hi, nbins))
+    return edges
+
+
+def pdf_from_counts(counts, edges):
+    """np.histogram's density=True: counts / (counts.sum() * bin width), float64 (NaN when every count is 0)."""
+    c = np.asarray(counts, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return c / np.diff(edges) / c.sum()
+
+
+def field_pdf(field, lo, hi, nbins=120):
+    """One-point histogram and PDF of a field, replacing np.histogram(x[np.isfinite(x)], bins=np.linspace(lo, hi,
+    nbins + 1), density=True) (reference scripts/utils.py:1248-1274; choosing lo and hi is the caller's business).
+
+    field: any 3-D float32 NumPy array or CUDA tensor.  edges = np.linspace(lo, hi, nbins + 1) in float64, hi > lo,
+    2 <= nbins <= 4096.  A voxel x (float32, widened to float64) falls into bin searchsorted(edges, x, "right") - 1, and
+    x == hi into the last bin: NumPy's rule, so counts equals np.histogram's.  Returns a dict of host objects: edges,
+    centers, pdf (float64), counts (int64), outside (finite voxels beyond the edges) and nonfinite (ints).  pdf = counts /
+    (counts.sum() * bin width).  One pass over the field, integer sums: reproducible bit for bit."""
+    f, count = _onepoint_validate(field, "field_pdf")
+    edges = pdf_edges(lo, hi, nbins)
+    nbins = int(nbins)
+    host = not _is_torch(f)
+    dev = _device() if host else f.device
+    l = _lib.lib()
+    with torch.cuda.device(dev):
+        x = _to_device(f, dev, (torch.float32,))
+        ed = torch.from_numpy(edges).to(dev)
+        cd = torch.zeros(nbins + 2, dtype=torch.int64, device=dev)
+        _lib.check(l.nbe_field_histogram(_ptr(x), count, float(edges[0]), float(edges[-1]), _ptr(ed), nbins, _ptr(cd),
+                                         _stream(dev)))
+        c = cd.cpu().numpy()
+    counts = c[:nbins].copy()
+    return {"edges": edges, "centers": 0.5 * (edges[:-1] + edges[1:]), "counts": counts,
+            "pdf": pdf_from_counts(counts, edges), "outside": int(c[nbins]), "nonfinite": int(c[nbins + 1])}

@@ -20,8 +20,13 @@ Density fields (the fork's DISCO-DJ step, scripts/core.py:447-458): with `--dens
 1-4 = NGP/CIC/TSC/PCS, default 2; `--no-deconvolve` keeps the assignment window; `--boxsize` in Mpc/h, default 1000),
 with `--pk` <output_dir>/emu_pk.npz (k, pk, nmodes), and with `--minkowski` <output_dir>/emu_minkowski.npz
 (thresholds, v0, v1, v2, v3, counts, mean, std: the Minkowski functionals of the painted delta at the 41 default
-thresholds of the standardized field, computed on the device by density.minkowski_functionals).  Painting reads the
-float32 displacement on the device; the saved emu_dis.npy is rounded to --output-precision afterwards.
+thresholds of the standardized field, computed on the device by density.minkowski_functionals).  With `--bispectrum`
+<output_dir>/emu_bispectrum.npz holds density.bispectrum's arrays for the reference's two configurations
+(scripts/utils.py:1314-1399: k1 = k2 = 0.1 and k1 = 0.05, k2 = 0.1 h/Mpc, theta = linspace(0, pi, 25)), keys suffixed
+_cfg1 and _cfg2; with `--onepoint` <output_dir>/emu_onepoint.npz holds mean, std, skewness, kurtosis_excess
+(density.field_statistics) and a 120-bin PDF between the field's minimum and maximum (density.field_pdf: edges, centers,
+counts, pdf, outside, nonfinite).  Painting reads the float32 displacement on the device; the saved emu_dis.npy is
+rounded to --output-precision afterwards.
 
 What differs from the reference: the engine, its weights and its ~100 GB workspace stay resident on the
 GPU for the whole batch, and disk I/O overlaps compute -- the next displacement file is read and the
@@ -165,6 +170,12 @@ def build_parser():
     ap.add_argument('--minkowski', action='store_true', default=argparse.SUPPRESS,
                     help='With --density_res: also write the Minkowski functionals of the density field (standardized, '
                          '41 thresholds in [-3, 3]) to <output_dir>/emu_minkowski.npz')
+    ap.add_argument('--bispectrum', action='store_true', default=argparse.SUPPRESS,
+                    help='With --density_res: also write B and Q(theta) of the density field for k1 = k2 = 0.1 and '
+                         'k1 = 0.05, k2 = 0.1 h/Mpc at 25 angles to <output_dir>/emu_bispectrum.npz')
+    ap.add_argument('--onepoint', action='store_true', default=argparse.SUPPRESS,
+                    help='With --density_res: also write mean, std, skewness, excess kurtosis and a 120-bin PDF of the '
+                         'density field to <output_dir>/emu_onepoint.npz')
     return ap
 
 
@@ -198,6 +209,43 @@ def minkowski_option(args):
     return on
 
 
+BISPECTRUM_CONFIGS = ((0.1, 0.1), (0.05, 0.1))           # (k1, k2) in h/Mpc: reference scripts/utils.py:1314-1399
+BISPECTRUM_KEYS = ('theta', 'k3', 'B', 'Q', 'ntriangles', 'pk', 'k', 'nmodes')
+ONEPOINT_BINS = 120
+
+
+def summary_options(args):
+    """(bispectrum, onepoint): whether --bispectrum / --onepoint were given (read apart from density_options, whose dict
+    they leave as it was)."""
+    on = tuple(bool(getattr(args, name, False)) for name in ('bispectrum', 'onepoint'))
+    for flag, name in zip(on, ('--bispectrum', '--onepoint')):
+        if flag and getattr(args, 'density_res', None) is None:
+            _die(f'{name} needs --density_res')
+    return on
+
+
+def density_summaries(delta, dens, bispec, onepoint):
+    """The arrays of emu_bispectrum.npz and emu_onepoint.npz for the device field `delta` (None where not asked for)."""
+    from .density import bispectrum, field_pdf, field_statistics
+    bk = op = None
+    if bispec:
+        # the reference's mas_for_model (scripts/utils.py:1349): no window for a field that is already deconvolved
+        mas = None if dens['deconvolve'] else dens['worder']
+        bk = {}
+        for i, (k1, k2) in enumerate(BISPECTRUM_CONFIGS, 1):
+            r = bispectrum(delta, boxsize=dens['boxsize'], k1=k1, k2=k2, theta=np.linspace(0.0, np.pi, 25),
+                           mas_worder=mas)
+            bk.update({f'{key}_cfg{i}': r[key] for key in BISPECTRUM_KEYS})
+    if onepoint:
+        import torch
+        lo, hi = (float(v) for v in torch.aminmax(delta))
+        if lo == hi:                                         # a constant field: np.histogram's widening
+            lo, hi = lo - 0.5, hi + 0.5
+        op = dict(field_statistics(delta))
+        op.update(field_pdf(delta, lo=lo, hi=hi, nbins=ONEPOINT_BINS))
+    return bk, op
+
+
 def load_params(path):
     from .nbody_emulator import load_default_parameters
     if path is None:
@@ -224,9 +272,16 @@ def run(args):
     print(f'  Subbox divisions: {args.ndiv}')
     dens = density_options(args)
     mink = minkowski_option(args)
+    bispec, onepoint = summary_options(args)
+    if bispec:
+        for k1, k2 in BISPECTRUM_CONFIGS:                    # density.bispectrum's closure condition, before any work
+            if 2.0 * (k1 + k2) * dens['boxsize'] / (2.0 * np.pi) + 1.5 >= dens['res']:
+                _die(f"--bispectrum: k1 = {k1}, k2 = {k2} h/Mpc do not fit a {dens['res']}^3 mesh of a "
+                     f"{dens['boxsize']} Mpc/h box")
     if dens is not None:
         print(f"  Density: {dens['res']}^3 mesh, worder {dens['worder']}, deconvolve {dens['deconvolve']}, "
-              f"boxsize {dens['boxsize']}, P(k) {dens['pk']}" + (", Minkowski functionals" if mink else ""))
+              f"boxsize {dens['boxsize']}, P(k) {dens['pk']}" + (", Minkowski functionals" if mink else "")
+              + (", bispectrum" if bispec else "") + (", one-point statistics" if onepoint else ""))
     print()
 
     shape = None
@@ -261,6 +316,10 @@ def run(args):
                 mf = extra['mf']
                 np.savez(out_dir / 'emu_minkowski.npz', **{key: mf[key] for key in
                          ('thresholds', 'v0', 'v1', 'v2', 'v3', 'counts', 'mean', 'std')})
+            if extra.get('bk') is not None:
+                np.savez(out_dir / 'emu_bispectrum.npz', **extra['bk'])
+            if extra.get('onepoint') is not None:
+                np.savez(out_dir / 'emu_onepoint.npz', **extra['onepoint'])
 
     def with_density(dis_in, z, Om):
         """process_box on the device, the density field of its float32 displacement, host copies of the fields."""
@@ -276,6 +335,8 @@ def run(args):
             extra['pk'] = power_spectrum(delta, boxsize=dens['boxsize'])
         if mink:
             extra['mf'] = minkowski_functionals(delta, boxsize=dens['boxsize'])
+        if bispec or onepoint:
+            extra['bk'], extra['onepoint'] = density_summaries(delta, dens, bispec, onepoint)
         out_dt = np.dtype(args.output_precision)
         host = tuple(t.cpu().numpy().astype(out_dt, copy=False) for t in (result if args.vel else (result,)))
         return (host if args.vel else host[0]), extra
