@@ -252,6 +252,36 @@ int nbe_paint_mesh(const void* disp, int disp_dtype, const int64_t n[3], const d
                    int worder, int count_atomics, void* mesh, void* stats, void* stream);
 /* mesh (int64, as above) -> delta = rho / rho_mean - 1 (float32), rho_mean = nparticles / (res0 res1 res2) */
 int nbe_mesh_to_delta(const void* mesh, const int64_t res[3], int64_t nparticles, void* delta, void* stream);
+
+/* Per-particle fields: weighted mass assignment in the integer scheme of nbe_paint_mesh.  Channel
+ * c of a quantity has the binary exponent e_c with max |q_c| < 2^e_c; particle p carries V_p = rint(q_p 2^(24 - e_c)),
+ * |V_p| <= 2^24, and a cell holds S = sum of w V_p (int64, two's complement) over the fixed-point weights w of
+ * nbe_paint_mesh.  |S| <= M 2^24 for a cell of mass M units: cells below 2^39 units (2^17 particle masses) cannot overflow. */
+#define NBE_PAINT_MAX_CHANNELS 4
+#define NBE_FIELD_DENSITY 0
+#define NBE_FIELD_MEAN 1
+/* first half of project_field_from_particles (scripts/utils.py:151-183, DISCO-DJ compute_field_quantity_from_particles):
+ * the range of the quantity.  quantity = (nchan, count) float32 / float16; range = (nchan + 1) uint32, zeroed by the
+ * caller: [c] receives the float32 bits of max |q_c| over the finite values, [nchan] the number of non-finite values. */
+int nbe_quantity_range(const void* quantity, int dtype, int nchan, int64_t count, void* range, void* stream);
+/* replaces the particle-to-mesh step of project_field_from_particles (scripts/utils.py:151-183) and of
+ * project_density_slab (scripts/halos.py:468): one read of the particles paints the mass mesh of nbe_paint_mesh (same
+ * units, same bits) and nchan quantity meshes.  disp = (3, N0, N1, N2) or NULL (the undisplaced lattice); quantity =
+ * (nchan, N0, N1, N2), 0 <= nchan <= NBE_PAINT_MAX_CHANNELS (0: masses only); exponents = nchan host ints e_c.  shift =
+ * (N0, N1, N2) or NULL: position along axis shift_axis is i a + psi s + shift * (shift_scale * res / L) in float64
+ * (redshift space: shift = the line-of-sight velocity, shift_scale = length per unit of velocity).  mesh = (res) int64,
+ * qmesh = (nchan, res) int64, both ZEROED by the caller.  stats = 4 int32, zeroed: [0] tiles on the direct path (footprint
+ * beyond the 8192-cell LDS image), [1] particles with a non-finite or out-of-range position, NOT painted; [2] is written
+ * by nbe_mesh_to_field. */
+int nbe_paint_fields(const void* disp, int disp_dtype, const void* quantity, int quantity_dtype, int nchan,
+                     const int exponents[], const void* shift, int shift_dtype, int shift_axis, double shift_scale,
+                     const int64_t n[3], const double boxsize[3], const int64_t res[3], int worder, void* mesh,
+                     void* qmesh, void* stats, void* stream);
+/* second half of project_field_from_particles (normalize_by_density): the meshes of nbe_paint_fields -> field = (nchan,
+ * res) float32, in float64 with one rounding.  NBE_FIELD_MEAN: S 2^(e_c - 46) n_cells / nparticles.  NBE_FIELD_DENSITY:
+ * S 2^(e_c - 24) / M, and `fill` where M = 0.  stats[2] += the cells with M >= 2^39, whose S may have wrapped. */
+int nbe_mesh_to_field(const void* mesh, const void* qmesh, int nchan, const int exponents[], const int64_t res[3],
+                      int64_t nparticles, int mode, double fill, void* field, void* stats, void* stream);
 /* replaces deconvolve_mas_kernel (scripts/utils.py:136-148): in place on the rfft (res0, res1, res2/2+1) complex64 of a
  * mesh, divide by prod_c sinc(pi f_c / res_c)^worder, sinc(x) = sin(x) / x (the window alone, no alias sum) */
 int nbe_deconvolve_mas(void* field, const int64_t res[3], int worder, void* stream);

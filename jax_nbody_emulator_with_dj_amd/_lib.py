@@ -78,6 +78,12 @@ SIGNATURES = {
     "nbe_paint_mesh": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                  C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nbe_mesh_to_delta": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_void_p]),
+    "nbe_quantity_range": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nbe_paint_fields": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p,
+                                   C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                                   C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nbe_mesh_to_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.c_int64,
+                                    C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nbe_deconvolve_mas": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
     "nbe_power_spectrum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nbe_field_moments": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

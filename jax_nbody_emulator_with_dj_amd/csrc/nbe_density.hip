@@ -216,6 +216,217 @@ __global__ void mesh_to_delta_kernel(const long long* __restrict__ mesh, float* 
         out[i] = (float)((double)mesh[i] * scale - 1.0);
 }
 
+// ---- Per-particle fields --------------------------------------------------------------------
+// Weighted mass assignment: besides its unit mass every particle carries up to NBE_PAINT_MAX_CHANNELS quantities, each as
+// an integer V = rint(q 2^(24 - e_c)) with |V| <= 2^24 (e_c: the channel's binary exponent, max |q_c| < 2^e_c, from
+// quantity_range_kernel).  A cell sums w V over its particles in 64-bit integers with the weights w of particle_weights
+// (two's complement: unsigned adds wrap correctly), so the sums are bitwise independent of scheduling, of the path a tile
+// takes and of the other channels.  Positions may be shifted along one axis by a second field (redshift space), and
+// disp == NULL paints the undisplaced lattice.
+//
+// LDS: a tile adds up to 512 * 2^22 * 2^24 = 2^55 to a cell, so the image has 64-bit cells; 8192 of them keep the 64 KiB
+// and the two workgroups per CU of paint_kernel.  The one image is reused pass by pass (the mass, then each channel);
+// positions and the V stay in registers and the weights are recomputed per pass.  A footprint beyond 8192 cells takes the
+// direct path: the same integers into the global meshes, all channels in one sweep over the weights.
+constexpr int kFieldCells = 8192;
+constexpr long long kMassLimit = 1LL << 39;               // a cell at or above it could overflow |S| <= M 2^24 < 2^63
+
+struct FieldArgs {
+    const void* disp;           // (3, N0, N1, N2), or NULL: the undisplaced lattice
+    const void* qty;            // (nchan, N0, N1, N2)
+    const void* shift;          // (N0, N1, N2) added along axis `los` after scaling by vs, or NULL
+    int disp_half, qty_half, shift_half, nchan, los;
+    double vs;                  // mesh cells per unit of the shift field
+    long long n0, n1, n2;
+    double s0, s1, s2;
+    double a0, a1, a2;
+    int r0, r1, r2;
+    int tiles1, tiles2;
+    int qexp[NBE_PAINT_MAX_CHANNELS];   // 24 - e_c
+    unsigned long long* mesh;   // (r0, r1, r2) int64 masses, zeroed by the caller
+    unsigned long long* qmesh;  // (nchan, r0, r1, r2) int64 sums of w V, zeroed by the caller
+    int* stats;                 // [0] tiles on the direct path, [1] particles with a non-finite or huge position
+};
+
+__device__ inline float load_real(const void* p, int half, long long i) {
+    return half ? (float)((const _Float16*)p)[i] : ((const float*)p)[i];
+}
+
+template <int P>
+__global__ __launch_bounds__(kPaintThreads) void paint_field_kernel(FieldArgs A) {
+    __shared__ unsigned long long img[kFieldCells];
+    __shared__ int lo[3], hi[3];
+    const int tid = threadIdx.x;
+    const long long tile = blockIdx.x;
+    const int t2 = (int)(tile % A.tiles2);
+    const long long rest = tile / A.tiles2;
+    const int t1 = (int)(rest % A.tiles1), t0 = (int)(rest / A.tiles1);
+    if (tid < 3) { lo[tid] = INT_MAX; hi[tid] = INT_MIN; }
+    __syncthreads();
+
+    const long long ncell = A.n0 * A.n1 * A.n2;
+    const int nchan = A.nchan;
+    static_assert(kPerThread == 2, "the scatter steps below name both particles of a thread");
+    double u[kPerThread][3];
+    int V[kPerThread][NBE_PAINT_MAX_CHANNELS];
+    bool live[kPerThread];
+    int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
+#pragma unroll
+    for (int k = 0; k < kPerThread; ++k) {
+        const int l = tid + k * kPaintThreads;
+        const long long i0 = t0 * kTile + (l >> 6), i1 = t1 * kTile + ((l >> 3) & 7), i2 = t2 * kTile + (l & 7);
+        live[k] = i0 < A.n0 && i1 < A.n1 && i2 < A.n2;
+#pragma unroll
+        for (int c = 0; c < NBE_PAINT_MAX_CHANNELS; ++c) V[k][c] = 0;
+        if (!live[k]) continue;
+        const long long idx = (i0 * A.n1 + i1) * A.n2 + i2;
+        float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f;
+        if (A.disp) {
+            p0 = load_real(A.disp, A.disp_half, idx);
+            p1 = load_real(A.disp, A.disp_half, ncell + idx);
+            p2 = load_real(A.disp, A.disp_half, 2 * ncell + idx);
+        }
+        // as paint_kernel; along the line of sight i a + psi s + v vs, all in float64
+        u[k][0] = (double)i0 * A.a0 + (double)p0 * A.s0;
+        u[k][1] = (double)i1 * A.a1 + (double)p1 * A.s1;
+        u[k][2] = (double)i2 * A.a2 + (double)p2 * A.s2;
+        if (A.shift) {
+            const double d = (double)load_real(A.shift, A.shift_half, idx) * A.vs;
+            if (A.los == 0) u[k][0] += d;
+            else if (A.los == 1) u[k][1] += d;
+            else u[k][2] += d;
+        }
+        if (!(fabs(u[k][0]) < kUMax && fabs(u[k][1]) < kUMax && fabs(u[k][2]) < kUMax)) {
+            live[k] = false;
+            atomicAdd(&A.stats[1], 1);
+            continue;
+        }
+#pragma unroll
+        for (int c = 0; c < NBE_PAINT_MAX_CHANNELS; ++c)
+            if (c < nchan)
+                V[k][c] = (int)rint(ldexp((double)load_real(A.qty, A.qty_half, c * ncell + idx), A.qexp[c]));
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int j = (int)floor(u[k][c] + 1.0 - 0.5 * P);
+            mn[c] = min(mn[c], j);
+            mx[c] = max(mx[c], j + P - 1);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (mn[c] != INT_MAX) { atomicMin(&lo[c], mn[c]); atomicMax(&hi[c], mx[c]); }
+    }
+    __syncthreads();
+    if (hi[0] < lo[0]) return;                             // no live particle in this tile (uniform)
+
+    const long long e0 = (long long)hi[0] - lo[0] + 1, e1 = (long long)hi[1] - lo[1] + 1,
+                    e2 = (long long)hi[2] - lo[2] + 1;
+    const int r0 = A.r0, r1 = A.r1, r2 = A.r2;
+    const long long cells = (long long)r0 * r1 * r2;
+    // (each extent is tested first: the product of three extents of up to 2^31 cells does not fit 64 bits)
+    if (e0 > kFieldCells || e1 > kFieldCells || e2 > kFieldCells || e0 * e1 * e2 > kFieldCells) {
+        // footprint larger than the image: the same integers straight into the meshes
+        if (tid == 0) atomicAdd(&A.stats[0], 1);
+        auto direct = [&](const double* uk, const int* Vk) {
+            int j0[3];
+            particle_weights<P>(uk, j0, [&](int a, int b, int c, unsigned q) {
+                const long long g = ((long long)wrap(j0[0] + a, r0) * r1 + wrap(j0[1] + b, r1)) * r2 + wrap(j0[2] + c, r2);
+                atomicAdd(&A.mesh[g], (unsigned long long)q);
+                if (0 < nchan && Vk[0]) atomicAdd(&A.qmesh[g], (unsigned long long)((long long)q * Vk[0]));
+                if (1 < nchan && Vk[1]) atomicAdd(&A.qmesh[cells + g], (unsigned long long)((long long)q * Vk[1]));
+                if (2 < nchan && Vk[2]) atomicAdd(&A.qmesh[2 * cells + g], (unsigned long long)((long long)q * Vk[2]));
+                if (3 < nchan && Vk[3]) atomicAdd(&A.qmesh[3 * cells + g], (unsigned long long)((long long)q * Vk[3]));
+            });
+        };
+        if (live[0]) direct(u[0], V[0]);
+        if (live[1]) direct(u[1], V[1]);
+        return;
+    }
+
+    const int E1 = (int)e1, E2 = (int)e2, vol = (int)(e0 * e1 * e2);
+    const int l0 = lo[0], l1 = lo[1], l2 = lo[2];
+    for (int pass = 0; pass <= nchan; ++pass) {            // the mass, then one channel per pass through the one image
+        for (int i = tid; i < vol; i += kPaintThreads) img[i] = 0ull;
+        __syncthreads();
+        auto scatter = [&](double* uk, const int* Vk) {
+            const int v = pass == 0 ? 1 : pass == 1 ? Vk[0] : pass == 2 ? Vk[1] : pass == 3 ? Vk[2] : Vk[3];
+            if (!v) return;
+            // keeps the weights from being computed ahead of the pass loop and held in ~2 P^3 registers
+            asm volatile("" : "+v"(uk[0]), "+v"(uk[1]), "+v"(uk[2]));
+            int j0[3];
+            particle_weights<P>(uk, j0, [&](int a, int b, int c, unsigned q) {
+                atomicAdd(&img[((j0[0] + a - l0) * E1 + (j0[1] + b - l1)) * E2 + (j0[2] + c - l2)],
+                          (unsigned long long)((long long)q * v));
+            });
+        };
+        if (live[0]) scatter(u[0], V[0]);
+        if (live[1]) scatter(u[1], V[1]);
+        __syncthreads();
+        unsigned long long* dst = pass == 0 ? A.mesh : A.qmesh + (pass - 1) * cells;
+        for (int i = tid; i < vol; i += kPaintThreads) {
+            const unsigned long long v = img[i];
+            if (!v) continue;
+            const int c2 = i % E2, r = i / E2, c1 = r % E1, c0 = r / E1;
+            const long long g = ((long long)wrap(l0 + c0, r0) * r1 + wrap(l1 + c1, r1)) * r2 + wrap(l2 + c2, r2);
+            atomicAdd(&dst[g], v);
+        }
+        __syncthreads();
+    }
+}
+
+// per channel: the largest |q| as float bits (unsigned order = float order for non-negative floats; atomicMax commutes)
+// in range[c], and the number of non-finite values of all channels in range[nchan]
+__global__ __launch_bounds__(256) void quantity_range_kernel(const void* q, int half, int nchan, long long count,
+                                                             unsigned* __restrict__ range) {
+    __shared__ unsigned smax[NBE_PAINT_MAX_CHANNELS], sbad;
+    if (threadIdx.x < NBE_PAINT_MAX_CHANNELS) smax[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) sbad = 0u;
+    __syncthreads();
+    unsigned bad = 0;
+    for (int c = 0; c < nchan; ++c) {
+        unsigned m = 0u;
+        for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < count; i += (long long)gridDim.x * blockDim.x) {
+            const float v = load_real(q, half, c * count + i);
+            if (!isfinite(v)) ++bad;
+            else m = max(m, __float_as_uint(fabsf(v)));
+        }
+        if (m) atomicMax(&smax[c], m);
+    }
+    if (bad) atomicAdd(&sbad, bad);
+    __syncthreads();
+    if ((int)threadIdx.x < nchan && smax[threadIdx.x]) atomicMax(&range[threadIdx.x], smax[threadIdx.x]);
+    if (threadIdx.x == 0 && sbad) atomicAdd(&range[nchan], sbad);
+}
+
+struct ToFieldArgs {
+    const long long* mesh;
+    const long long* qmesh;
+    float* out;
+    long long cells;
+    int nchan, mode;
+    int e[NBE_PAINT_MAX_CHANNELS];
+    double ratio;               // n_cells / N_p
+    float fill;
+    int* stats;                 // [2] cells whose mass reaches kMassLimit
+};
+
+// float64 throughout, one rounding to float32: mean S 2^(e - 46) n_cells / N_p, density S 2^(e - 24) / M (fill at M = 0)
+__global__ void mesh_to_field_kernel(ToFieldArgs A) {
+    int over = 0;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < A.cells; i += (long long)gridDim.x * blockDim.x) {
+        const long long M = A.mesh[i];
+        if (M >= kMassLimit) ++over;
+        for (int c = 0; c < A.nchan; ++c) {
+            const double S = (double)A.qmesh[c * A.cells + i];
+            float v;
+            if (A.mode == NBE_FIELD_MEAN) v = (float)(ldexp(S, A.e[c] - 46) * A.ratio);
+            else v = M == 0 ? A.fill : (float)(ldexp(S, A.e[c] - 24) / (double)M);
+            A.out[c * A.cells + i] = v;
+        }
+    }
+    if (over) atomicAdd(&A.stats[2], over);
+}
+
 // frequency index of position i on an axis of n points (numpy.fft.fftfreq * n)
 __device__ inline long long freq(long long i, long long n) { return i <= n / 2 ? i : i - n; }
 
@@ -890,6 +1101,103 @@ int nbe_mesh_to_delta(const void* mesh, const int64_t res[3], int64_t nparticles
     hipLaunchKernelGGL(mesh_to_delta_kernel, dim3(grid_for(cells, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const long long*)mesh, (float*)delta, cells, scale);
     return launched("nbe_mesh_to_delta");
+}
+
+int nbe_quantity_range(const void* quantity, int dtype, int nchan, int64_t count, void* range, void* stream) {
+    if (!quantity || !range) return fail("nbe_quantity_range: NULL argument");
+    if (dtype != NBE_F32 && dtype != NBE_F16) return fail("nbe_quantity_range: dtype %d unsupported", dtype);
+    if (nchan < 1 || nchan > NBE_PAINT_MAX_CHANNELS)
+        return fail("nbe_quantity_range: %d channels unsupported (1 .. %d)", nchan, NBE_PAINT_MAX_CHANNELS);
+    if (count < 1) return fail("nbe_quantity_range: bad size");
+    const int g = grid_for(count, 256 * 8);
+    hipLaunchKernelGGL(quantity_range_kernel, dim3(g < 2048 ? g : 2048), dim3(256), 0, (hipStream_t)stream, quantity,
+                       dtype == NBE_F16, nchan, (long long)count, (unsigned*)range);
+    return launched("nbe_quantity_range");
+}
+
+int nbe_paint_fields(const void* disp, int disp_dtype, const void* quantity, int quantity_dtype, int nchan,
+                     const int exponents[], const void* shift, int shift_dtype, int shift_axis, double shift_scale,
+                     const int64_t n[3], const double boxsize[3], const int64_t res[3], int worder, void* mesh,
+                     void* qmesh, void* stats, void* stream) {
+    if (!mesh || !stats || !n || !boxsize || !res) return fail("nbe_paint_fields: NULL argument");
+    if (nchan < 0 || nchan > NBE_PAINT_MAX_CHANNELS)
+        return fail("nbe_paint_fields: %d channels unsupported (0 .. %d)", nchan, NBE_PAINT_MAX_CHANNELS);
+    if (nchan && (!quantity || !qmesh || !exponents)) return fail("nbe_paint_fields: NULL quantity argument");
+    if ((disp && disp_dtype != NBE_F32 && disp_dtype != NBE_F16) ||
+        (nchan && quantity_dtype != NBE_F32 && quantity_dtype != NBE_F16) ||
+        (shift && shift_dtype != NBE_F32 && shift_dtype != NBE_F16))
+        return fail("nbe_paint_fields: dtype unsupported (disp %d, quantity %d, shift %d)", disp_dtype, quantity_dtype,
+                    shift_dtype);
+    if (shift && (shift_axis < 0 || shift_axis > 2 || !std::isfinite(shift_scale)))
+        return fail("nbe_paint_fields: bad shift (axis %d, scale %g)", shift_axis, shift_scale);
+    if (worder < 1 || worder > 4) return fail("nbe_paint_fields: worder %d not in 1..4", worder);
+    for (int c = 0; c < 3; ++c) {
+        if (n[c] < 1 || res[c] < 1 || res[c] > (1 << 20) || !(boxsize[c] > 0.0) || !std::isfinite(boxsize[c]))
+            return fail("nbe_paint_fields: bad geometry on axis %d (n %lld, res %lld, boxsize %g)", c, (long long)n[c],
+                        (long long)res[c], boxsize[c]);
+    }
+    FieldArgs A;
+    A.disp = disp;
+    A.qty = quantity;
+    A.shift = shift;
+    A.disp_half = disp_dtype == NBE_F16;
+    A.qty_half = quantity_dtype == NBE_F16;
+    A.shift_half = shift_dtype == NBE_F16;
+    A.nchan = nchan;
+    A.los = shift ? shift_axis : 0;
+    A.n0 = n[0]; A.n1 = n[1]; A.n2 = n[2];
+    A.s0 = res[0] / boxsize[0]; A.s1 = res[1] / boxsize[1]; A.s2 = res[2] / boxsize[2];
+    A.a0 = (double)res[0] / n[0]; A.a1 = (double)res[1] / n[1]; A.a2 = (double)res[2] / n[2];
+    A.vs = shift ? shift_scale * (res[A.los] / boxsize[A.los]) : 0.0;
+    A.r0 = (int)res[0]; A.r1 = (int)res[1]; A.r2 = (int)res[2];
+    for (int c = 0; c < NBE_PAINT_MAX_CHANNELS; ++c) {
+        A.qexp[c] = 0;
+        if (c < nchan) {
+            if (exponents[c] < -200 || exponents[c] > 200)
+                return fail("nbe_paint_fields: exponent %d of channel %d out of range", exponents[c], c);
+            A.qexp[c] = 24 - exponents[c];
+        }
+    }
+    const long long tl0 = (n[0] + kTile - 1) / kTile;
+    A.tiles1 = (int)((n[1] + kTile - 1) / kTile);
+    A.tiles2 = (int)((n[2] + kTile - 1) / kTile);
+    A.mesh = (unsigned long long*)mesh;
+    A.qmesh = (unsigned long long*)qmesh;
+    A.stats = (int*)stats;
+    const long long tiles = tl0 * A.tiles1 * A.tiles2;
+    if (tiles > INT_MAX) return fail("nbe_paint_fields: %lld tiles exceed one launch", tiles);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)tiles), block(kPaintThreads);
+    switch (worder) {
+        case 1: hipLaunchKernelGGL(paint_field_kernel<1>, grid, block, 0, s, A); break;
+        case 2: hipLaunchKernelGGL(paint_field_kernel<2>, grid, block, 0, s, A); break;
+        case 3: hipLaunchKernelGGL(paint_field_kernel<3>, grid, block, 0, s, A); break;
+        default: hipLaunchKernelGGL(paint_field_kernel<4>, grid, block, 0, s, A); break;
+    }
+    return launched("nbe_paint_fields");
+}
+
+int nbe_mesh_to_field(const void* mesh, const void* qmesh, int nchan, const int exponents[], const int64_t res[3],
+                      int64_t nparticles, int mode, double fill, void* field, void* stats, void* stream) {
+    if (!mesh || !qmesh || !exponents || !res || !field || !stats) return fail("nbe_mesh_to_field: NULL argument");
+    if (nchan < 1 || nchan > NBE_PAINT_MAX_CHANNELS)
+        return fail("nbe_mesh_to_field: %d channels unsupported (1 .. %d)", nchan, NBE_PAINT_MAX_CHANNELS);
+    if (mode != NBE_FIELD_DENSITY && mode != NBE_FIELD_MEAN) return fail("nbe_mesh_to_field: mode %d unknown", mode);
+    if (nparticles < 1 || res[0] < 1 || res[1] < 1 || res[2] < 1) return fail("nbe_mesh_to_field: bad sizes");
+    if (!std::isfinite(fill)) return fail("nbe_mesh_to_field: fill is not finite");
+    ToFieldArgs A;
+    A.mesh = (const long long*)mesh;
+    A.qmesh = (const long long*)qmesh;
+    A.out = (float*)field;
+    A.cells = (long long)res[0] * res[1] * res[2];
+    A.nchan = nchan;
+    A.mode = mode;
+    for (int c = 0; c < NBE_PAINT_MAX_CHANNELS; ++c) A.e[c] = c < nchan ? exponents[c] : 0;
+    A.ratio = (double)A.cells / (double)nparticles;
+    A.fill = (float)fill;
+    A.stats = (int*)stats;
+    hipLaunchKernelGGL(mesh_to_field_kernel, dim3(grid_for(A.cells, 256)), dim3(256), 0, (hipStream_t)stream, A);
+    return launched("nbe_mesh_to_field");
 }
 
 int nbe_deconvolve_mas(void* field, const int64_t res[3], int worder, void* stream) {

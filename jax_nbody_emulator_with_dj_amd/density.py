@@ -10,6 +10,8 @@ assignment window (`scripts/utils.py:136-148`) and measures P(k) (`scripts/utils
     k, pk, nmodes = power_spectrum(delta, boxsize=1000.0)
     k, pk, nmodes = power_spectrum(delta_emu, boxsize=1000.0, other=delta_lpt)     # cross spectrum Re<a b*>
     delta_c = deconvolve_mas(delta, worder=2)
+    vmesh = paint_field(displacement, velocity, boxsize=1000.0, res=512)     # mass-weighted mean velocity, (3, res...)
+    delta_s = paint_density(displacement, res=512, velocity=velocity, los=2, velocity_to_length=rsd_factor(z, Om))
     mf = minkowski_functionals(delta, boxsize=1000.0)    # v0 .. v3 at 41 thresholds of the standardized field
     bk = bispectrum(delta, boxsize=1000.0, k1=0.1, k2=0.1, theta=np.linspace(0, np.pi, 25))    # B, Q, ntriangles, ...
     st = field_statistics(delta)                         # mean, std, skewness, kurtosis_excess
@@ -26,6 +28,11 @@ Conventions (as DISCO-DJ / Pylians and the lattice of `scripts/halos.py:394-403`
 - Masses are summed in fixed point (units of 2^-22 particle masses, 64-bit integers): the painted field is bitwise
   reproducible, each particle adds exactly its unit mass, and every cell is within 2^-22 per contributing particle of the
   exact float64 sum before the conversion to float32.
+- `paint_field` (reference `scripts/utils.py:151-183`, project_field_from_particles) assigns a per-particle quantity with
+  the same weights: every value is carried as an integer of 25 bits relative to its channel's largest magnitude and the
+  sums are 64-bit integers, so the fields are bitwise reproducible too (its docstring has the arithmetic).  `velocity`,
+  `los` and `velocity_to_length` move the particles along one axis first: redshift space for
+  velocity_to_length = `rsd_factor(z, Om)`.
 - Deconvolution divides the rfft of the mesh by prod_c sinc(k_c L_c / (2 res_c))^worder, sinc(x) = sin(x) / x (the
   window alone, no alias sum).
 - `power_spectrum` uses the unnormalised forward FFT: P = |delta_k|^2 L^3 / n^6.  Shell b = 1 .. n/2 holds the modes
@@ -56,7 +63,7 @@ except Exception:  # pragma: no cover
     torch = None
 
 __all__ = ["paint_density", "deconvolve_mas", "power_spectrum", "minkowski_functionals", "bispectrum",
-           "field_statistics", "field_pdf"]
+           "field_statistics", "field_pdf", "paint_field", "rsd_factor"]
 
 WORDERS = {1: "NGP", 2: "CIC", 3: "TSC", 4: "PCS"}
 _UNIT = 2.0 ** 22           # fixed-point units per particle mass (include/nbe.h, nbe_paint_mesh)
@@ -71,6 +78,8 @@ _BK_PARTIALS = 2048
 _MOMENT4_WORDS = 6148           # include/nbe.h: NBE_MOMENTS4_WORDS, NBE_PDF_MAX_BINS, NBE_ONEPOINT_MAX_VOXELS
 _PDF_MAX_BINS = 4096
 _ONEPOINT_MAX = 1 << 40
+_MAX_CHANNELS = 4               # include/nbe.h: NBE_PAINT_MAX_CHANNELS, NBE_FIELD_DENSITY, NBE_FIELD_MEAN
+_NORMALIZE = {"density": 0, "mean": 1}
 
 
 def _is_torch(x):
@@ -185,24 +194,211 @@ def _deconvolve(delta, worder):
     return torch.fft.irfftn(fk, s=res).contiguous()
 
 
-def paint_density(displacement, boxsize=1000.0, res=512, worder=2, deconvolve=True):
+def _validate_shift(velocity, los, velocity_to_length, n, kind_of, what):
+    """The line-of-sight arguments: (velocity array or None, los, velocity_to_length as a float or None)."""
+    if isinstance(los, (bool, np.bool_)) or not isinstance(los, numbers.Integral) or int(los) not in (0, 1, 2):
+        raise ValueError("los must be the array axis 0, 1 or 2, got %r" % (los,))
+    if velocity is None:
+        return None, int(los), None
+    v = _check_array(velocity, "velocity")
+    if tuple(v.shape) not in ((3,) + tuple(n), tuple(n)):
+        raise ValueError("velocity must have shape %s or %s, got %s" % ((3,) + tuple(n), tuple(n), tuple(v.shape)))
+    if _dtype_name(v) not in ("float32", "float16"):
+        raise ValueError("velocity must be float32 or float16, got %s" % _dtype_name(v))
+    _same_kind(kind_of, v, what, "velocity")
+    f = velocity_to_length
+    if f is None:
+        raise ValueError("velocity_to_length is required with a velocity (rsd_factor(z, Om) for redshift space)")
+    if isinstance(f, (bool, np.bool_)) or not isinstance(f, numbers.Real) or not np.isfinite(float(f)):
+        raise ValueError("velocity_to_length must be a finite number, got %r" % (f,))
+    return v, int(los), float(f)
+
+
+def _same_kind(a, b, name_a, name_b):
+    if _is_torch(a) != _is_torch(b) or (_is_torch(a) and a.device != b.device):
+        raise ValueError("%s and %s must both be NumPy arrays or both tensors on one device" % (name_a, name_b))
+
+
+def _validate_field(displacement, quantity, boxsize, res, worder, normalize, fill, velocity, los, velocity_to_length):
+    q = _check_array(quantity, "quantity")
+    if q.ndim not in (3, 4) or min(q.shape) < 1 or (q.ndim == 4 and q.shape[0] > _MAX_CHANNELS):
+        raise ValueError("quantity must have shape (N0, N1, N2) or (C, N0, N1, N2) with 1 <= C <= %d, got %s"
+                         % (_MAX_CHANNELS, tuple(q.shape)))
+    if _dtype_name(q) not in ("float32", "float16"):
+        raise ValueError("quantity must be float32 or float16, got %s" % _dtype_name(q))
+    n = tuple(int(v) for v in q.shape[-3:])
+    if displacement is None:
+        x, boxsize, res, worder = None, _triple(boxsize, "boxsize", "a length"), _triple(res, "res", "an int"), \
+            _check_worder(worder)
+    else:
+        x, boxsize, res, worder = _validate_paint(displacement, boxsize, res, worder)
+        if tuple(x.shape[1:]) != n:
+            raise ValueError("quantity must have the lattice shape %s of the displacement, got %s"
+                             % (tuple(x.shape[1:]), tuple(q.shape)))
+        _same_kind(x, q, "displacement", "quantity")
+    if normalize not in _NORMALIZE:
+        raise ValueError("normalize must be 'density' or 'mean', got %r" % (normalize,))
+    if isinstance(fill, (bool, np.bool_)) or not isinstance(fill, numbers.Real) or not np.isfinite(float(fill)):
+        raise ValueError("fill must be a finite number, got %r" % (fill,))
+    v, los, f = _validate_shift(velocity, los, velocity_to_length, n, q, "quantity")
+    return x, q, v, los, f, n, boxsize, res, worder
+
+
+def _paint_fields(x, q, v, los, scale, n, boxsize, res, worder, normalize="density", fill=0.0, want_delta=False):
+    """Device work of paint_field and of paint_density with a velocity.  x: contiguous CUDA (3,) + n tensor or None (the
+    lattice); q: contiguous (C,) + n tensor or None (masses only); v: contiguous n tensor (the line-of-sight component) or
+    None.  Returns (field (C,) + res or None, delta or None, stats): stats[0] tiles on the direct path, stats[1]
+    particles not painted, stats[2] cells at the overflow limit.  Raises NBEError for a non-finite quantity."""
+    l = _lib.lib()
+    dev = (q if q is not None else x).device
+    half = lambda t: 1 if t is not None and t.dtype == torch.float16 else 0
+    nchan = 0 if q is None else int(q.shape[0])
+    count = n[0] * n[1] * n[2]
+    with torch.cuda.device(dev):
+        s = _stream(dev)
+        exps = (C.c_int * _MAX_CHANNELS)()
+        if nchan:
+            rng = torch.zeros(nchan + 1, dtype=torch.int32, device=dev)
+            _lib.check(l.nbe_quantity_range(_ptr(q), half(q), nchan, count, _ptr(rng), s))
+            r = rng.cpu().numpy()
+            if int(r[nchan]):
+                raise NBEError("paint_field: %d value(s) of the quantity are not finite" % int(r[nchan].view(np.uint32)))
+            amax = r[:nchan].view(np.float32).astype(np.float64)
+            for c, e in enumerate(np.frexp(amax)[1]):             # A_c = m 2^e, m in [0.5, 1): A_c < 2^e; 0 for A_c = 0
+                exps[c] = int(e)
+        mesh = torch.zeros(res, dtype=torch.int64, device=dev)
+        qmesh = torch.zeros((nchan,) + tuple(res), dtype=torch.int64, device=dev) if nchan else None
+        stats = torch.zeros(4, dtype=torch.int32, device=dev)
+        _lib.check(l.nbe_paint_fields(_ptr(x) if x is not None else None, half(x), _ptr(q) if nchan else None, half(q),
+                                      nchan, exps, _ptr(v) if v is not None else None, half(v), los,
+                                      float(scale) if v is not None else 0.0, _i64(n), (C.c_double * 3)(*boxsize),
+                                      _i64(res), worder, _ptr(mesh), _ptr(qmesh) if nchan else None, _ptr(stats), s))
+        field = delta = None
+        if nchan:
+            field = torch.empty((nchan,) + tuple(res), dtype=torch.float32, device=dev)
+            _lib.check(l.nbe_mesh_to_field(_ptr(mesh), _ptr(qmesh), nchan, exps, _i64(res), count, _NORMALIZE[normalize],
+                                           float(fill), _ptr(field), _ptr(stats), s))
+        if want_delta:
+            delta = torch.empty(res, dtype=torch.float32, device=dev)
+            _lib.check(l.nbe_mesh_to_delta(_ptr(mesh), _i64(res), count, _ptr(delta), s))
+    return field, delta, stats
+
+
+def _los_component(v, los, n):
+    """The contiguous (N0, N1, N2) line-of-sight component of a device velocity."""
+    return (v[los] if v.ndim == 4 else v).contiguous()
+
+
+def _check_stats(stats, what, overflow):
+    st = stats.cpu().tolist()
+    if st[1]:
+        raise NBEError("%s: %d particle(s) have a non-finite or out-of-range position" % (what, st[1]))
+    if overflow and st[2]:
+        raise NBEError("%s: %d cell(s) hold 2^17 particle masses or more (2^39 mass units), beyond which the 64-bit "
+                       "sums of a quantity can overflow" % (what, st[2]))
+
+
+def paint_density(displacement, boxsize=1000.0, res=512, worder=2, deconvolve=True, velocity=None, los=2,
+                  velocity_to_length=None):
     """Mass assignment of the displaced lattice onto a periodic mesh (reference scripts/core.py:449,
     dj.get_delta_from_psi(psi, method="pm", res, worder, deconvolve)).
 
     displacement: (3, N0, N1, N2) float32 / float16, NumPy array or CUDA torch tensor (process_box's output).
     boxsize: L (scalar or 3-tuple, units of the displacement).  res: mesh size (int or 3-tuple; any value >= 1).
     worder: 1 NGP, 2 CIC, 3 TSC, 4 PCS.  deconvolve: divide by the assignment window (deconvolve_mas).
+    velocity, los, velocity_to_length: with a velocity ((3, N0, N1, N2), of which component `los` is read, or
+    (N0, N1, N2); float32 / float16, same kind and device as the displacement) every particle is moved by
+    velocity_to_length * v along array axis los (0, 1 or 2) before it is painted: the plane-parallel redshift-space
+    density for velocity_to_length = rsd_factor(z, Om).  The position along los is i a + psi s + v vs in float64 (mesh
+    units; vs = velocity_to_length res / L).  Without a velocity the call is what it was before these arguments existed.
     Returns delta = rho / rho_mean - 1, float32, shape res; NumPy for NumPy input, a CUDA tensor on the input's device
-    for tensor input.  Raises NBEError if a displacement is not finite (those particles could not be painted).
+    for tensor input.  Raises NBEError if a displacement or velocity is not finite (those particles could not be painted).
     See the module docstring for the conventions."""
     x, boxsize, res, worder = _validate_paint(displacement, boxsize, res, worder)
+    n = tuple(int(d) for d in x.shape[1:])
+    v, los, f = _validate_shift(velocity, los, velocity_to_length, n, x, "displacement")
     host = not _is_torch(x)
-    xd = _to_device(x, _device() if host else x.device, (torch.float32, torch.float16) if torch else ())
-    delta, stats = _paint(xd, boxsize, res, worder, bool(deconvolve))
-    bad = int(stats[1].item())
-    if bad:
-        raise NBEError("paint_density: %d particle(s) have a non-finite or out-of-range position" % bad)
+    dtypes = (torch.float32, torch.float16) if torch else ()
+    xd = _to_device(x, _device() if host else x.device, dtypes)
+    if v is None:
+        delta, stats = _paint(xd, boxsize, res, worder, bool(deconvolve))
+        bad = int(stats[1].item())
+        if bad:
+            raise NBEError("paint_density: %d particle(s) have a non-finite or out-of-range position" % bad)
+        return delta.cpu().numpy() if host else delta
+    vd = _los_component(_to_device(v, xd.device, dtypes), los, n)
+    _, delta, stats = _paint_fields(xd, None, vd, los, f, n, boxsize, res, worder, want_delta=True)
+    _check_stats(stats, "paint_density", False)
+    if deconvolve:
+        with torch.cuda.device(xd.device):
+            delta = _deconvolve(delta, worder)
     return delta.cpu().numpy() if host else delta
+
+
+def paint_field(displacement, quantity, boxsize=1000.0, res=512, worder=2, normalize="density", deconvolve=False,
+                fill=0.0, return_delta=False, velocity=None, los=2, velocity_to_length=None):
+    """Assign a per-particle quantity to a periodic mesh with the weights of paint_density (reference
+    scripts/utils.py:151-183, project_field_from_particles: DISCO-DJ compute_field_quantity_from_particles(pos, quantity,
+    method="pm", res, worder, deconvolve, normalize_by_density=True); scripts/halos.py:468, project_density_slab).
+
+    displacement: as paint_density, or None for the undisplaced lattice (the reference's use: a field of the particle grid
+    carried to another mesh); the lattice shape then comes from `quantity`.
+    quantity: (N0, N1, N2) or (C, N0, N1, N2), 1 <= C <= 4, float32 / float16, same kind (NumPy or tensor) and device as
+    the displacement.  process_box's velocity is a valid quantity as it stands.
+    normalize: "density" gives sum(w q) / sum(w) per cell, the mass-weighted mean (normalize_by_density=True), and `fill`
+    in cells without mass.  "mean" gives sum(w q) / (N_p / n_cells), the momentum-like field (1 + delta) q.
+    deconvolve: divide every channel of the finished field by the assignment window (deconvolve_mas).  DISCO-DJ is not
+    available where this library is developed, so whether it deconvolves the numerator and the density separately before
+    it divides them under normalize_by_density cannot be pinned; here the window is divided out of the ratio.
+    return_delta: also return the density contrast of the same pass, bit for bit paint_density(..., deconvolve=False).
+    velocity, los, velocity_to_length: the line-of-sight shift of paint_density.
+    Returns the field, float32, shape res or (C,) + res (and delta with return_delta): NumPy for NumPy input, CUDA tensors
+    on the input's device for tensor input, on torch's current stream.
+
+    Arithmetic.  The mass of a cell is paint_density's integer M (2^-22 particle masses).  For channel c let A_c = max |q_c|
+    and e_c the binary exponent with A_c < 2^e_c.  Particle p carries V_p = rint(q_p 2^(24 - e_c)), |V_p| <= 2^24: a
+    float32 value in the channel's top binade is exact, smaller ones are rounded at 2^(e_c - 25).  The cell holds S = sum
+    of w V_p in a 64-bit integer, w the integer weights of the mass.  In float64, rounded once to float32: "mean" is
+    S 2^(e_c - 46) n_cells / N_p, "density" is S 2^(e_c - 24) / M.  Before that rounding the numerator of a cell of mass m
+    (particle masses) is within 2^-22 sum |q_p| + m 2^(e_c - 25) of the exact sum.  Integer adds commute: the result is
+    the same bits on every call, whichever path a tile takes on the device, and whatever the other channels are; a
+    float16 input gives the bits of its float32 widening.
+
+    Raises NBEError for a non-finite position, velocity or quantity value, and when a cell holds 2^17 particle masses or
+    more: |S| <= M 2^24 stays below 2^63 only for M < 2^39 units."""
+    x, q, v, los, f, n, boxsize, res, worder = _validate_field(displacement, quantity, boxsize, res, worder, normalize,
+                                                               fill, velocity, los, velocity_to_length)
+    host = not _is_torch(q)
+    dev = _device() if host else q.device
+    dtypes = (torch.float32, torch.float16) if torch else ()
+    xd = None if x is None else _to_device(x, dev, dtypes)
+    qd = _to_device(q, dev, dtypes)
+    single = qd.ndim == 3
+    if single:
+        qd = qd[None]
+    vd = None if v is None else _los_component(_to_device(v, dev, dtypes), los, n)
+    field, delta, stats = _paint_fields(xd, qd, vd, los, f, n, boxsize, res, worder, normalize, float(fill),
+                                        bool(return_delta))
+    _check_stats(stats, "paint_field", True)
+    if deconvolve:
+        with torch.cuda.device(dev):
+            field = torch.stack([_deconvolve(field[c], worder) for c in range(field.shape[0])])
+    if single:
+        field = field[0]
+    if host:
+        field = field.cpu().numpy()
+        delta = delta.cpu().numpy() if delta is not None else None
+    return (field, delta) if return_delta else field
+
+
+def rsd_factor(z, Om):
+    """(1 + z) / H(z) in (Mpc/h) per (km/s): the comoving displacement of a proper peculiar velocity along the line of
+    sight, s = x + v_los (1 + z) / H(z), with cosmology.hubble_rate.  A Python float."""
+    from .cosmology import hubble_rate
+    for name, val in (("z", z), ("Om", Om)):
+        if isinstance(val, (bool, np.bool_)) or not isinstance(val, numbers.Real) or not np.isfinite(float(val)):
+            raise ValueError("%s must be a finite number, got %r" % (name, val))
+    return (1.0 + float(z)) / float(hubble_rate(float(z), float(Om)))
 
 
 def deconvolve_mas(delta, worder=2):

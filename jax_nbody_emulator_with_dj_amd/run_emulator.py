@@ -25,7 +25,11 @@ thresholds of the standardized field, computed on the device by density.minkowsk
 (scripts/utils.py:1314-1399: k1 = k2 = 0.1 and k1 = 0.05, k2 = 0.1 h/Mpc, theta = linspace(0, pi, 25)), keys suffixed
 _cfg1 and _cfg2; with `--onepoint` <output_dir>/emu_onepoint.npz holds mean, std, skewness, kurtosis_excess
 (density.field_statistics) and a 120-bin PDF between the field's minimum and maximum (density.field_pdf: edges, centers,
-counts, pdf, outside, nonfinite).  Painting reads the float32 displacement on the device; the saved emu_dis.npy is
+counts, pdf, outside, nonfinite).  With `--vel`, `--paint_vel` writes <output_dir>/emu_vel_mesh.npy, the (3, N, N, N)
+mass-weighted mean velocity on the same mesh (density.paint_field, normalize="density", not deconvolved), and `--rsd AXIS`
+writes <output_dir>/emu_delta_rsd.npy, the density with every particle moved by v_AXIS (1 + z) / H(z) along array axis
+AXIS (density.rsd_factor of the box's own redshift and Omega_m; `--mas_worder` and `--no-deconvolve` apply), and with
+`--pk` its power spectrum <output_dir>/emu_pk_rsd.npz.  Painting reads the float32 displacement on the device; the saved emu_dis.npy is
 rounded to --output-precision afterwards.
 
 What differs from the reference: the engine, its weights and its ~100 GB workspace stay resident on the
@@ -176,6 +180,12 @@ def build_parser():
     ap.add_argument('--onepoint', action='store_true', default=argparse.SUPPRESS,
                     help='With --density_res: also write mean, std, skewness, excess kurtosis and a 120-bin PDF of the '
                          'density field to <output_dir>/emu_onepoint.npz')
+    ap.add_argument('--paint_vel', action='store_true', default=argparse.SUPPRESS,
+                    help='With --vel and --density_res: also write the mass-weighted mean velocity on the density mesh to '
+                         '<output_dir>/emu_vel_mesh.npy (3, N, N, N)')
+    ap.add_argument('--rsd', type=int, choices=(0, 1, 2), metavar='AXIS', default=argparse.SUPPRESS,
+                    help='With --vel and --density_res: also write the redshift-space density along array axis AXIS to '
+                         '<output_dir>/emu_delta_rsd.npy (and with --pk <output_dir>/emu_pk_rsd.npz)')
     return ap
 
 
@@ -222,6 +232,36 @@ def summary_options(args):
         if flag and getattr(args, 'density_res', None) is None:
             _die(f'{name} needs --density_res')
     return on
+
+
+def velocity_options(args):
+    """(paint_vel, rsd): whether --paint_vel was given, and the axis of --rsd or None (read apart from density_options,
+    whose dict they leave as it was).  Both need --density_res and --vel."""
+    paint_vel = bool(getattr(args, 'paint_vel', False))
+    rsd = getattr(args, 'rsd', None)
+    for flag, name in ((paint_vel, '--paint_vel'), (rsd is not None, '--rsd')):
+        if flag and getattr(args, 'density_res', None) is None:
+            _die(f'{name} needs --density_res')
+        if flag and not getattr(args, 'vel', True):
+            _die(f'{name} needs --vel')
+    return paint_vel, (None if rsd is None else int(rsd))
+
+
+def velocity_fields(disp, vel, dens, paint_vel, rsd, z, Om):
+    """The arrays of emu_vel_mesh.npy, emu_delta_rsd.npy and emu_pk_rsd.npz for the device fields of one box."""
+    from .density import paint_density, paint_field, power_spectrum, rsd_factor
+    out = {}
+    if paint_vel:
+        out['vel_mesh'] = paint_field(disp, vel, boxsize=dens['boxsize'], res=dens['res'], worder=dens['worder'],
+                                      normalize='density').cpu().numpy()
+    if rsd is not None:
+        delta = paint_density(disp, boxsize=dens['boxsize'], res=dens['res'], worder=dens['worder'],
+                              deconvolve=dens['deconvolve'], velocity=vel, los=rsd,
+                              velocity_to_length=rsd_factor(z, Om))
+        out['delta_rsd'] = delta.cpu().numpy()
+        if dens['pk']:
+            out['pk_rsd'] = power_spectrum(delta, boxsize=dens['boxsize'])
+    return out
 
 
 def density_summaries(delta, dens, bispec, onepoint):
@@ -273,6 +313,7 @@ def run(args):
     dens = density_options(args)
     mink = minkowski_option(args)
     bispec, onepoint = summary_options(args)
+    paint_vel, rsd = velocity_options(args)
     if bispec:
         for k1, k2 in BISPECTRUM_CONFIGS:                    # density.bispectrum's closure condition, before any work
             if 2.0 * (k1 + k2) * dens['boxsize'] / (2.0 * np.pi) + 1.5 >= dens['res']:
@@ -281,7 +322,8 @@ def run(args):
     if dens is not None:
         print(f"  Density: {dens['res']}^3 mesh, worder {dens['worder']}, deconvolve {dens['deconvolve']}, "
               f"boxsize {dens['boxsize']}, P(k) {dens['pk']}" + (", Minkowski functionals" if mink else "")
-              + (", bispectrum" if bispec else "") + (", one-point statistics" if onepoint else ""))
+              + (", bispectrum" if bispec else "") + (", one-point statistics" if onepoint else "")
+              + (", velocity mesh" if paint_vel else "") + (f", redshift space along axis {rsd}" if rsd is not None else ""))
     print()
 
     shape = None
@@ -320,6 +362,13 @@ def run(args):
                 np.savez(out_dir / 'emu_bispectrum.npz', **extra['bk'])
             if extra.get('onepoint') is not None:
                 np.savez(out_dir / 'emu_onepoint.npz', **extra['onepoint'])
+            if 'vel_mesh' in extra:
+                np.save(out_dir / 'emu_vel_mesh.npy', extra['vel_mesh'])
+            if 'delta_rsd' in extra:
+                np.save(out_dir / 'emu_delta_rsd.npy', extra['delta_rsd'])
+            if 'pk_rsd' in extra:
+                k, pk, nmodes = extra['pk_rsd']
+                np.savez(out_dir / 'emu_pk_rsd.npz', k=k, pk=pk, nmodes=nmodes)
 
     def with_density(dis_in, z, Om):
         """process_box on the device, the density field of its float32 displacement, host copies of the fields."""
@@ -337,6 +386,8 @@ def run(args):
             extra['mf'] = minkowski_functionals(delta, boxsize=dens['boxsize'])
         if bispec or onepoint:
             extra['bk'], extra['onepoint'] = density_summaries(delta, dens, bispec, onepoint)
+        if paint_vel or rsd is not None:
+            extra.update(velocity_fields(disp, result[1], dens, paint_vel, rsd, z, Om))
         out_dt = np.dtype(args.output_precision)
         host = tuple(t.cpu().numpy().astype(out_dt, copy=False) for t in (result if args.vel else (result,)))
         return (host if args.vel else host[0]), extra
