@@ -13,6 +13,13 @@
 // wave-instruction cover contiguous runs of a mesh row.  Integer adds commute: the mesh is bitwise independent of the
 // order in which workgroups and lanes arrive.  A tile whose footprint exceeds the LDS image adds its weights straight
 // into the global mesh (the same integers, so the same bits) and is counted in stats[0].
+//
+// Shared pieces, each written once.  Both moment entry points and the triple sums reduce with moments_pass_kernel<CENTRED,
+// ORDER> / triple_sums_kernel, block_sum and sum_finish_kernel.  The spectral kernels decode a mode with half_mode and
+// the shell sums of the power spectrum and of the shell filter share power_exponent and shell_add.  upper_bound bins
+// the Minkowski thresholds and the triangle counts; with_worder turns worder into a template argument.  The two
+// painters (paint_kernel, paint_field_kernel) still carry their own copies of the tile pass: their positions are
+// i a + psi s as the compiler contracts it, and moving that expression changes which product is fused.
 
 #include "../../include/nbe.h"
 
@@ -23,6 +30,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 namespace nbe { int api_fail(const char* msg); }
 
@@ -430,6 +438,20 @@ __global__ void mesh_to_field_kernel(ToFieldArgs A) {
 // frequency index of position i on an axis of n points (numpy.fft.fftfreq * n)
 __device__ inline long long freq(long long i, long long n) { return i <= n / 2 ? i : i - n; }
 
+// Mode i of the row-major half spectrum (r0, r1, r2/2+1) of an (r0, r1, r2) mesh: its integer frequencies, their
+// |m|^2 = q and its weight in the full grid (the modes whose mirror image the half spectrum leaves out count twice)
+struct HalfMode { long long f0, f1, f2, q; int w; };
+
+__device__ inline HalfMode half_mode(long long i, long long r0, long long r1, long long r2) {
+    const long long h2 = r2 / 2 + 1;
+    const long long i2 = i % h2, r = i / h2, i1 = r % r1, i0 = r / r1;
+    HalfMode m;
+    m.f0 = freq(i0, r0); m.f1 = freq(i1, r1); m.f2 = i2;
+    m.q = m.f0 * m.f0 + m.f1 * m.f1 + i2 * i2;
+    m.w = (i2 == 0 || (r2 % 2 == 0 && i2 == r2 / 2)) ? 1 : 2;
+    return m;
+}
+
 __device__ inline double sinc_pi(long long f, long long n) {            // sinc(pi f / n), sinc(x) = sin(x) / x
     if (f == 0) return 1.0;
     const double x = (double)f / (double)n;
@@ -438,10 +460,10 @@ __device__ inline double sinc_pi(long long f, long long n) {            // sinc(
 
 template <int P>
 __global__ void deconvolve_kernel(float2* __restrict__ f, long long r0, long long r1, long long r2) {
-    const long long h2 = r2 / 2 + 1, n = r0 * r1 * h2;
+    const long long n = r0 * r1 * (r2 / 2 + 1);
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const long long i2 = i % h2, r = i / h2, i1 = r % r1, i0 = r / r1;
-        const double w = sinc_pi(freq(i0, r0), r0) * sinc_pi(freq(i1, r1), r1) * sinc_pi(i2, r2);
+        const HalfMode m = half_mode(i, r0, r1, r2);
+        const double w = sinc_pi(m.f0, r0) * sinc_pi(m.f1, r1) * sinc_pi(m.f2, r2);
         double wp = w;
 #pragma unroll
         for (int p = 1; p < P; ++p) wp *= w;
@@ -453,24 +475,42 @@ __global__ void deconvolve_kernel(float2* __restrict__ f, long long r0, long lon
     }
 }
 
+// Shell sums, shared by the power spectrum and the shell filter.  A first pass finds the largest |term| of each shell as
+// float bits (unsigned order = float order for non-negative floats; atomicMax commutes): binmax = m 2^e, m in [0.5, 1).
+// The second adds, per shell and in integers, the weights, w (|k| / k_F - offset) in the shell's k unit and w term in
+// units of 2^(e - 32), so that every term is at most 2^32 units.
+// the power exponent 32 - e of a binmax word; INT_MIN: non-finite shell, reported by the caller
+__device__ inline int power_exponent(unsigned binmax) {
+    const float m = __uint_as_float(binmax);
+    int e = 0;
+    if (isfinite(m) && m > 0.0f) frexp((double)m, &e);
+    return isfinite(m) ? 32 - e : INT_MIN;
+}
+
+// one mode into the LDS triple t[0], t[stride], t[2 stride] of its shell: weight, k, power
+__device__ inline void shell_add(unsigned long long* t, int stride, int w, long long kq, double p, int pexp) {
+    const long long pq = pexp == INT_MIN ? 0 : (long long)rint(ldexp(p, pexp));
+    atomicAdd(t, (unsigned long long)w);
+    atomicAdd(t + stride, (unsigned long long)(w * kq));
+    atomicAdd(t + 2 * stride, (unsigned long long)(w * pq));
+}
+
 // One mode of the half spectrum of an n^3 mesh: shell b (0 = not binned), full-grid weight, |k| / k_F, Re(a b*)
 struct Mode { int b; int w; double kk; double p; };
 
 __device__ inline Mode mode_at(const float2* a, const float2* bb, long long i, long long n) {
-    const long long h2 = n / 2 + 1;
-    const long long i2 = i % h2, r = i / h2, i1 = r % n, i0 = r / n;
-    const long long f0 = freq(i0, n), f1 = freq(i1, n);
+    const HalfMode h = half_mode(i, n, n, n);
     Mode m;
-    m.kk = sqrt((double)(f0 * f0 + f1 * f1 + i2 * i2));
+    m.kk = sqrt((double)h.q);
     m.b = (int)floor(m.kk + 0.5);
     if (m.b < 1 || m.b > n / 2) { m.b = 0; return m; }
-    m.w = (i2 == 0 || (n % 2 == 0 && i2 == n / 2)) ? 1 : 2;
+    m.w = h.w;
     const float2 x = a[i], y = bb ? bb[i] : x;
     m.p = (double)x.x * y.x + (double)x.y * y.y;
     return m;
 }
 
-// pass 1: per-shell max |Re(a b*)| as float bits (unsigned order = float order for non-negative floats)
+// pass 1: per-shell max |Re(a b*)|
 __global__ void pk_max_kernel(const float2* __restrict__ a, const float2* __restrict__ b, long long n,
                               unsigned* __restrict__ binmax) {
     extern __shared__ unsigned smax[];
@@ -487,8 +527,7 @@ __global__ void pk_max_kernel(const float2* __restrict__ a, const float2* __rest
         if (smax[i]) atomicMax(&binmax[i], smax[i]);
 }
 
-// pass 2: per shell, in integers: sum of weights, sum of w (|k|/k_F - b) in units of 2^-36, sum of w Re(a b*) in units
-// of 2^(e_b - 32) where binmax_b = m 2^e_b, m in [0.5, 1) -- every term is at most 2^32 units
+// pass 2: every mode binned by rint(|k| / k_F); k in units of 2^-36 about the shell's index
 constexpr double kKUnit = 68719476736.0;                  // 2^36
 __global__ void pk_sum_kernel(const float2* __restrict__ a, const float2* __restrict__ b, long long n,
                               const unsigned* __restrict__ binmax, unsigned long long* __restrict__ sums) {
@@ -496,23 +535,12 @@ __global__ void pk_sum_kernel(const float2* __restrict__ a, const float2* __rest
     const int nb = (int)(n / 2) + 1;
     int* sexp = (int*)(ssum + 3 * nb);
     for (int i = threadIdx.x; i < 3 * nb; i += blockDim.x) ssum[i] = 0ull;
-    for (int i = threadIdx.x; i < nb; i += blockDim.x) {
-        const float m = __uint_as_float(binmax[i]);
-        int e = 0;
-        if (isfinite(m) && m > 0.0f) frexp((double)m, &e);
-        sexp[i] = isfinite(m) ? 32 - e : INT_MIN;          // INT_MIN: non-finite shell, reported by the caller
-    }
+    for (int i = threadIdx.x; i < nb; i += blockDim.x) sexp[i] = power_exponent(binmax[i]);
     __syncthreads();
     const long long total = n * n * (n / 2 + 1);
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const Mode m = mode_at(a, b, i, n);
-        if (!m.b) continue;
-        const long long kq = (long long)rint((m.kk - m.b) * kKUnit);
-        const int s = sexp[m.b];
-        const long long pq = s == INT_MIN ? 0 : (long long)rint(ldexp(m.p, s));
-        atomicAdd(&ssum[m.b], (unsigned long long)m.w);
-        atomicAdd(&ssum[nb + m.b], (unsigned long long)(m.w * kq));
-        atomicAdd(&ssum[2 * nb + m.b], (unsigned long long)(m.w * pq));
+        if (m.b) shell_add(ssum + m.b, nb, m.w, (long long)rint((m.kk - m.b) * kKUnit), m.p, sexp[m.b]);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < 3 * nb; i += blockDim.x)
@@ -520,14 +548,30 @@ __global__ void pk_sum_kernel(const float2* __restrict__ a, const float2* __rest
 }
 
 // ---- Minkowski functionals ------------------------------------------------------------------
-// Moments: two passes in float64 (the sum, then the sum of squared deviations from the mean), each over a fixed
-// partition of the n^3 voxels into kMomBlocks(n) * kMomThreads strided runs, reduced in a fixed order by one block.
+// Moments (nbe_field_moments, and to the fourth order nbe_field_moments4): two passes in float64 (the sum, then the sums
+// of powers of the deviation from the mean), each over a fixed partition of the voxels into mom_blocks(total) *
+// kMomThreads strided runs, reduced in a fixed order by one block.
 constexpr int kMomThreads = 256;
 constexpr int kMomMaxBlocks = NBE_MOMENTS_WORDS - 2;
 
 int mom_blocks(long long total) {
     const long long b = (total + 8 * kMomThreads - 1) / (8 * kMomThreads);
     return (int)(b < kMomMaxBlocks ? b : kMomMaxBlocks);
+}
+
+// Fixed-step upper_bound: #{a[i] <= v} over the n sorted values of a (LDS); top = top_step(n).  A NaN v gives 0.
+__device__ inline int top_step(int n) {
+    int top = 1;
+    while (2 * top <= n) top *= 2;
+    return top;
+}
+
+template <typename T>
+__device__ inline int upper_bound(const T* a, int n, int top, T v) {
+    int pos = 0;
+    for (int step = top; step > 0; step >>= 1)
+        if (pos + step <= n && a[pos + step - 1] <= v) pos += step;
+    return pos;
 }
 
 // the block's sum of v over its threads, in a fixed tree order; valid in thread 0
@@ -541,39 +585,55 @@ __device__ inline double block_sum(double v, double* red) {
     return red[0];
 }
 
-// CENTRED = false: partial[b] = sum of x; true: partial[b] = sum of (x - mom[0])^2
-template <bool CENTRED>
+// One pass over a field: block b's sums of x (CENTRED = false), or of the powers 2 .. ORDER of d = x - *mean, into
+// partial[(p - 2) * kMomMaxBlocks + b].  Each ORDER keeps its own expression: the compiler contracts `a2 += d * d` and
+// `d2 = d * d; a2 += d2` differently, and one ulp of the ORDER 2 std can move a voxel across a Minkowski threshold.
+template <bool CENTRED, int ORDER>
 __global__ __launch_bounds__(kMomThreads) void moments_pass_kernel(const float* __restrict__ x, long long total,
-                                                                   double* __restrict__ mom) {
+                                                                   const double* mean_at, double* partial) {
+    static_assert(ORDER == 2 || ORDER == 4, "the variance alone, or the central moments to the fourth");
     __shared__ double red[kMomThreads];
-    const double mean = CENTRED ? mom[0] : 0.0;
+    const double mean = CENTRED ? *mean_at : 0.0;
     const long long stride = (long long)gridDim.x * kMomThreads;
-    double acc = 0.0;
+    double a2 = 0.0, a3 = 0.0, a4 = 0.0;
+    auto add = [&](float v) {
+        if (!CENTRED) {
+            a2 += v;
+        } else if (ORDER == 2) {
+            const double d = v - mean;
+            a2 += d * d;
+        } else {
+            const double d = v - mean, d2 = d * d;
+            a2 += d2; a3 += d2 * d; a4 += d2 * d2;
+        }
+    };
     long long i = (long long)blockIdx.x * kMomThreads + threadIdx.x;
     for (; i + 3 * stride < total; i += 4 * stride) {        // four loads in flight, added in index order
         const float a = x[i], b = x[i + stride], c = x[i + 2 * stride], d = x[i + 3 * stride];
-        if (CENTRED) {
-            const double da = a - mean, db = b - mean, dc = c - mean, dd = d - mean;
-            acc += da * da; acc += db * db; acc += dc * dc; acc += dd * dd;
-        } else {
-            acc += a; acc += b; acc += c; acc += d;
-        }
+        add(a); add(b); add(c); add(d);
     }
-    for (; i < total; i += stride) {
-        const double v = CENTRED ? (x[i] - mean) * (x[i] - mean) : (double)x[i];
-        acc += v;
-    }
-    const double s = block_sum(acc, red);
-    if (threadIdx.x == 0) mom[2 + blockIdx.x] = s;
+    for (; i < total; i += stride) add(x[i]);
+    const double s2 = block_sum(a2, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s2;
+    if (!CENTRED || ORDER == 2) return;
+    __syncthreads();
+    const double s3 = block_sum(a3, red);
+    if (threadIdx.x == 0) partial[kMomMaxBlocks + blockIdx.x] = s3;
+    __syncthreads();
+    const double s4 = block_sum(a4, red);
+    if (threadIdx.x == 0) partial[2 * kMomMaxBlocks + blockIdx.x] = s4;
 }
 
-// one block: mom[slot] = sum of the nb partials / total (slot 0: the mean; slot 1: the std, after a square root)
-__global__ __launch_bounds__(kMomThreads) void moments_finish_kernel(double* mom, int nb, long long total, int slot) {
+// block j: out[j] = the sum of the nb partials of row j (rows of `row` words) in a fixed order; with total != 0 divided
+// by it, and with root its square root after that
+__global__ __launch_bounds__(kMomThreads) void sum_finish_kernel(const double* partial, long long row, int nb, double* out,
+                                                                 long long total, int root) {
     __shared__ double red[kMomThreads];
     double acc = 0.0;
-    for (int b = threadIdx.x; b < nb; b += kMomThreads) acc += mom[2 + b];
-    const double s = block_sum(acc, red) / (double)total;
-    if (threadIdx.x == 0) mom[slot] = slot == 0 ? s : sqrt(s);
+    for (int b = threadIdx.x; b < nb; b += kMomThreads) acc += partial[blockIdx.x * row + b];
+    double s = block_sum(acc, red);
+    if (total) s = s / (double)total;
+    if (threadIdx.x == 0) out[blockIdx.x] = root ? sqrt(s) : s;
 }
 
 // Counts: one pass.  Each voxel v owns the 8 elements at its low corner (1 cube, 3 faces, 3 edges, 1 vertex); an element
@@ -641,8 +701,7 @@ __global__ __launch_bounds__(kMfThreads) void minkowski_counts_kernel(MfArgs A) 
     for (int i = tid; i < T; i += kMfThreads) thr[i] = A.thr[i];
     for (int i = tid; i < NB; i += kMfThreads) hist[i] = 0u;
     if (tid == 0) nonfinite = 0u;
-    int top = 1;
-    while (2 * top <= T) top *= 2;
+    const int top = top_step(T);
     const bool stdz = A.mom != nullptr;
     float mf = 0.0f, sf = 0.0f;
     if (stdz) { mf = (float)A.mom[0]; sf = (float)A.mom[1]; }
@@ -650,14 +709,11 @@ __global__ __launch_bounds__(kMfThreads) void minkowski_counts_kernel(MfArgs A) 
     __syncthreads();
 
     // bin of one value: standardized with correctly rounded float32 subtraction and division (no reciprocal, nothing to
-    // contract), then the number of thresholds <= w by a fixed-step search (NaN: 0; the caller rejects the field)
+    // contract), then the number of thresholds <= w (NaN: 0; the caller rejects the field)
     auto bin_of = [&](float v) -> int {
         float w = v;
         if (stdz) w = sf == 0.0f ? 0.0f : __fdiv_rn(__fsub_rn(v, mf), sf);
-        int pos = 0;
-        for (int step = top; step > 0; step >>= 1)
-            if (pos + step <= T && thr[pos + step - 1] <= w) pos += step;
-        return pos;
+        return upper_bound(thr, T, top, w);
     };
 
     const int wv = tid >> 6, kl = tid & 63;         // this thread's voxels: (j0 + 4 wv + r, k0 + kl), r = 0 .. 3
@@ -747,8 +803,7 @@ __global__ __launch_bounds__(kMfThreads) void minkowski_counts_kernel(MfArgs A) 
 // Shell filter: one pass over the half spectrum of an n^3 mesh serves a batch of S spherical shells.  Every mode forms its
 // integer |m|^2 once and tests it against the batch's [lo2, hi2) bounds (integers, prepared by the host); shell s receives
 // the mode or 0 in its own filtered spectrum.  The bounds are symmetric under m -> -m, so the filtered half spectra stay
-// Hermitian.  The per-shell sums use the integer scheme of nbe_power_spectrum: a first pass finds the largest |delta|^2
-// of each shell, the second adds the weights, |m| - koff in units of 2^-kexp and |delta|^2 in units of 2^(e - 32).
+// Hermitian.  The per-shell sums use the shell-sum scheme above, with |m| - koff in units of 2^-kexp.
 constexpr int kBkThreads = 256;
 
 struct ShellArgs {
@@ -760,15 +815,6 @@ struct ShellArgs {
     unsigned* binmax;              // S, or NULL (no sums)
     unsigned long long* sums;      // S x 3: weight, k, power
 };
-
-// |m|^2 of mode i of the half spectrum and its weight in the full grid
-__device__ inline long long mode_q(long long i, long long n, int* w) {
-    const long long h2 = n / 2 + 1;
-    const long long i2 = i % h2, r = i / h2, i1 = r % n, i0 = r / n;
-    const long long f0 = freq(i0, n), f1 = freq(i1, n);
-    *w = (i2 == 0 || (n % 2 == 0 && i2 == n / 2)) ? 1 : 2;
-    return f0 * f0 + f1 * f1 + i2 * i2;
-}
 
 __global__ __launch_bounds__(kBkThreads) void shell_max_kernel(ShellArgs A) {
     __shared__ long long lo2[NBE_BK_MAX_SHELLS], hi2[NBE_BK_MAX_SHELLS];
@@ -785,8 +831,7 @@ __global__ __launch_bounds__(kBkThreads) void shell_max_kernel(ShellArgs A) {
     __syncthreads();
     const long long total = A.n * A.n * (A.n / 2 + 1), q0 = qmin, q1 = qmax;
     for (long long i = blockIdx.x * (long long)kBkThreads + threadIdx.x; i < total; i += (long long)gridDim.x * kBkThreads) {
-        int w;
-        const long long q = mode_q(i, A.n, &w);
+        const long long q = half_mode(i, A.n, A.n, A.n).q;
         if (q < q0 || q >= q1) continue;
         const float2 v = A.spec[i];
         const unsigned bits = __float_as_uint((float)fabs((double)v.x * v.x + (double)v.y * v.y));
@@ -809,19 +854,13 @@ __global__ __launch_bounds__(kBkThreads) void shell_filter_kernel(ShellArgs A) {
         lo2[s] = A.par[4 * s]; hi2[s] = A.par[4 * s + 1];
         koff[s] = (double)A.par[4 * s + 2]; kexp[s] = (int)A.par[4 * s + 3];
         ssum[3 * s] = ssum[3 * s + 1] = ssum[3 * s + 2] = 0ull;
-        pexp[s] = INT_MIN;
-        if (sums) {
-            const float m = __uint_as_float(A.binmax[s]);
-            int e = 0;
-            if (isfinite(m) && m > 0.0f) frexp((double)m, &e);
-            pexp[s] = isfinite(m) ? 32 - e : INT_MIN;      // INT_MIN: non-finite shell, reported by the caller
-        }
+        pexp[s] = sums ? power_exponent(A.binmax[s]) : INT_MIN;
     }
     __syncthreads();
     const long long total = A.n * A.n * (A.n / 2 + 1);
     for (long long i = blockIdx.x * (long long)kBkThreads + threadIdx.x; i < total; i += (long long)gridDim.x * kBkThreads) {
-        int w;
-        const long long q = mode_q(i, A.n, &w);
+        const HalfMode m = half_mode(i, A.n, A.n, A.n);
+        const long long q = m.q;
         const float2 v = A.spec[i];
         const float2 zero = make_float2(0.0f, 0.0f);
         for (int s = 0; s < S; ++s) {
@@ -829,11 +868,7 @@ __global__ __launch_bounds__(kBkThreads) void shell_filter_kernel(ShellArgs A) {
             if (A.out) A.out[(long long)s * total + i] = in ? v : zero;
             if (in && sums) {
                 const double p = (double)v.x * v.x + (double)v.y * v.y;
-                const long long kq = (long long)rint(ldexp(sqrt((double)q) - koff[s], kexp[s]));
-                const long long pq = pexp[s] == INT_MIN ? 0 : (long long)rint(ldexp(p, pexp[s]));
-                atomicAdd(&ssum[3 * s], (unsigned long long)w);
-                atomicAdd(&ssum[3 * s + 1], (unsigned long long)(w * kq));
-                atomicAdd(&ssum[3 * s + 2], (unsigned long long)(w * pq));
+                shell_add(ssum + 3 * s, 1, m.w, (long long)rint(ldexp(sqrt((double)q) - koff[s], kexp[s])), p, pexp[s]);
             }
         }
     }
@@ -845,8 +880,8 @@ __global__ __launch_bounds__(kBkThreads) void shell_filter_kernel(ShellArgs A) {
 
 // Triple sums: out[j] = sum over the voxels of f1 f2 f3_j in float64.  The voxels are cut into mom_blocks(total) *
 // kMomThreads strided runs (a function of the mesh size only); every run is added in index order with one fused
-// multiply-add per voxel, the runs of a block in block_sum's tree and the blocks by one workgroup in a fixed order.  The
-// result of field j therefore does not depend on which other fields share its launch.
+// multiply-add per voxel, the runs of a block in block_sum's tree and the blocks by one workgroup of sum_finish_kernel.
+// The result of field j therefore does not depend on which other fields share its launch.
 constexpr int kTsFields = 8;
 
 struct TripleArgs {
@@ -879,16 +914,6 @@ __global__ __launch_bounds__(kMomThreads) void triple_sums_kernel(TripleArgs A) 
     }
 }
 
-// block j: out[j] = sum of partial[j][0 .. nb) in a fixed order
-__global__ __launch_bounds__(kMomThreads) void triple_finish_kernel(const double* __restrict__ partial, int nb,
-                                                                    double* __restrict__ out) {
-    __shared__ double red[kMomThreads];
-    double acc = 0.0;
-    for (int b = threadIdx.x; b < nb; b += kMomThreads) acc += partial[(long long)blockIdx.x * NBE_BK_PARTIALS + b];
-    const double s = block_sum(acc, red);
-    if (threadIdx.x == 0) out[blockIdx.x] = s;
-}
-
 // Triangle counts: every pair (m1, m2) of the modes of shells 1 and 2 closes with m3 = -(m1 + m2); |m3|^2 is binned by
 // upper_bound over the K sorted distinct bounds of the third shells, and the count of a shell [lo2, hi2) is the sum of
 // the bins between its two bounds.  Integers throughout: exact at every mesh size.
@@ -914,8 +939,7 @@ __global__ __launch_bounds__(kBkThreads) void pair_count_kernel(PairArgs A) {
     for (int i = tid; i < K; i += kBkThreads) edges[i] = A.edges[i];
     for (int i = tid; i <= K; i += kBkThreads) hist[i] = 0u;
     __syncthreads();
-    int top = 1;
-    while (2 * top <= K) top *= 2;
+    const int top = top_step(K);
     const long long i1 = t1 * kBkThreads + tid;
     if (i1 < A.c1) {
         const int4 a = A.m1[i1];
@@ -925,59 +949,12 @@ __global__ __launch_bounds__(kBkThreads) void pair_count_kernel(PairArgs A) {
             const int x = a.x + b.x, y = a.y + b.y, z = a.z + b.z;
             const int q = x * x + y * y + z * z;
             if (q < e0 || q >= e1) continue;
-            int pos = 0;
-            for (int step = top; step > 0; step >>= 1)
-                if (pos + step <= K && edges[pos + step - 1] <= q) pos += step;
-            atomicAdd(&hist[pos], 1u);
+            atomicAdd(&hist[upper_bound(edges, K, top, q)], 1u);
         }
     }
     __syncthreads();
     for (int i = tid; i <= K; i += kBkThreads)
         if (hist[i]) atomicAdd(&A.hist[i], (unsigned long long)hist[i]);
-}
-
-// Central moments to the fourth: the sum, then the sums of d^2, d^3 and d^4 about the mean, over the partition and in the
-// order of nbe_field_moments.  mom[0..3] = mean, std, m3, m4; partials from mom[4], three rows of kMomMaxBlocks.
-template <bool CENTRED>
-__global__ __launch_bounds__(kMomThreads) void moments4_pass_kernel(const float* __restrict__ x, long long total,
-                                                                    double* __restrict__ mom) {
-    __shared__ double red[kMomThreads];
-    const double mean = CENTRED ? mom[0] : 0.0;
-    const long long stride = (long long)gridDim.x * kMomThreads;
-    double a2 = 0.0, a3 = 0.0, a4 = 0.0;
-    auto add = [&](float v) {
-        if (CENTRED) {
-            const double d = v - mean, d2 = d * d;
-            a2 += d2; a3 += d2 * d; a4 += d2 * d2;
-        } else {
-            a2 += v;
-        }
-    };
-    long long i = (long long)blockIdx.x * kMomThreads + threadIdx.x;
-    for (; i + 3 * stride < total; i += 4 * stride) {        // four loads in flight, added in index order
-        const float a = x[i], b = x[i + stride], c = x[i + 2 * stride], d = x[i + 3 * stride];
-        add(a); add(b); add(c); add(d);
-    }
-    for (; i < total; i += stride) add(x[i]);
-    const double s2 = block_sum(a2, red);
-    if (threadIdx.x == 0) mom[4 + blockIdx.x] = s2;
-    if (!CENTRED) return;
-    __syncthreads();
-    const double s3 = block_sum(a3, red);
-    if (threadIdx.x == 0) mom[4 + kMomMaxBlocks + blockIdx.x] = s3;
-    __syncthreads();
-    const double s4 = block_sum(a4, red);
-    if (threadIdx.x == 0) mom[4 + 2 * kMomMaxBlocks + blockIdx.x] = s4;
-}
-
-// one block: mom[slot] = sum of row `row` of the partials / total (slot 1: its square root)
-__global__ __launch_bounds__(kMomThreads) void moments4_finish_kernel(double* mom, int nb, long long total, int row,
-                                                                      int slot) {
-    __shared__ double red[kMomThreads];
-    double acc = 0.0;
-    for (int b = threadIdx.x; b < nb; b += kMomThreads) acc += mom[4 + (long long)row * kMomMaxBlocks + b];
-    const double s = block_sum(acc, red) / (double)total;
-    if (threadIdx.x == 0) mom[slot] = slot == 1 ? sqrt(s) : s;
 }
 
 // One-point histogram over nbins uniform bins with float64 edges (np.linspace): voxel x, widened to float64, falls into
@@ -1049,6 +1026,32 @@ int grid_for(long long n, int threads) {
     return (int)(g < 1 ? 1 : g > 65536 ? 65536 : g);
 }
 
+// mom[0] = mean, mom[1] = std and for ORDER 4 mom[2], mom[3] = the third and fourth central moments; the partials start at
+// mom[ORDER], ORDER - 1 rows of kMomMaxBlocks
+template <int ORDER>
+void field_moments(const float* x, long long total, double* mom, hipStream_t s) {
+    const int nb = mom_blocks(total);
+    const dim3 grid(nb), one(1), block(kMomThreads);
+    double* partial = mom + ORDER;
+    hipLaunchKernelGGL((moments_pass_kernel<false, 2>), grid, block, 0, s, x, total, mom, partial);
+    hipLaunchKernelGGL(sum_finish_kernel, one, block, 0, s, partial, 0LL, nb, mom, total, 0);
+    hipLaunchKernelGGL((moments_pass_kernel<true, ORDER>), grid, block, 0, s, x, total, mom, partial);
+    for (int p = 2; p <= ORDER; ++p)
+        hipLaunchKernelGGL(sum_finish_kernel, one, block, 0, s, partial + (p - 2) * kMomMaxBlocks, 0LL, nb, mom + p - 1,
+                           total, p == 2);
+}
+
+// f(std::integral_constant<int, P>) for the assignment order P = worder (validated by the caller: 1 .. 4)
+template <typename F>
+void with_worder(int worder, F f) {
+    switch (worder) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1080,16 +1083,10 @@ int nbe_paint_mesh(const void* disp, int disp_dtype, const int64_t n[3], const d
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)tiles), block(kPaintThreads);
     const bool half = disp_dtype == NBE_F16;
-    switch (worder * 2 + half) {
-        case 2: hipLaunchKernelGGL((paint_kernel<1, false>), grid, block, 0, s, A); break;
-        case 3: hipLaunchKernelGGL((paint_kernel<1, true>), grid, block, 0, s, A); break;
-        case 4: hipLaunchKernelGGL((paint_kernel<2, false>), grid, block, 0, s, A); break;
-        case 5: hipLaunchKernelGGL((paint_kernel<2, true>), grid, block, 0, s, A); break;
-        case 6: hipLaunchKernelGGL((paint_kernel<3, false>), grid, block, 0, s, A); break;
-        case 7: hipLaunchKernelGGL((paint_kernel<3, true>), grid, block, 0, s, A); break;
-        case 8: hipLaunchKernelGGL((paint_kernel<4, false>), grid, block, 0, s, A); break;
-        default: hipLaunchKernelGGL((paint_kernel<4, true>), grid, block, 0, s, A); break;
-    }
+    with_worder(worder, [&](auto P) {
+        if (half) hipLaunchKernelGGL((paint_kernel<decltype(P)::value, true>), grid, block, 0, s, A);
+        else hipLaunchKernelGGL((paint_kernel<decltype(P)::value, false>), grid, block, 0, s, A);
+    });
     return launched("nbe_paint_mesh");
 }
 
@@ -1168,12 +1165,7 @@ int nbe_paint_fields(const void* disp, int disp_dtype, const void* quantity, int
     if (tiles > INT_MAX) return fail("nbe_paint_fields: %lld tiles exceed one launch", tiles);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)tiles), block(kPaintThreads);
-    switch (worder) {
-        case 1: hipLaunchKernelGGL(paint_field_kernel<1>, grid, block, 0, s, A); break;
-        case 2: hipLaunchKernelGGL(paint_field_kernel<2>, grid, block, 0, s, A); break;
-        case 3: hipLaunchKernelGGL(paint_field_kernel<3>, grid, block, 0, s, A); break;
-        default: hipLaunchKernelGGL(paint_field_kernel<4>, grid, block, 0, s, A); break;
-    }
+    with_worder(worder, [&](auto P) { hipLaunchKernelGGL(paint_field_kernel<decltype(P)::value>, grid, block, 0, s, A); });
     return launched("nbe_paint_fields");
 }
 
@@ -1205,15 +1197,10 @@ int nbe_deconvolve_mas(void* field, const int64_t res[3], int worder, void* stre
     if (worder < 1 || worder > 4) return fail("nbe_deconvolve_mas: worder %d not in 1..4", worder);
     if (res[0] < 1 || res[1] < 1 || res[2] < 1) return fail("nbe_deconvolve_mas: bad sizes");
     const long long n = (long long)res[0] * res[1] * (res[2] / 2 + 1);
-    const dim3 g(grid_for(n, 256)), b(256);
-    hipStream_t s = (hipStream_t)stream;
-    float2* f = (float2*)field;
-    switch (worder) {
-        case 1: hipLaunchKernelGGL(deconvolve_kernel<1>, g, b, 0, s, f, res[0], res[1], res[2]); break;
-        case 2: hipLaunchKernelGGL(deconvolve_kernel<2>, g, b, 0, s, f, res[0], res[1], res[2]); break;
-        case 3: hipLaunchKernelGGL(deconvolve_kernel<3>, g, b, 0, s, f, res[0], res[1], res[2]); break;
-        default: hipLaunchKernelGGL(deconvolve_kernel<4>, g, b, 0, s, f, res[0], res[1], res[2]); break;
-    }
+    with_worder(worder, [&](auto P) {
+        hipLaunchKernelGGL(deconvolve_kernel<decltype(P)::value>, dim3(grid_for(n, 256)), dim3(256), 0,
+                           (hipStream_t)stream, (float2*)field, res[0], res[1], res[2]);
+    });
     return launched("nbe_deconvolve_mas");
 }
 
@@ -1237,14 +1224,7 @@ int nbe_field_moments(const void* field, int64_t n, void* moments, void* stream)
     if (n < 1 || n > NBE_MF_MAX_N) return fail("nbe_field_moments: mesh size %lld unsupported (1 .. %d)", (long long)n,
                                                NBE_MF_MAX_N);
     const long long total = (long long)n * n * n;
-    const int nb = mom_blocks(total);
-    hipStream_t s = (hipStream_t)stream;
-    const float* x = (const float*)field;
-    double* mom = (double*)moments;
-    hipLaunchKernelGGL(moments_pass_kernel<false>, dim3(nb), dim3(kMomThreads), 0, s, x, total, mom);
-    hipLaunchKernelGGL(moments_finish_kernel, dim3(1), dim3(kMomThreads), 0, s, mom, nb, total, 0);
-    hipLaunchKernelGGL(moments_pass_kernel<true>, dim3(nb), dim3(kMomThreads), 0, s, x, total, mom);
-    hipLaunchKernelGGL(moments_finish_kernel, dim3(1), dim3(kMomThreads), 0, s, mom, nb, total, 1);
+    field_moments<2>((const float*)field, total, (double*)moments, (hipStream_t)stream);
     return launched("nbe_field_moments");
 }
 
@@ -1325,8 +1305,8 @@ int nbe_triple_sums(const void* f1, const void* f2, const void* f3, int nfields,
         hipLaunchKernelGGL(triple_sums_kernel, dim3(nb), dim3(kMomThreads), 0, s, A);
         if (int rc = launched("nbe_triple_sums")) return rc;
     }
-    hipLaunchKernelGGL(triple_finish_kernel, dim3(nfields), dim3(kMomThreads), 0, s, (const double*)partials, nb,
-                       (double*)out);
+    hipLaunchKernelGGL(sum_finish_kernel, dim3(nfields), dim3(kMomThreads), 0, s, (const double*)partials,
+                       (long long)NBE_BK_PARTIALS, nb, (double*)out, 0LL, 0);
     return launched("nbe_triple_sums (finish)");
 }
 
@@ -1353,16 +1333,7 @@ int nbe_field_moments4(const void* field, int64_t count, void* moments, void* st
     if (!field || !moments) return fail("nbe_field_moments4: NULL argument");
     if (count < 1 || count > NBE_ONEPOINT_MAX_VOXELS)
         return fail("nbe_field_moments4: %lld voxels unsupported (1 .. 2^40)", (long long)count);
-    const int nb = mom_blocks(count);
-    hipStream_t s = (hipStream_t)stream;
-    const float* x = (const float*)field;
-    double* mom = (double*)moments;
-    hipLaunchKernelGGL(moments4_pass_kernel<false>, dim3(nb), dim3(kMomThreads), 0, s, x, (long long)count, mom);
-    hipLaunchKernelGGL(moments4_finish_kernel, dim3(1), dim3(kMomThreads), 0, s, mom, nb, (long long)count, 0, 0);
-    hipLaunchKernelGGL(moments4_pass_kernel<true>, dim3(nb), dim3(kMomThreads), 0, s, x, (long long)count, mom);
-    hipLaunchKernelGGL(moments4_finish_kernel, dim3(1), dim3(kMomThreads), 0, s, mom, nb, (long long)count, 0, 1);
-    hipLaunchKernelGGL(moments4_finish_kernel, dim3(1), dim3(kMomThreads), 0, s, mom, nb, (long long)count, 1, 2);
-    hipLaunchKernelGGL(moments4_finish_kernel, dim3(1), dim3(kMomThreads), 0, s, mom, nb, (long long)count, 2, 3);
+    field_moments<4>((const float*)field, count, (double*)moments, (hipStream_t)stream);
     return launched("nbe_field_moments4");
 }
 

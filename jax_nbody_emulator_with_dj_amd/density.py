@@ -67,7 +67,7 @@ __all__ = ["paint_density", "deconvolve_mas", "power_spectrum", "minkowski_funct
 
 WORDERS = {1: "NGP", 2: "CIC", 3: "TSC", 4: "PCS"}
 _UNIT = 2.0 ** 22           # fixed-point units per particle mass (include/nbe.h, nbe_paint_mesh)
-_KUNIT = 2.0 ** -36         # units of the |k| sums of nbe_power_spectrum
+_KEXP = 36                  # the |k| sums of nbe_power_spectrum are in units of 2^-36
 _MF_MAX_N = 2048            # include/nbe.h: NBE_MF_MAX_N, NBE_MF_MAX_THRESHOLDS, NBE_MOMENTS_WORDS
 _MF_MAX_T = 1024
 _MOMENT_WORDS = 2050
@@ -116,6 +116,14 @@ def _check_worder(worder):
     return int(worder)
 
 
+def _real(v, name, positive=False):
+    """v as a float: a finite (with `positive`, positive) real number that is not a bool."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Real) or not np.isfinite(float(v)) or \
+            (positive and float(v) <= 0):
+        raise ValueError("%s must be a %sfinite number, got %r" % (name, "positive " if positive else "", v))
+    return float(v)
+
+
 def _dtype_name(x):
     return str(x.dtype).replace("torch.", "")
 
@@ -130,12 +138,39 @@ def _check_array(x, name):
     raise ValueError("%s must be a NumPy array or a CUDA torch tensor, got %s" % (name, type(x).__name__))
 
 
+def _cubic(x, name, boxsize, what, noun, lo, hi):
+    """A cubic float32 mesh of size lo .. hi in a cubic box, for the public function `what` (which calls it a `noun`):
+    (array, n, L)."""
+    x = _check_array(x, name)
+    if x.ndim != 3 or len(set(x.shape)) != 1:
+        raise ValueError("%s needs a cubic %s, got shape %s" % (what, noun, tuple(x.shape)))
+    n = int(x.shape[0])
+    if not lo <= n <= hi:
+        raise ValueError("%s: mesh size %d unsupported (%d .. %d)" % (what, n, lo, hi))
+    if _dtype_name(x) != "float32":
+        raise ValueError("%s must be float32, got %s" % (name, _dtype_name(x)))
+    L = _triple(boxsize, "boxsize", "a length")
+    if len(set(L)) != 1:
+        raise ValueError("%s needs a cubic box, got boxsize %s" % (what, L))
+    return x, n, L[0]
+
+
 def _device():
     """The device for host (NumPy) inputs: cuda:<current>.  Raises NBEError when none is visible (no CPU fallback)."""
     if torch is None or not torch.cuda.is_available():
         raise NBEError("density: no HIP device is visible; this library has no CPU fallback")
     _lib.lib()
     return torch.device("cuda", torch.cuda.current_device())
+
+
+def _device_of(x):
+    """Where a public call works: the device of a tensor input, `_device()` for a NumPy input."""
+    return x.device if _is_torch(x) else _device()
+
+
+def _back(x, t):
+    """The result tensor t (or None) in the kind of the input x: NumPy for a NumPy input, t itself for a tensor."""
+    return t if t is None or _is_torch(x) else t.cpu().numpy()
 
 
 def _stream(dev):
@@ -206,12 +241,9 @@ def _validate_shift(velocity, los, velocity_to_length, n, kind_of, what):
     if _dtype_name(v) not in ("float32", "float16"):
         raise ValueError("velocity must be float32 or float16, got %s" % _dtype_name(v))
     _same_kind(kind_of, v, what, "velocity")
-    f = velocity_to_length
-    if f is None:
+    if velocity_to_length is None:
         raise ValueError("velocity_to_length is required with a velocity (rsd_factor(z, Om) for redshift space)")
-    if isinstance(f, (bool, np.bool_)) or not isinstance(f, numbers.Real) or not np.isfinite(float(f)):
-        raise ValueError("velocity_to_length must be a finite number, got %r" % (f,))
-    return v, int(los), float(f)
+    return v, int(los), _real(velocity_to_length, "velocity_to_length")
 
 
 def _same_kind(a, b, name_a, name_b):
@@ -238,8 +270,7 @@ def _validate_field(displacement, quantity, boxsize, res, worder, normalize, fil
         _same_kind(x, q, "displacement", "quantity")
     if normalize not in _NORMALIZE:
         raise ValueError("normalize must be 'density' or 'mean', got %r" % (normalize,))
-    if isinstance(fill, (bool, np.bool_)) or not isinstance(fill, numbers.Real) or not np.isfinite(float(fill)):
-        raise ValueError("fill must be a finite number, got %r" % (fill,))
+    _real(fill, "fill")
     v, los, f = _validate_shift(velocity, los, velocity_to_length, n, q, "quantity")
     return x, q, v, los, f, n, boxsize, res, worder
 
@@ -317,22 +348,20 @@ def paint_density(displacement, boxsize=1000.0, res=512, worder=2, deconvolve=Tr
     x, boxsize, res, worder = _validate_paint(displacement, boxsize, res, worder)
     n = tuple(int(d) for d in x.shape[1:])
     v, los, f = _validate_shift(velocity, los, velocity_to_length, n, x, "displacement")
-    host = not _is_torch(x)
-    dtypes = (torch.float32, torch.float16) if torch else ()
-    xd = _to_device(x, _device() if host else x.device, dtypes)
+    dev = _device_of(x)
+    dtypes = (torch.float32, torch.float16)
+    xd = _to_device(x, dev, dtypes)
     if v is None:
         delta, stats = _paint(xd, boxsize, res, worder, bool(deconvolve))
-        bad = int(stats[1].item())
-        if bad:
-            raise NBEError("paint_density: %d particle(s) have a non-finite or out-of-range position" % bad)
-        return delta.cpu().numpy() if host else delta
-    vd = _los_component(_to_device(v, xd.device, dtypes), los, n)
+        _check_stats(stats, "paint_density", False)
+        return _back(x, delta)
+    vd = _los_component(_to_device(v, dev, dtypes), los, n)
     _, delta, stats = _paint_fields(xd, None, vd, los, f, n, boxsize, res, worder, want_delta=True)
     _check_stats(stats, "paint_density", False)
     if deconvolve:
-        with torch.cuda.device(xd.device):
+        with torch.cuda.device(dev):
             delta = _deconvolve(delta, worder)
-    return delta.cpu().numpy() if host else delta
+    return _back(x, delta)
 
 
 def paint_field(displacement, quantity, boxsize=1000.0, res=512, worder=2, normalize="density", deconvolve=False,
@@ -368,9 +397,8 @@ def paint_field(displacement, quantity, boxsize=1000.0, res=512, worder=2, norma
     more: |S| <= M 2^24 stays below 2^63 only for M < 2^39 units."""
     x, q, v, los, f, n, boxsize, res, worder = _validate_field(displacement, quantity, boxsize, res, worder, normalize,
                                                                fill, velocity, los, velocity_to_length)
-    host = not _is_torch(q)
-    dev = _device() if host else q.device
-    dtypes = (torch.float32, torch.float16) if torch else ()
+    dev = _device_of(q)
+    dtypes = (torch.float32, torch.float16)
     xd = None if x is None else _to_device(x, dev, dtypes)
     qd = _to_device(q, dev, dtypes)
     single = qd.ndim == 3
@@ -385,20 +413,15 @@ def paint_field(displacement, quantity, boxsize=1000.0, res=512, worder=2, norma
             field = torch.stack([_deconvolve(field[c], worder) for c in range(field.shape[0])])
     if single:
         field = field[0]
-    if host:
-        field = field.cpu().numpy()
-        delta = delta.cpu().numpy() if delta is not None else None
-    return (field, delta) if return_delta else field
+    return (_back(q, field), _back(q, delta)) if return_delta else _back(q, field)
 
 
 def rsd_factor(z, Om):
     """(1 + z) / H(z) in (Mpc/h) per (km/s): the comoving displacement of a proper peculiar velocity along the line of
     sight, s = x + v_los (1 + z) / H(z), with cosmology.hubble_rate.  A Python float."""
     from .cosmology import hubble_rate
-    for name, val in (("z", z), ("Om", Om)):
-        if isinstance(val, (bool, np.bool_)) or not isinstance(val, numbers.Real) or not np.isfinite(float(val)):
-            raise ValueError("%s must be a finite number, got %r" % (name, val))
-    return (1.0 + float(z)) / float(hubble_rate(float(z), float(Om)))
+    z, Om = _real(z, "z"), _real(Om, "Om")
+    return (1.0 + z) / float(hubble_rate(z, Om))
 
 
 def deconvolve_mas(delta, worder=2):
@@ -411,11 +434,9 @@ def deconvolve_mas(delta, worder=2):
     if _dtype_name(d) != "float32":
         raise ValueError("delta must be float32, got %s" % _dtype_name(d))
     worder = _check_worder(worder)
-    host = not _is_torch(d)
-    dd = _to_device(d, _device() if host else d.device, (torch.float32,) if torch else ())
-    with torch.cuda.device(dd.device):
-        out = _deconvolve(dd, worder)
-    return out.cpu().numpy() if host else out
+    dev = _device_of(d)
+    with torch.cuda.device(dev):
+        return _back(d, _deconvolve(_to_device(d, dev, (torch.float32,)), worder))
 
 
 def power_spectrum(delta, boxsize=1000.0, other=None):
@@ -425,26 +446,15 @@ def power_spectrum(delta, boxsize=1000.0, other=None):
     delta / other: (n, n, n) float32, NumPy arrays or CUDA tensors on one device.  boxsize: L (scalar, or a 3-tuple of
     equal values).  Returns (k, pk, nmodes), float64 NumPy arrays of n // 2 shells: the mean |k| (h/Mpc for L in Mpc/h),
     the mean P = |delta_k|^2 L^3 / n^6 and the number of modes of the full complex grid."""
-    d = _check_array(delta, "delta")
-    L = _triple(boxsize, "boxsize", "a length")
-    if d.ndim != 3 or len(set(d.shape)) != 1:
-        raise ValueError("power_spectrum needs a cubic mesh, got shape %s" % (tuple(d.shape),))
-    if len(set(L)) != 1:
-        raise ValueError("power_spectrum needs a cubic box, got boxsize %s" % (L,))
-    n = int(d.shape[0])
-    if n < 2 or n > 4096:
-        raise ValueError("power_spectrum: mesh size %d unsupported (2 .. 4096)" % n)
-    if _dtype_name(d) != "float32":
-        raise ValueError("delta must be float32, got %s" % _dtype_name(d))
+    d, n, L = _cubic(delta, "delta", boxsize, "power_spectrum", "mesh", 2, 4096)
     o = None
     if other is not None:
         o = _check_array(other, "other")
         if tuple(o.shape) != tuple(d.shape) or _dtype_name(o) != "float32":
             raise ValueError("other must match delta: float32 %s, got %s %s"
                              % (tuple(d.shape), _dtype_name(o), tuple(o.shape)))
-        if _is_torch(o) != _is_torch(d) or (_is_torch(o) and o.device != d.device):
-            raise ValueError("delta and other must both be NumPy arrays or both tensors on one device")
-    dev = _device() if not _is_torch(d) else d.device
+        _same_kind(d, o, "delta", "other")
+    dev = _device_of(d)
     l = _lib.lib()
     nb = n // 2 + 1
     with torch.cuda.device(dev):
@@ -454,17 +464,21 @@ def power_spectrum(delta, boxsize=1000.0, other=None):
         sums = torch.zeros(3 * nb, dtype=torch.int64, device=dev)
         _lib.check(l.nbe_power_spectrum(_ptr(a), _ptr(b) if b is not None else None, n, _ptr(binmax), _ptr(sums),
                                         _stream(dev)))
-        bm = binmax.cpu().numpy().view(np.float32).astype(np.float64)[1:]
+        bm = binmax.cpu().numpy()[1:]
         sm = sums.cpu().numpy().reshape(3, nb)[:, 1:]
-    cnt = sm[0].astype(np.float64)
-    shell = np.arange(1, nb, dtype=np.float64)
-    kF = 2.0 * np.pi / L[0]
+    return _shell_means(bm, sm[0], sm[1], sm[2], np.arange(1, nb, dtype=np.float64), _KEXP, L, n)
+
+
+def _shell_means(binmax, weight, ksum, psum, koff, kexp, L, n):
+    """(k, pk, modes), float64, from the integer shell sums of nbe_power_spectrum / nbe_shell_filter: binmax the shells'
+    uint32 words, ksum in units of 2^-kexp about koff, psum in units of 2^(e - 32).  pk is NaN in a non-finite shell."""
+    bm = binmax.view(np.float32).astype(np.float64)
+    cnt = weight.astype(np.float64)
     _, e = np.frexp(np.where(np.isfinite(bm), bm, 1.0))
     with np.errstate(invalid="ignore", divide="ignore"):
-        k = (shell + sm[1].astype(np.float64) * _KUNIT / cnt) * kF
-        pk = np.ldexp(sm[2].astype(np.float64), e - 32) / cnt * (L[0] ** 3 / float(n) ** 6)
-    pk = np.where(np.isfinite(bm), pk, np.nan)
-    return k, pk, cnt
+        k = (koff + np.ldexp(ksum.astype(np.float64), -np.asarray(kexp, np.int64)) / cnt) * (2.0 * np.pi / L)
+        pk = np.ldexp(psum.astype(np.float64), e - 32) / cnt * (L ** 3 / float(n) ** 6)
+    return k, np.where(np.isfinite(bm), pk, np.nan), cnt
 
 
 def _mf_thresholds(thresholds):
@@ -484,18 +498,8 @@ def _mf_thresholds(thresholds):
 
 
 def _mf_validate(field, boxsize, thresholds):
-    f = _check_array(field, "field")
-    if f.ndim != 3 or len(set(f.shape)) != 1:
-        raise ValueError("minkowski_functionals needs a cubic (n, n, n) field, got shape %s" % (tuple(f.shape),))
-    n = int(f.shape[0])
-    if not 1 <= n <= _MF_MAX_N:
-        raise ValueError("minkowski_functionals: mesh size %d unsupported (1 .. %d)" % (n, _MF_MAX_N))
-    if _dtype_name(f) != "float32":
-        raise ValueError("field must be float32, got %s" % _dtype_name(f))
-    L = _triple(boxsize, "boxsize", "a length")
-    if len(set(L)) != 1:
-        raise ValueError("minkowski_functionals needs a cubic box, got boxsize %s" % (L,))
-    return f, n, L[0], _mf_thresholds(thresholds)
+    return _cubic(field, "field", boxsize, "minkowski_functionals", "(n, n, n) field", 1, _MF_MAX_N) + \
+        (_mf_thresholds(thresholds),)
 
 
 def _mf_values(counts, n, boxsize):
@@ -540,8 +544,7 @@ def minkowski_functionals(field, boxsize=1000.0, thresholds=None, standardize=Tr
     12.1)."""
     f, n, L, thr = _mf_validate(field, boxsize, thresholds)
     standardize = bool(standardize)
-    host = not _is_torch(f)
-    dev = _device() if host else f.device
+    dev = _device_of(f)
     l = _lib.lib()
     T = int(thr.size)
     order = np.argsort(thr, kind="stable")
@@ -610,22 +613,8 @@ def _shell_modes(lo2, hi2):
 
 
 def _bk_validate(delta, boxsize, k1, k2, theta, dk, mas_worder):
-    d = _check_array(delta, "delta")
-    if d.ndim != 3 or len(set(d.shape)) != 1:
-        raise ValueError("bispectrum needs a cubic (n, n, n) field, got shape %s" % (tuple(d.shape),))
-    n = int(d.shape[0])
-    if not _BK_MIN_N <= n <= _BK_MAX_N:
-        raise ValueError("bispectrum: mesh size %d unsupported (%d .. %d)" % (n, _BK_MIN_N, _BK_MAX_N))
-    if _dtype_name(d) != "float32":
-        raise ValueError("delta must be float32, got %s" % _dtype_name(d))
-    L = _triple(boxsize, "boxsize", "a length")
-    if len(set(L)) != 1:
-        raise ValueError("bispectrum needs a cubic box, got boxsize %s" % (L,))
-    vals = {}
-    for name, v in (("k1", k1), ("k2", k2), ("dk", dk)):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Real) or not np.isfinite(float(v)) or float(v) <= 0:
-            raise ValueError("%s must be a positive finite number, got %r" % (name, v))
-        vals[name] = float(v)
+    d, n, L = _cubic(delta, "delta", boxsize, "bispectrum", "(n, n, n) field", _BK_MIN_N, _BK_MAX_N)
+    vals = {name: _real(v, name, positive=True) for name, v in (("k1", k1), ("k2", k2), ("dk", dk))}
     try:
         th = np.asarray(theta, dtype=np.float64).ravel()
     except (TypeError, ValueError):
@@ -636,7 +625,7 @@ def _bk_validate(delta, boxsize, k1, k2, theta, dk, mas_worder):
         raise ValueError("theta must be finite angles in [0, pi]")
     if mas_worder is not None:
         mas_worder = _check_worder(mas_worder)
-    kF = 2.0 * np.pi / L[0]
+    kF = 2.0 * np.pi / L
     ka1, ka2, dk = vals["k1"] / kF, vals["k2"] / kF, vals["dk"]
     if 2.0 * (ka1 + ka2) + 1.5 * dk >= n:
         raise ValueError("bispectrum: 2 (k1 + k2) / k_F + 1.5 dk = %.6g reaches the mesh size %d: triangles would close "
@@ -648,7 +637,7 @@ def _bk_validate(delta, boxsize, k1, k2, theta, dk, mas_worder):
         if not len(modes[i]):
             raise ValueError("bispectrum: shell %d (k%d = %g, |m| in [%g, %g)) holds no mode of the mesh"
                              % (i + 1, i + 1, vals["k%d" % (i + 1)], max(kappa[i] - dk / 2, 0.0), kappa[i] + dk / 2))
-    return d, n, L[0], th, kappa, lo2, hi2, modes, mas_worder
+    return d, n, L, th, kappa, lo2, hi2, modes, mas_worder
 
 
 def _bk_shell_params(n, lo2, hi2):
@@ -725,8 +714,7 @@ def bispectrum(delta, boxsize=1000.0, k1=0.1, k2=0.1, theta=None, dk=1.0, mas_wo
     if theta is None:
         theta = np.linspace(0.0, np.pi, 25)
     d, n, L, th, kappa, lo2, hi2, modes, mas_worder = _bk_validate(delta, boxsize, k1, k2, theta, dk, mas_worder)
-    host = not _is_torch(d)
-    dev = _device() if host else d.device
+    dev = _device_of(d)
     l = _lib.lib()
     T, S = int(th.size), int(th.size) + 2
     kF = 2.0 * np.pi / L
@@ -789,25 +777,22 @@ def bispectrum(delta, boxsize=1000.0, k1=0.1, k2=0.1, theta=None, dk=1.0, mas_wo
             mark("triangle_counts")
             hist = hist_d.cpu().numpy()
         tri = out.cpu().numpy()
-        bm = binmax.cpu().numpy().view(np.float32).astype(np.float64)
+        bm = binmax.cpu().numpy()
         sm = sums.cpu().numpy()
         if _timings is not None:
             torch.cuda.synchronize(dev)
             for (_, a), (name, b) in zip(ev[:-1], ev[1:]):
                 _timings[name] = _timings.get(name, 0.0) + a.elapsed_time(b)
             _timings["batch"] = batch
-    if not np.isfinite(bm).all() or not np.isfinite(tri).all():
+    if not np.isfinite(bm.view(np.float32)).all() or not np.isfinite(tri).all():
         raise NBEError("bispectrum: the field has voxels that are not finite")
     ntri = np.zeros(T, np.int64)
     if hist is not None:
         cum = np.cumsum(hist)
         ntri = cum[np.searchsorted(edges, hi2[2:])] - cum[np.searchsorted(edges, lo2[2:])]
         ntri = np.where(hi2[2:] > lo2[2:], ntri, 0).astype(np.int64)
-    cnt = sm[:, 0].astype(np.float64)
-    _, e = np.frexp(bm)
+    k, pk, _ = _shell_means(bm, sm[:, 0], sm[:, 1], sm[:, 2], par[:, 2], par[:, 3], L, n)
     with np.errstate(invalid="ignore", divide="ignore"):
-        k = (par[:, 2] + np.ldexp(sm[:, 1].astype(np.float64), -par[:, 3].astype(np.int64)) / cnt) * kF
-        pk = np.ldexp(sm[:, 2].astype(np.float64), e - 32) / cnt * (L ** 3 / float(n) ** 6)
         B = np.where(ntri > 0, tri * (L ** 6 / float(n) ** 3) / ntri, np.nan)
         Q = B / (pk[0] * pk[1] + pk[1] * pk[2:] + pk[2:] * pk[0])
     return {"theta": th.copy(), "k3": kappa[2:] * kF, "B": B, "Q": Q, "ntriangles": ntri, "pk": pk, "k": k,
@@ -836,8 +821,7 @@ def field_statistics(field):
     voxels that depends on their number only and in a fixed order: the same bits on every call.  Returns a dict of Python
     floats: mean, std, skewness, kurtosis_excess; the last two are 0.0 when std <= 0, as in the reference."""
     f, count = _onepoint_validate(field, "field_statistics")
-    host = not _is_torch(f)
-    dev = _device() if host else f.device
+    dev = _device_of(f)
     l = _lib.lib()
     with torch.cuda.device(dev):
         x = _to_device(f, dev, (torch.float32,))
@@ -851,14 +835,12 @@ def field_statistics(field):
 
 def pdf_edges(lo, hi, nbins):
     """The float64 edges np.linspace(lo, hi, nbins + 1) of field_pdf, validated."""
-    for name, v in (("lo", lo), ("hi", hi)):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Real) or not np.isfinite(float(v)):
-            raise ValueError("%s must be a finite number, got %r" % (name, v))
+    flo, fhi = _real(lo, "lo"), _real(hi, "hi")
     if isinstance(nbins, (bool, np.bool_)) or not isinstance(nbins, numbers.Integral) or not 2 <= int(nbins) <= _PDF_MAX_BINS:
         raise ValueError("nbins must be an int in 2 .. %d, got %r" % (_PDF_MAX_BINS, nbins))
-    if not float(hi) > float(lo):
+    if not fhi > flo:
         raise ValueError("hi must exceed lo, got lo %r, hi %r" % (lo, hi))
-    edges = np.linspace(float(lo), float(hi), int(nbins) + 1)
+    edges = np.linspace(flo, fhi, int(nbins) + 1)
     if not (np.diff(edges) > 0).all():
         raise ValueError("lo %r and hi %r are too close for %d distinct float64 edges" % (lo, hi, nbins))
     return edges
@@ -883,8 +865,7 @@ def field_pdf(field, lo, hi, nbins=120):
     f, count = _onepoint_validate(field, "field_pdf")
     edges = pdf_edges(lo, hi, nbins)
     nbins = int(nbins)
-    host = not _is_torch(f)
-    dev = _device() if host else f.device
+    dev = _device_of(f)
     l = _lib.lib()
     with torch.cuda.device(dev):
         x = _to_device(f, dev, (torch.float32,))

@@ -2,6 +2,8 @@
 validation before any device work, the missing-device error and the CLI flags."""
 
 import argparse
+import os
+import re
 
 import numpy as np
 import pytest
@@ -144,6 +146,27 @@ def test_density_names_stay_out_of_the_package_namespace():
     for name in D.__all__:
         assert name not in J.__all__
     assert "density" in J.__doc__
+
+
+def test_mirrored_constants_equal_the_header():
+    """density.py sizes its buffers and validates against limits that include/nbe.h defines: read as data, compared."""
+    header = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "nbe.h")
+    H = {}
+    for name, value in re.findall(r"^#define (NBE_\w+)[ \t]+(\(?[-\w <]+\)?)", open(header).read(), re.M):
+        m = re.fullmatch(r"\(?\s*(-?\d+)(?:LL)?(?:\s*<<\s*(\d+))?\s*\)?", value.strip())
+        if m:
+            H[name] = int(m.group(1)) << int(m.group(2) or 0)
+    assert D._MF_MAX_N == H["NBE_MF_MAX_N"]
+    assert D._MF_MAX_T == H["NBE_MF_MAX_THRESHOLDS"]
+    assert D._MOMENT_WORDS == H["NBE_MOMENTS_WORDS"]
+    assert (D._BK_MIN_N, D._BK_MAX_N) == (H["NBE_BK_MIN_N"], H["NBE_BK_MAX_N"])
+    assert D._BK_MAX_T == H["NBE_BK_MAX_SHELLS"] - 2
+    assert D._BK_PARTIALS == H["NBE_BK_PARTIALS"]
+    assert D._MOMENT4_WORDS == H["NBE_MOMENTS4_WORDS"]
+    assert D._PDF_MAX_BINS == H["NBE_PDF_MAX_BINS"]
+    assert D._ONEPOINT_MAX == H["NBE_ONEPOINT_MAX_VOXELS"] == 1 << 40
+    assert D._MAX_CHANNELS == H["NBE_PAINT_MAX_CHANNELS"]
+    assert D._NORMALIZE == {"density": H["NBE_FIELD_DENSITY"], "mean": H["NBE_FIELD_MEAN"]}
 
 
 # ---- CLI ---------------------------------------------------------------------------------------------------------------
