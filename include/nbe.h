@@ -377,6 +377,52 @@ int nbe_field_moments4(const void* field, int64_t count, void* moments, void* st
 int nbe_field_histogram(const void* field, int64_t count, double lo, double hi, const void* edges, int nbins,
                         void* counts, void* stream);
 
+/* ---- Input fields (no context) ---------------------------------------------------------------------
+ * The reference's pipeline brings a linear density field to the particle grid (resize_density_grid) and turns it into
+ * the first-order LPT displacement before process_box (scripts/core.py:302-409).  These are the passes between the
+ * caller's transforms.  Pointers, `stream` and asynchrony as for "Density".  A spectrum is torch's
+ * row-major half spectrum (n, n, n/2+1) complex64 of an n^3 real field, the unnormalised forward transform; a mode has the
+ * integer wave vector m, k = 2 pi m / L, each component in (-n/2, n/2], so an even axis stores its Nyquist row as +n/2.
+ * Factors are formed in float64 and every output word is rounded to float32 once.  No atomics: the results do not depend
+ * on the launch geometry. */
+#define NBE_LPT_MIN_N 2
+#define NBE_LPT_MAX_N 2048
+/* replaces dj.with_lpt(n_order=1) / dj.evaluate_lpt_psi_at_a(a, n_order=1) (scripts/core.py:396-397): psi_spectrum =
+ * (3, n, n, n/2+1) receives psi_c = scale i k_c / |k|^2 delta_k, so that div psi = -scale delta.  psi is 0 at m = 0, and
+ * component c is 0 where n is even and |m_c| = n/2: a Nyquist row has no sign, so its derivative is set to zero, which
+ * keeps the field real. */
+int nbe_zeldovich_spectrum(const void* spectrum, int64_t n, double boxsize, double scale, void* psi_spectrum,
+                           void* stream);
+/* replaces the "fourier" method of upsample_density_with_discodj (scripts/utils.py:186-234), and is its inverse for
+ * n_out < n_in: destination mode m = (n_out / n_in)^3 times the source value at m, where the source value at -m is the
+ * conjugate of the stored mirror mode.  n_out > n_in: 0 if any |m_c| > n_in / 2, and a factor 1/2 per axis with
+ * 2 |m_c| = n_in (the coarse Nyquist row is split evenly onto +-n_in/2).  n_out < n_in: a destination Nyquist component
+ * (2 m_c = n_out) is the sum of the source values at m_c = +n_out/2 and -n_out/2, over all sign combinations of such
+ * axes, added in float64.  sphere != 0: modes with 4 |m|^2 > n_in^2 (integers) are 0.  dst must not alias src. */
+int nbe_spectrum_resize(const void* src, int64_t n_in, void* dst, int64_t n_out, int sphere, void* stream);
+/* replaces _upsample_density_mode_inject_numpy / _jax (scripts/utils.py:261-346, :349-425), n_out >= n_in.  Inside the
+ * sphere 4 |m|^2 <= n_in^2: the bits of nbe_spectrum_resize(sphere = 1).  Outside: a Gaussian draw with E|F|^2 = sigma^2,
+ * sigma = n_out^3 sqrt(P(|k|) / L^3).  P in float64 from k_table / pk_table (ntable >= 2 float64 ON THE DEVICE, k
+ * strictly increasing): linear in k between the points (np.interp), pk_table[0] below them, exp(tail_intercept +
+ * tail_slope ln k) above k_table[ntable-1], clamped at 0.  The draw is Philox4x32-10 with key (seed low word, seed high
+ * word) and counter (r0, r1, i2, 0), where (r0, r1, i2) is the mode's index in dst; on the planes i2 = 0 and (n_out even)
+ * i2 = n_out/2 the rows (i0, i1) and ((n - i0) % n, (n - i1) % n) form a pair, the one with the smaller i0 n + i1
+ * supplies the counter and the other takes the complex conjugate.  U1 = (x0 + 1/2) 2^-32, U2 = (x1 + 1/2) 2^-32,
+ * g = sqrt(-2 ln U1) (cospi(2 U2) + i sinpi(2 U2)) in float64; F = sigma Re g for a mode that is its own mirror image and
+ * sigma g / sqrt(2) otherwise.  dst is the half spectrum of a real field by construction. */
+int nbe_spectrum_inject(const void* src, int64_t n_in, void* dst, int64_t n_out, const void* k_table,
+                        const void* pk_table, int ntable, double tail_slope, double tail_intercept, double boxsize,
+                        uint64_t seed, void* stream);
+/* replaces Pylians' FT_filter(boxsize, sigma, n, "Gaussian") and field_smoothing (scripts/utils.py:590-591): in place,
+ * spectrum *= exp(-|k|^2 sigma^2 / 2) = exp(-2 pi^2 |m|^2 sigma_over_L^2) */
+int nbe_gaussian_filter(void* spectrum, int64_t n, double sigma_over_L, void* stream);
+/* replaces downsample_density_block_average (scripts/utils.py:531-555): dst (n_out^3 float32) = the mean of each
+ * (n_in / n_out)^3 block of src (n_in^3 float32), summed in float64 in a fixed order; n_out divides n_in */
+int nbe_block_average(const void* src, int64_t n_in, void* dst, int64_t n_out, void* stream);
+/* replaces the "linear" method of upsample_density_with_discodj (scripts/utils.py:186-234): dst (n_out^3 float32) =
+ * periodic trilinear interpolation of src (n_in^3 float32) at the nodes i n_in / n_out; n_in divides n_out */
+int nbe_trilinear_upsample(const void* src, int64_t n_in, void* dst, int64_t n_out, void* stream);
+
 /* ---- test / measurement hooks (not part of the reference surface) ------------------------------ */
 
 /* One layer through the production kernels, host NCDHW in / out.  kind: 0 conv3 (VALID 3x3x3),

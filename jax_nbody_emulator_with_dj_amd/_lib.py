@@ -12,7 +12,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NBE_LIB") or os.path.join(_HERE, "libnbe.so")   # NBE_LIB: timing-probe builds only
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("nbe_kernels.hip", "nbe_kernels_h3.hip", "nbe_density.hip", "nbe_engine.cpp")
+SOURCES = ("nbe_kernels.hip", "nbe_kernels_h3.hip", "nbe_density.hip", "nbe_lpt.hip", "nbe_engine.cpp")
 
 
 class NBEError(RuntimeError):
@@ -97,6 +97,13 @@ SIGNATURES = {
     "nbe_field_moments4": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "nbe_field_histogram": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p,
                                       C.c_void_p]),
+    "nbe_zeldovich_spectrum": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "nbe_spectrum_resize": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "nbe_spectrum_inject": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+                                      C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_void_p]),
+    "nbe_gaussian_filter": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_void_p]),
+    "nbe_block_average": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "nbe_trilinear_upsample": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "nbe_growth_factor": (C.c_double, [C.c_double, C.c_double]),
     "nbe_vel_norm": (C.c_double, [C.c_double, C.c_double]),
     "nbe_test_layer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
@@ -143,7 +150,7 @@ def source_hash():
 def build(force=False, verbose=False):
     """Compile the HIP sources for gfx950 into libnbe.so (in-tree)."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, "nbe_kernels.h"), os.path.join(CSRC, "nbe_kernels_internal.h"), os.path.join(CSRC, "nbe_kernels_wino.h"), os.path.join(CSRC, "nbe_kernels_head.h"), os.path.join(_HERE, "..", "include", "nbe.h")]
+    deps = srcs + [os.path.join(CSRC, "nbe_kernels.h"), os.path.join(CSRC, "nbe_kernels_internal.h"), os.path.join(CSRC, "nbe_kernels_wino.h"), os.path.join(CSRC, "nbe_kernels_head.h"), os.path.join(CSRC, "nbe_spectral.h"), os.path.join(_HERE, "..", "include", "nbe.h")]
     if not force and os.path.exists(LIB_PATH):
         if all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
             return LIB_PATH

@@ -15,13 +15,15 @@
 // into the global mesh (the same integers, so the same bits) and is counted in stats[0].
 //
 // Shared pieces, each written once.  Both moment entry points and the triple sums reduce with moments_pass_kernel<CENTRED,
-// ORDER> / triple_sums_kernel, block_sum and sum_finish_kernel.  The spectral kernels decode a mode with half_mode and
+// ORDER> / triple_sums_kernel, block_sum and sum_finish_kernel.  The spectral kernels decode a mode with half_mode
+// (nbe_spectral.h, with fail, launched and grid_for, which nbe_lpt.hip shares) and
 // the shell sums of the power spectrum and of the shell filter share power_exponent and shell_add.  upper_bound bins
 // the Minkowski thresholds and the triangle counts; with_worder turns worder into a template argument.  The two
 // painters (paint_kernel, paint_field_kernel) still carry their own copies of the tile pass: their positions are
 // i a + psi s as the compiler contracts it, and moving that expression changes which product is fused.
 
 #include "../../include/nbe.h"
+#include "nbe_spectral.h"
 
 #include <hip/hip_runtime.h>
 
@@ -31,8 +33,6 @@
 #include <cstdint>
 #include <cstdio>
 #include <type_traits>
-
-namespace nbe { int api_fail(const char* msg); }
 
 namespace {
 
@@ -433,23 +433,6 @@ __global__ void mesh_to_field_kernel(ToFieldArgs A) {
         }
     }
     if (over) atomicAdd(&A.stats[2], over);
-}
-
-// frequency index of position i on an axis of n points (numpy.fft.fftfreq * n)
-__device__ inline long long freq(long long i, long long n) { return i <= n / 2 ? i : i - n; }
-
-// Mode i of the row-major half spectrum (r0, r1, r2/2+1) of an (r0, r1, r2) mesh: its integer frequencies, their
-// |m|^2 = q and its weight in the full grid (the modes whose mirror image the half spectrum leaves out count twice)
-struct HalfMode { long long f0, f1, f2, q; int w; };
-
-__device__ inline HalfMode half_mode(long long i, long long r0, long long r1, long long r2) {
-    const long long h2 = r2 / 2 + 1;
-    const long long i2 = i % h2, r = i / h2, i1 = r % r1, i0 = r / r1;
-    HalfMode m;
-    m.f0 = freq(i0, r0); m.f1 = freq(i1, r1); m.f2 = i2;
-    m.q = m.f0 * m.f0 + m.f1 * m.f1 + i2 * i2;
-    m.w = (i2 == 0 || (r2 % 2 == 0 && i2 == r2 / 2)) ? 1 : 2;
-    return m;
 }
 
 __device__ inline double sinc_pi(long long f, long long n) {            // sinc(pi f / n), sinc(x) = sin(x) / x
@@ -1005,25 +988,6 @@ __global__ __launch_bounds__(kBkThreads) void field_histogram_kernel(PdfArgs A) 
         for (int c = 0; c < copies; ++c) v += hist[c * (nb + 2) + i];
         if (v) atomicAdd(&A.counts[i], (unsigned long long)v);
     }
-}
-
-int fail(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return nbe::api_fail(buf);
-}
-
-int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("%s: launch failed: %s", what, hipGetErrorString(e));
-}
-
-int grid_for(long long n, int threads) {
-    long long g = (n + threads - 1) / threads;
-    return (int)(g < 1 ? 1 : g > 65536 ? 65536 : g);
 }
 
 // mom[0] = mean, mom[1] = std and for ORDER 4 mom[2], mom[3] = the third and fourth central moments; the partials start at

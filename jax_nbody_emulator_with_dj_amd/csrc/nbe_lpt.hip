@@ -1,0 +1,374 @@
+// The emulator's input (include/nbe.h, "Input fields"): a linear density field brought to the particle grid and turned
+// into the first-order LPT displacement.  Replaces resize_density_grid and its helpers (scripts/utils.py:186-234,
+// :261-346, :349-425, :531-555, :590-591) and dj.evaluate_lpt_psi_at_a(n_order=1) (scripts/core.py:396-397).  The
+// transforms are the caller's (rocFFT); these are the passes between them.  No context: no weights.
+//
+// Every kernel walks rows: a (64, 4) workgroup takes four rows (i0, i1) of the destination at a time, decodes the row
+// once (the only 64-bit division) and strides its 64 lanes along the contiguous axis, so that a wave-instruction reads
+// and writes one run of a row.  Factors are formed in float64 and every output word is rounded to float32 once.  No LDS,
+// no atomics: every destination word has one writer, so the results do not depend on the launch geometry.
+//
+// Spectra are torch's row-major half spectra (n, n, n/2+1) complex64.  Wave vectors are integers m, k = 2 pi m / L; axis
+// position i holds m = freq(i, n) (nbe_spectral.h), so an even axis stores its Nyquist row as +n/2.
+
+#include "../../include/nbe.h"
+#include "nbe_spectral.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+namespace {
+
+constexpr int kLanes = 64;              // along the contiguous axis
+constexpr int kRows = 4;                // rows per workgroup
+constexpr double kPi = 3.141592653589793;
+
+#define NBE_FOR_ROWS(r, rows) \
+    for (long long r = blockIdx.x * (long long)kRows + threadIdx.y; r < (rows); r += (long long)gridDim.x * kRows)
+
+// ---- first-order LPT ---------------------------------------------------------------------------------------------------
+
+// psi_c = scale i k_c / |k|^2 delta = i c m_c / |m|^2 delta with c = scale L / (2 pi); i (x + i y) = -y + i x
+__global__ __launch_bounds__(kLanes * kRows) void zeldovich_kernel(const float2* __restrict__ delta,
+                                                                   float2* __restrict__ psi, long long n, double c) {
+    const long long h = n / 2 + 1, rows = n * n, plane = rows * h;
+    const long long nyq = n % 2 == 0 ? n / 2 : -1;          // the position of a row without a sign
+    NBE_FOR_ROWS(r, rows) {
+        const long long i0 = r / n, i1 = r - i0 * n;
+        const long long m0 = freq(i0, n), m1 = freq(i1, n), q01 = m0 * m0 + m1 * m1;
+        const double c0 = i0 == nyq ? 0.0 : c * (double)m0, c1 = i1 == nyq ? 0.0 : c * (double)m1;
+        const float2* src = delta + r * h;
+        float2* dst = psi + r * h;
+        for (long long i2 = threadIdx.x; i2 < h; i2 += kLanes) {
+            const long long q = q01 + i2 * i2;
+            const double inv = q ? 1.0 / (double)q : 0.0;
+            const double f0 = c0 * inv, f1 = c1 * inv, f2 = i2 == nyq ? 0.0 : c * (double)i2 * inv;
+            const float2 v = src[i2];
+            dst[i2] = make_float2((float)(-f0 * v.y), (float)(f0 * v.x));
+            dst[plane + i2] = make_float2((float)(-f1 * v.y), (float)(f1 * v.x));
+            dst[2 * plane + i2] = make_float2((float)(-f2 * v.y), (float)(f2 * v.x));
+        }
+    }
+}
+
+// ---- Fourier interpolation -----------------------------------------------------------------------------------------------
+
+// The source wave numbers that feed destination wave number m on one axis: none (cnt 0) beyond the source's band, one
+// (with weight 1/2 on an even source's Nyquist row when upsampling, which splits that row evenly onto +-n_in/2), or both
+// signs for a destination Nyquist row when downsampling.
+struct AxisTerms { int cnt; long long m[2]; double w; };
+
+__device__ inline AxisTerms axis_terms(long long m, long long n_in, long long n_out) {
+    AxisTerms t;
+    t.cnt = 1; t.m[0] = m; t.m[1] = -m; t.w = 1.0;
+    const long long a = m < 0 ? -m : m;
+    if (n_out > n_in) {
+        if (2 * a > n_in) t.cnt = 0;
+        else if (2 * a == n_in) t.w = 0.5;
+    } else if (n_out < n_in && 2 * a == n_out) {
+        t.cnt = 2;
+    }
+    return t;
+}
+
+// Where the terms of a destination row (m0, m1) start in the source half spectrum: pos for a source wave number along
+// axis 2 that is >= 0, neg for a negative one, which is the conjugate of the stored mode at (-a, -b, -c).
+struct RowTerms { AxisTerms t0, t1; long long pos[2][2], neg[2][2]; long long q01; };
+
+__device__ inline long long axis_index(long long m, long long n) { return m < 0 ? m + n : m; }
+
+__device__ inline RowTerms row_terms(long long i0, long long i1, long long n_in, long long n_out) {
+    const long long m0 = freq(i0, n_out), m1 = freq(i1, n_out), h_in = n_in / 2 + 1;
+    RowTerms R;
+    R.t0 = axis_terms(m0, n_in, n_out);
+    R.t1 = axis_terms(m1, n_in, n_out);
+    R.q01 = m0 * m0 + m1 * m1;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const bool live = a < R.t0.cnt && b < R.t1.cnt;          // indices of dead terms are never formed
+            const long long ma = live ? R.t0.m[a] : 0, mb = live ? R.t1.m[b] : 0;
+            R.pos[a][b] = (axis_index(ma, n_in) * n_in + axis_index(mb, n_in)) * h_in;
+            R.neg[a][b] = (axis_index(-ma, n_in) * n_in + axis_index(-mb, n_in)) * h_in;
+        }
+    return R;
+}
+
+// Destination mode (row R, i2) of the resized spectrum: scale * w * the sum of its source terms, added in float64 in the
+// fixed order (axis 0, axis 1, axis 2) and multiplied once, so that no product can be fused into a sum and every kernel
+// that calls this gets the same bits.
+__device__ inline float2 resized_mode(const float2* __restrict__ src, const RowTerms& R, long long i2, long long n_in,
+                                      long long n_out, double scale, int sphere) {
+    const AxisTerms t2 = axis_terms(i2, n_in, n_out);
+    const long long q = R.q01 + i2 * i2;
+    if (R.t0.cnt == 0 || R.t1.cnt == 0 || t2.cnt == 0 || (sphere && 4 * q > n_in * n_in)) return make_float2(0.0f, 0.0f);
+    double re = 0.0, im = 0.0;
+#pragma unroll                                              // constant indices keep the terms in registers
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                if (a >= R.t0.cnt || b >= R.t1.cnt || c >= t2.cnt) continue;
+                const long long mc = t2.m[c];
+                const float2 v = mc >= 0 ? src[R.pos[a][b] + mc] : src[R.neg[a][b] - mc];
+                re += (double)v.x;
+                im += mc >= 0 ? (double)v.y : -(double)v.y;
+            }
+    const double f = scale * (R.t0.w * R.t1.w * t2.w);
+    return make_float2((float)(re * f), (float)(im * f));
+}
+
+__global__ __launch_bounds__(kLanes * kRows) void spectrum_resize_kernel(const float2* __restrict__ src, long long n_in,
+                                                                         float2* __restrict__ dst, long long n_out,
+                                                                         double scale, int sphere) {
+    const long long h = n_out / 2 + 1;
+    NBE_FOR_ROWS(r, n_out * n_out) {
+        const long long i0 = r / n_out, i1 = r - i0 * n_out;
+        const RowTerms R = row_terms(i0, i1, n_in, n_out);
+        float2* out = dst + r * h;
+        for (long long i2 = threadIdx.x; i2 < h; i2 += kLanes)
+            out[i2] = resized_mode(src, R, i2, n_in, n_out, scale, sphere);
+    }
+}
+
+// ---- mode injection --------------------------------------------------------------------------------------------------------
+
+// Philox4x32-10 (Salmon et al. 2011): counter c, key (k0, k1)
+__device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+    for (int round = 0; round < 10; ++round) {
+        const uint64_t p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+        c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
+struct InjectArgs {
+    const float2* src; float2* dst;
+    long long n_in, n_out;
+    const double* k_table; const double* pk_table; int ntable;
+    double tail_slope, tail_intercept;
+    double kf;                  // 2 pi / L
+    double amp;                 // n_out^3 / sqrt(L^3): sigma = amp sqrt(P)
+    double scale;               // (n_out / n_in)^3
+    uint32_t key0, key1;
+};
+
+// P(k): np.interp inside the table, pk_table[0] below it, the fitted power law above it, clamped at 0
+__device__ inline double table_power(const InjectArgs& A, double k) {
+    const double* kt = A.k_table;
+    const double* pt = A.pk_table;
+    const int last = A.ntable - 1;
+    double p;
+    if (k < kt[0]) p = pt[0];
+    else if (k > kt[last]) p = exp(A.tail_intercept + A.tail_slope * log(k));
+    else if (k == kt[last]) p = pt[last];
+    else {
+        int lo = 0, hi = last;                              // kt[lo] <= k < kt[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) / 2;
+            if (kt[mid] <= k) lo = mid; else hi = mid;
+        }
+        const double slope = (pt[lo + 1] - pt[lo]) / (kt[lo + 1] - kt[lo]);
+        p = slope * (k - kt[lo]) + pt[lo];
+    }
+    return p > 0.0 ? p : 0.0;
+}
+
+__global__ __launch_bounds__(kLanes * kRows) void spectrum_inject_kernel(InjectArgs A) {
+    const long long n = A.n_out, h = n / 2 + 1;
+    const long long nyq = n % 2 == 0 ? n / 2 : -1;
+    NBE_FOR_ROWS(r, n * n) {
+        const long long i0 = r / n, i1 = r - i0 * n;
+        const RowTerms R = row_terms(i0, i1, A.n_in, n);
+        // on the planes that are their own mirror image, (i0, i1) and its mirror row form a pair: the smaller index draws
+        const long long p0 = i0 ? n - i0 : 0, p1 = i1 ? n - i1 : 0, mirror = p0 * n + p1;
+        float2* out = A.dst + r * h;
+        for (long long i2 = threadIdx.x; i2 < h; i2 += kLanes) {
+            const long long q = R.q01 + i2 * i2;
+            if (4 * q <= A.n_in * A.n_in) {
+                out[i2] = resized_mode(A.src, R, i2, A.n_in, n, A.scale, 1);
+                continue;
+            }
+            const bool paired = i2 == 0 || i2 == nyq;
+            const bool second = paired && mirror < r, self = paired && mirror == r;
+            uint32_t x[4] = {(uint32_t)(second ? p0 : i0), (uint32_t)(second ? p1 : i1), (uint32_t)i2, 0u};
+            philox4x32_10(x, A.key0, A.key1);
+            const double u1 = ((double)x[0] + 0.5) * 0x1p-32, u2 = ((double)x[1] + 0.5) * 0x1p-32;
+            double s, c;
+            sincospi(2.0 * u2, &s, &c);
+            const double sigma = A.amp * sqrt(table_power(A, A.kf * sqrt((double)q)));
+            const double mag = sigma * sqrt(-2.0 * log(u1));
+            if (self) {
+                out[i2] = make_float2((float)(mag * c), 0.0f);
+            } else {
+                const double g = mag * 0.7071067811865476;
+                out[i2] = make_float2((float)(g * c), (float)(second ? -(g * s) : g * s));
+            }
+        }
+    }
+}
+
+// ---- Gaussian filter, block average, trilinear interpolation ---------------------------------------------------------------
+
+// in place: exp(-|k|^2 sigma^2 / 2) = exp(a |m|^2), a = -2 pi^2 (sigma / L)^2
+__global__ __launch_bounds__(kLanes * kRows) void gaussian_filter_kernel(float2* __restrict__ f, long long n, double a) {
+    const long long h = n / 2 + 1;
+    NBE_FOR_ROWS(r, n * n) {
+        const long long i0 = r / n, i1 = r - i0 * n;
+        const long long m0 = freq(i0, n), m1 = freq(i1, n), q01 = m0 * m0 + m1 * m1;
+        float2* row = f + r * h;
+        for (long long i2 = threadIdx.x; i2 < h; i2 += kLanes) {
+            const double w = exp(a * (double)(q01 + i2 * i2));
+            const float2 v = row[i2];
+            row[i2] = make_float2((float)(v.x * w), (float)(v.y * w));
+        }
+    }
+}
+
+// mean of each ratio^3 block, summed in float64 in the order (a, b, c) of the block's axes
+__global__ __launch_bounds__(kLanes * kRows) void block_average_kernel(const float* __restrict__ src, long long n_in,
+                                                                       float* __restrict__ dst, long long n_out) {
+    const long long ratio = n_in / n_out;
+    const double cells = (double)(ratio * ratio * ratio);
+    NBE_FOR_ROWS(r, n_out * n_out) {
+        const long long i0 = r / n_out, i1 = r - i0 * n_out;
+        const float* block = src + (i0 * ratio * n_in + i1 * ratio) * n_in;
+        float* out = dst + r * n_out;
+        for (long long i2 = threadIdx.x; i2 < n_out; i2 += kLanes) {
+            double sum = 0.0;
+            for (long long a = 0; a < ratio; ++a)
+                for (long long b = 0; b < ratio; ++b) {
+                    const float* p = block + (a * n_in + b) * n_in + i2 * ratio;
+                    if (ratio == 2) {                       // the rows of a pair of cells: one 8-byte load per lane
+                        const float2 v = *reinterpret_cast<const float2*>(p);
+                        sum += (double)v.x;
+                        sum += (double)v.y;
+                    } else {
+                        for (long long c = 0; c < ratio; ++c) sum += (double)p[c];
+                    }
+                }
+            out[i2] = (float)(sum / cells);
+        }
+    }
+}
+
+// periodic trilinear interpolation at the fine nodes i n_in / n_out (an integer ratio): nested lerps in float64, so that
+// a fine node on a coarse node (t = 0) returns the coarse value itself
+__device__ inline double lerp(double a, double b, double t) { return (1.0 - t) * a + t * b; }
+
+__global__ __launch_bounds__(kLanes * kRows) void trilinear_kernel(const float* __restrict__ src, long long n_in,
+                                                                   float* __restrict__ dst, long long n_out) {
+    const int ratio = (int)(n_out / n_in), ni = (int)n_in;
+    const double step = 1.0 / (double)ratio;
+    NBE_FOR_ROWS(r, n_out * n_out) {
+        const long long i0 = r / n_out, i1 = r - i0 * n_out;
+        const long long j0 = i0 / ratio, j1 = i1 / ratio;
+        const double t0 = (double)(i0 - j0 * ratio) * step, t1 = (double)(i1 - j1 * ratio) * step;
+        const long long j0p = j0 + 1 == n_in ? 0 : j0 + 1, j1p = j1 + 1 == n_in ? 0 : j1 + 1;
+        const float* r00 = src + (j0 * n_in + j1) * n_in;
+        const float* r01 = src + (j0 * n_in + j1p) * n_in;
+        const float* r10 = src + (j0p * n_in + j1) * n_in;
+        const float* r11 = src + (j0p * n_in + j1p) * n_in;
+        float* out = dst + r * n_out;
+        for (int i2 = threadIdx.x; i2 < (int)n_out; i2 += kLanes) {
+            const int j2 = i2 / ratio, j2p = j2 + 1 == ni ? 0 : j2 + 1;
+            const double t2 = (double)(i2 - j2 * ratio) * step;
+            const double a = lerp(lerp((double)r00[j2], (double)r00[j2p], t2), lerp((double)r01[j2], (double)r01[j2p], t2), t1);
+            const double b = lerp(lerp((double)r10[j2], (double)r10[j2p], t2), lerp((double)r11[j2], (double)r11[j2p], t2), t1);
+            out[i2] = (float)lerp(a, b, t0);
+        }
+    }
+}
+
+bool size_ok(int64_t n) { return n >= NBE_LPT_MIN_N && n <= NBE_LPT_MAX_N; }
+
+dim3 row_grid(long long n) { return dim3((unsigned)grid_for(n * n, kRows)); }
+
+const dim3 kBlock(kLanes, kRows);
+
+double cube(double x) { return x * x * x; }
+
+}  // namespace
+
+extern "C" {
+
+int nbe_zeldovich_spectrum(const void* spectrum, int64_t n, double boxsize, double scale, void* psi_spectrum,
+                           void* stream) {
+    if (!spectrum || !psi_spectrum) return fail("nbe_zeldovich_spectrum: NULL argument");
+    if (!size_ok(n)) return fail("nbe_zeldovich_spectrum: n %lld not in %d .. %d", (long long)n, NBE_LPT_MIN_N, NBE_LPT_MAX_N);
+    if (!(boxsize > 0.0) || !std::isfinite(boxsize) || !std::isfinite(scale))
+        return fail("nbe_zeldovich_spectrum: bad boxsize %g or scale %g", boxsize, scale);
+    hipLaunchKernelGGL(zeldovich_kernel, row_grid(n), kBlock, 0, (hipStream_t)stream, (const float2*)spectrum,
+                       (float2*)psi_spectrum, (long long)n, scale * boxsize / (2.0 * kPi));
+    return launched("nbe_zeldovich_spectrum");
+}
+
+int nbe_spectrum_resize(const void* src, int64_t n_in, void* dst, int64_t n_out, int sphere, void* stream) {
+    if (!src || !dst || src == dst) return fail("nbe_spectrum_resize: NULL or aliased argument");
+    if (!size_ok(n_in) || !size_ok(n_out))
+        return fail("nbe_spectrum_resize: sizes %lld -> %lld not in %d .. %d", (long long)n_in, (long long)n_out,
+                    NBE_LPT_MIN_N, NBE_LPT_MAX_N);
+    hipLaunchKernelGGL(spectrum_resize_kernel, row_grid(n_out), kBlock, 0, (hipStream_t)stream, (const float2*)src,
+                       (long long)n_in, (float2*)dst, (long long)n_out, cube((double)n_out / (double)n_in), sphere != 0);
+    return launched("nbe_spectrum_resize");
+}
+
+int nbe_spectrum_inject(const void* src, int64_t n_in, void* dst, int64_t n_out, const void* k_table,
+                        const void* pk_table, int ntable, double tail_slope, double tail_intercept, double boxsize,
+                        uint64_t seed, void* stream) {
+    if (!src || !dst || src == dst || !k_table || !pk_table) return fail("nbe_spectrum_inject: NULL or aliased argument");
+    if (!size_ok(n_in) || !size_ok(n_out) || n_out < n_in)
+        return fail("nbe_spectrum_inject: sizes %lld -> %lld not in %d .. %d, or not upwards", (long long)n_in,
+                    (long long)n_out, NBE_LPT_MIN_N, NBE_LPT_MAX_N);
+    if (ntable < 2) return fail("nbe_spectrum_inject: a table of %d points (at least 2)", ntable);
+    if (!(boxsize > 0.0) || !std::isfinite(boxsize) || !std::isfinite(tail_slope) || !std::isfinite(tail_intercept))
+        return fail("nbe_spectrum_inject: bad boxsize %g or tail (%g, %g)", boxsize, tail_slope, tail_intercept);
+    InjectArgs A;
+    A.src = (const float2*)src; A.dst = (float2*)dst;
+    A.n_in = n_in; A.n_out = n_out;
+    A.k_table = (const double*)k_table; A.pk_table = (const double*)pk_table; A.ntable = ntable;
+    A.tail_slope = tail_slope; A.tail_intercept = tail_intercept;
+    A.kf = 2.0 * kPi / boxsize;
+    A.amp = cube((double)n_out) / sqrt(cube(boxsize));
+    A.scale = cube((double)n_out / (double)n_in);
+    A.key0 = (uint32_t)seed; A.key1 = (uint32_t)(seed >> 32);
+    hipLaunchKernelGGL(spectrum_inject_kernel, row_grid(n_out), kBlock, 0, (hipStream_t)stream, A);
+    return launched("nbe_spectrum_inject");
+}
+
+int nbe_gaussian_filter(void* spectrum, int64_t n, double sigma_over_L, void* stream) {
+    if (!spectrum) return fail("nbe_gaussian_filter: NULL argument");
+    if (!size_ok(n)) return fail("nbe_gaussian_filter: n %lld not in %d .. %d", (long long)n, NBE_LPT_MIN_N, NBE_LPT_MAX_N);
+    if (!(sigma_over_L >= 0.0) || !std::isfinite(sigma_over_L))
+        return fail("nbe_gaussian_filter: bad sigma / L %g", sigma_over_L);
+    hipLaunchKernelGGL(gaussian_filter_kernel, row_grid(n), kBlock, 0, (hipStream_t)stream, (float2*)spectrum,
+                       (long long)n, -2.0 * kPi * kPi * sigma_over_L * sigma_over_L);
+    return launched("nbe_gaussian_filter");
+}
+
+int nbe_block_average(const void* src, int64_t n_in, void* dst, int64_t n_out, void* stream) {
+    if (!src || !dst || src == dst) return fail("nbe_block_average: NULL or aliased argument");
+    if (!size_ok(n_in) || n_out < 1 || n_out > n_in || n_in % n_out)
+        return fail("nbe_block_average: %lld -> %lld is not a division by an integer (sizes up to %d)", (long long)n_in,
+                    (long long)n_out, NBE_LPT_MAX_N);
+    hipLaunchKernelGGL(block_average_kernel, row_grid(n_out), kBlock, 0, (hipStream_t)stream, (const float*)src,
+                       (long long)n_in, (float*)dst, (long long)n_out);
+    return launched("nbe_block_average");
+}
+
+int nbe_trilinear_upsample(const void* src, int64_t n_in, void* dst, int64_t n_out, void* stream) {
+    if (!src || !dst || src == dst) return fail("nbe_trilinear_upsample: NULL or aliased argument");
+    if (!size_ok(n_out) || n_in < 1 || n_in > n_out || n_out % n_in)
+        return fail("nbe_trilinear_upsample: %lld -> %lld is not a multiplication by an integer (sizes up to %d)",
+                    (long long)n_in, (long long)n_out, NBE_LPT_MAX_N);
+    hipLaunchKernelGGL(trilinear_kernel, row_grid(n_out), kBlock, 0, (hipStream_t)stream, (const float*)src,
+                       (long long)n_in, (float*)dst, (long long)n_out);
+    return launched("nbe_trilinear_upsample");
+}
+
+}  // extern "C"

@@ -1,0 +1,286 @@
+"""The emulator's input, on the GPU: a linear density field brought to the particle grid and turned into the first-order
+LPT displacement that `process_box` reads.
+
+The reference's pipeline does this before `process_box` with DISCO-DJ, JAX and Pylians (`scripts/core.py:302-409`:
+`resize_density_grid`, `scripts/utils.py:186-234`, `:261-425`, `:531-592`; `dj.evaluate_lpt_psi_at_a(n_order=1)`).
+
+    from jax_nbody_emulator_with_dj_amd.lpt import zeldovich_displacement, resize_density, gaussian_smooth
+
+    delta512 = resize_density(delta256, 512, boxsize=1000.0, upsample_method="fourier")
+    psi = zeldovich_displacement(delta512, boxsize=1000.0)                 # (3, 512, 512, 512), process_box's input
+    delta128 = resize_density(delta256, 128, boxsize=1000.0, upsample_method="fourier", downsample_method="gaussian")
+    smooth = gaussian_smooth(delta256, boxsize=1000.0, sigma=8.0)
+
+Conventions:
+
+- Fields are cubic (n, n, n) float32 in a cubic periodic box of side `boxsize`, 2 <= n <= 2048.  Transforms are rocFFT's
+  through torch.fft (unnormalised forward); a mode has the integer wave vector m, k = 2 pi m / L.
+- `zeldovich_displacement` returns psi with psi_k = scale i k / |k|^2 delta_k, so that div psi = -scale delta: particles
+  move towards overdensities, the sign of DISCO-DJ's and of the emulator's input.  psi_k is 0 at k = 0.  Where n is even,
+  component c is 0 on the Nyquist row |m_c| = n/2, which has no sign.
+- "fourier" resizing keeps every mode both grids hold, times (n_out / n_in)^3.  Upwards an even coarse Nyquist row is
+  split evenly onto +-n_in/2; downwards a fine Nyquist component is the sum of the source at both signs.  So an upsampled
+  field equals its input at the coarse nodes, and down(up(x)) = x.
+- "mode_inject" keeps the modes inside the sphere |m| <= n_in/2 and draws the others from a tabulated P(k) with a
+  counter-based generator: `inject_spectrum` has the definition.
+
+Residency: NumPy in gives NumPy out; a CUDA torch tensor in gives a CUDA tensor on the same device, with no host copy,
+enqueued on torch's current stream of that device.  There is no CPU fallback: without a device the first device call
+raises NBEError.  Arguments are validated before any device work.
+"""
+
+import numbers
+
+import numpy as np
+
+from . import _lib
+from .density import _back, _bk_batch, _check_array, _cubic, _device_of, _ptr, _real, _stream, _to_device
+
+try:
+    import torch
+except Exception:  # pragma: no cover
+    torch = None
+
+__all__ = ["zeldovich_displacement", "resize_density", "gaussian_smooth"]
+
+MIN_N, MAX_N = 2, 2048                  # include/nbe.h: NBE_LPT_MIN_N, NBE_LPT_MAX_N
+UPSAMPLE_METHODS = ("fourier", "linear", "mode_inject")
+DOWNSAMPLE_METHODS = ("gaussian", "block_average", "fourier")
+_TAIL_POINTS = 8                        # reference scripts/utils.py:307: the log-log tail is fitted to the last 8 points
+
+
+def _field(delta, boxsize, what):
+    return _cubic(delta, "delta", boxsize, what, "(n, n, n) field", MIN_N, MAX_N)
+
+
+def _size(v, name):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Integral) or not MIN_N <= int(v) <= MAX_N:
+        raise ValueError("%s must be an int in %d .. %d, got %r" % (name, MIN_N, MAX_N, v))
+    return int(v)
+
+
+def _half_spectrum(x):
+    return torch.fft.rfftn(x).contiguous()               # the kernels index the half spectrum row-major
+
+
+def _real_field(spec, n):
+    return torch.fft.irfftn(spec, s=(n, n, n)).contiguous()
+
+
+def _empty_spectrum(n, dev, lead=()):
+    return torch.empty(tuple(lead) + (n, n, n // 2 + 1), dtype=torch.complex64, device=dev)
+
+
+# ---- first-order LPT -----------------------------------------------------------------------------------------------------
+
+def zeldovich_displacement(delta, boxsize=1000.0, scale=1.0, _max_batch=None):
+    """First-order LPT (Zel'dovich) displacement of a linear density field (reference scripts/core.py:396-397,
+    dj.with_lpt(n_order=1) / dj.evaluate_lpt_psi_at_a(a, n_order=1); 2LPT is not built, the reference uses n_order=1).
+
+    delta: cubic (n, n, n) float32, NumPy array or CUDA tensor, 2 <= n <= 2048.  boxsize: L (scalar, or a 3-tuple of equal
+    values), the unit of the result.  Returns psi, (3, n, n, n) float32, channel c along array axis c: valid input to
+    process_box as it stands.
+
+    Sign convention: psi_k = scale i k / |k|^2 delta_k with k = 2 pi m / L, so that div psi = -scale delta and particles
+    move towards overdensities.  `scale` carries the growth factor for a field given at another epoch: for delta
+    normalised at a_0 and an emulator input at a, scale = D(a) / D(a_0) (cosmology.growth_factor); a negative or zero
+    scale is taken as given.  DISCO-DJ cannot be imported where this library is developed, so its normalisation of the
+    external field is not pinned; the definition above is what is computed.  psi_k = 0 at k = 0, and where n is even
+    component c is 0 on the row |m_c| = n/2: a Nyquist row has no sign, so its derivative is set to zero and the field
+    stays real.
+
+    One rfftn, one pass that reads delta_k once and writes the three spectra, and one batched irfftn over the three
+    components; where memory is short the components are transformed one at a time (the same bits)."""
+    d, n, L = _field(delta, boxsize, "zeldovich_displacement")
+    scale = _real(scale, "scale")
+    dev = _device_of(d)
+    with torch.cuda.device(dev):
+        spec = _half_spectrum(_to_device(d, dev, (torch.float32,)))
+        psi_k = _empty_spectrum(n, dev, (3,))
+        _lib.check(_lib.lib().nbe_zeldovich_spectrum(_ptr(spec), n, L, scale, _ptr(psi_k), _stream(dev)))
+        del spec
+        if _bk_batch(dev, n, 3, _max_batch) >= 3:
+            psi = torch.fft.irfftn(psi_k, s=(n, n, n), dim=(1, 2, 3)).contiguous()
+        else:
+            psi = torch.empty((3, n, n, n), dtype=torch.float32, device=dev)
+            # A batch of one through the same call: torch gives a transform with a leading batch axis to one 3-D
+            # complex-to-real plan, and a bare 3-D tensor to a 2-D complex plan plus 1-D real ones, which rounds differently.
+            for c in range(3):
+                psi[c:c + 1] = torch.fft.irfftn(psi_k[c:c + 1], s=(n, n, n), dim=(1, 2, 3))
+    return _back(d, psi)
+
+
+# ---- resizing --------------------------------------------------------------------------------------------------------------
+
+def _resize_spectrum(spec, n_in, n_out, sphere=False):
+    """nbe_spectrum_resize on a contiguous complex64 half spectrum on the device."""
+    out = _empty_spectrum(n_out, spec.device)
+    _lib.check(_lib.lib().nbe_spectrum_resize(_ptr(spec), n_in, _ptr(out), n_out, int(bool(sphere)),
+                                              _stream(spec.device)))
+    return out
+
+
+def _validate_table(k_target, pk_target):
+    """The tabulated P(k) of mode injection, checked as the reference checks it (scripts/utils.py:484-495) except that an
+    unsorted table is an error here: (k, pk, slope, intercept) with the log-log tail fit."""
+    if k_target is None or pk_target is None:
+        raise ValueError("mode_inject needs a tabulated P(k): both k_target and pk_target (there is no default spectrum)")
+    try:
+        k = np.asarray(k_target, dtype=np.float64).ravel()
+        pk = np.asarray(pk_target, dtype=np.float64).ravel()
+    except (TypeError, ValueError):
+        raise ValueError("k_target and pk_target must be numbers")
+    if k.size < 2 or pk.size != k.size:
+        raise ValueError("invalid tabulated P(k): need matching arrays with at least two points, got %d and %d"
+                         % (k.size, pk.size))
+    if not np.isfinite(k).all() or not np.isfinite(pk).all():
+        raise ValueError("k_target and pk_target must be finite")
+    if (np.diff(k) <= 0).any() or k[0] <= 0:
+        raise ValueError("k_target values must be positive and strictly increasing")
+    t = min(_TAIL_POINTS, k.size)
+    if (pk[-t:] <= 0).any():
+        raise ValueError("the last %d values of pk_target must be positive: the tail is fitted in log-log" % t)
+    slope, intercept = np.polyfit(np.log(k[-t:]), np.log(pk[-t:]), 1)
+    if not np.isfinite(slope) or not np.isfinite(intercept):
+        raise ValueError("the log-log tail fit of the tabulated P(k) is not finite")
+    return k, pk, float(slope), float(intercept)
+
+
+def _seed(seed):
+    if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, numbers.Integral) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("seed must be an int in 0 .. 2^64 - 1, got %r" % (seed,))
+    return int(seed)
+
+
+def _inject_spectrum(spec, n_in, n_out, table, L, seed):
+    """nbe_spectrum_inject on a contiguous complex64 half spectrum on the device; table from _validate_table."""
+    k, pk, slope, intercept = table
+    dev = spec.device
+    kd, pd = torch.from_numpy(k).to(dev), torch.from_numpy(pk).to(dev)
+    out = _empty_spectrum(n_out, dev)
+    _lib.check(_lib.lib().nbe_spectrum_inject(_ptr(spec), n_in, _ptr(out), n_out, _ptr(kd), _ptr(pd), int(k.size), slope,
+                                              intercept, L, seed, _stream(dev)))
+    return out
+
+
+def _validate_inject(delta, target_res, boxsize, k_target, pk_target, seed, what):
+    d, n, L = _field(delta, boxsize, what)
+    m = _size(target_res, "target_res")
+    if m < n:
+        raise ValueError("%s: target_res %d is below the input's %d" % (what, m, n))
+    return d, n, L, m, _validate_table(k_target, pk_target), _seed(seed)
+
+
+def inject_spectrum(delta, target_res, boxsize=1000.0, k_target=None, pk_target=None, seed=0):
+    """The complex half spectrum (target_res, target_res, target_res // 2 + 1) of "mode_inject" before its inverse
+    transform (reference scripts/utils.py:261-346, :349-425).
+
+    Inside the sphere 4 |m|^2 <= n_in^2 the modes are those of "fourier" upsampling.  Outside, mode m is a Gaussian draw
+    with E|F|^2 = sigma^2, sigma = n_out^3 sqrt(P(|k|) / L^3).  P is evaluated in float64: linear in k between the table's
+    points (np.interp), pk_target[0] below them, exp(intercept + slope ln k) above k_target[-1], with the line fitted by
+    np.polyfit to the last min(8, ntable) points in log-log as in the reference, and clamped at 0.
+
+    The draw is counter-based, so it depends on the seed and the mode alone: Philox4x32-10 with key (seed low word, seed
+    high word) and counter (r0, r1, i2, 0), where (r0, r1, i2) is the mode's index in the half spectrum.  On the planes
+    i2 = 0 and (n_out even) i2 = n_out/2 the rows (i0, i1) and ((n - i0) % n, (n - i1) % n) form a pair: the one with the
+    smaller i0 n + i1 supplies the counter and the other takes the complex conjugate.  U1 = (x0 + 1/2) 2^-32,
+    U2 = (x1 + 1/2) 2^-32, g = sqrt(-2 ln U1) (cospi(2 U2) + i sinpi(2 U2)) in float64.  A mode that is its own mirror image
+    gets F = sigma Re g, every other F = sigma g / sqrt(2); each word is rounded to float32 once.  The result is the half
+    spectrum of a real field by construction, without the two extra transforms of the reference's projection.
+
+    The 32-bit uniforms cut the Gaussian tail: |g| <= sqrt(-2 ln 2^-33) = 6.8, so no draw exceeds 6.8 sigma.  The random
+    streams of NumPy or JAX are not matched (the reference's two backends do not match each other either).
+
+    seed: an int in 0 .. 2^64 - 1.  Returns a complex64 array of the input's kind."""
+    d, n, L, m, table, seed = _validate_inject(delta, target_res, boxsize, k_target, pk_target, seed, "inject_spectrum")
+    dev = _device_of(d)
+    with torch.cuda.device(dev):
+        return _back(d, _inject_spectrum(_half_spectrum(_to_device(d, dev, (torch.float32,))), n, m, table, L, seed))
+
+
+def _smooth(x, n, sigma_over_L):
+    spec = _half_spectrum(x)
+    _lib.check(_lib.lib().nbe_gaussian_filter(_ptr(spec), n, sigma_over_L, _stream(x.device)))
+    return _real_field(spec, n)
+
+
+def _real_pass(fn, x, n_in, n_out):
+    """One of the real-space kernels (block average, trilinear interpolation) from n_in^3 to n_out^3."""
+    out = torch.empty((n_out,) * 3, dtype=torch.float32, device=x.device)
+    _lib.check(fn(_ptr(x), n_in, _ptr(out), n_out, _stream(x.device)))
+    return out
+
+
+def gaussian_smooth(delta, boxsize, sigma):
+    """The field smoothed with a Gaussian of standard deviation sigma (the unit of boxsize): its spectrum times
+    exp(-|k|^2 sigma^2 / 2), Pylians' FT_filter(boxsize, sigma, n, "Gaussian") and field_smoothing (reference
+    scripts/utils.py:590-591).  delta: cubic (n, n, n) float32, NumPy array or CUDA tensor; returns the same kind."""
+    d, n, L = _field(delta, boxsize, "gaussian_smooth")
+    sigma = _real(sigma, "sigma", positive=True)
+    dev = _device_of(d)
+    with torch.cuda.device(dev):
+        return _back(d, _smooth(_to_device(d, dev, (torch.float32,)), n, sigma / L))
+
+
+_REQUIRED = object()
+
+
+def _method(n, m, upsample_method, downsample_method):
+    """The method that takes n^3 to m^3 (None for equal sizes), after checking both names and the ratio it needs."""
+    if upsample_method is _REQUIRED or upsample_method not in UPSAMPLE_METHODS:
+        raise ValueError("upsample_method must be one of %s, got %s"
+                         % (UPSAMPLE_METHODS, "nothing" if upsample_method is _REQUIRED else repr(upsample_method)))
+    if downsample_method not in DOWNSAMPLE_METHODS:
+        raise ValueError("downsample_method must be one of %s, got %r" % (DOWNSAMPLE_METHODS, downsample_method))
+    if m == n:
+        return None
+    method = upsample_method if m > n else downsample_method
+    if method in ("linear", "gaussian", "block_average") and max(m, n) % min(m, n):
+        raise ValueError("resize_density: %r needs an integer ratio, got %d -> %d" % (method, n, m))
+    return method
+
+
+def resize_density(delta, target_res, boxsize=1000.0, upsample_method=_REQUIRED, downsample_method="gaussian",
+                   gaussian_sigma=None, k_target=None, pk_target=None, seed=0):
+    """Resize a cubic periodic density field between resolutions (reference scripts/utils.py:595-655,
+    resize_density_grid).
+
+    delta: cubic (n, n, n) float32, NumPy array or CUDA tensor, 2 <= n <= 2048; target_res: 2 .. 2048.  Equal sizes return
+    the input.  upsample_method has no default, as in the reference, and both method names are checked whichever way the
+    call goes.
+
+    Upwards: "fourier" (every mode of the coarse grid, an even Nyquist row split evenly onto +-n/2: the result equals the
+    input at the coarse nodes), "linear" (periodic trilinear interpolation at the fine nodes) or "mode_inject" (the coarse
+    modes inside the sphere |m| <= n/2, Gaussian draws from the table k_target / pk_target beyond it, reproducible from
+    `seed`: see inject_spectrum; the table is required, there is no default spectrum here).
+    Downwards: "gaussian" (gaussian_smooth with gaussian_sigma, default boxsize / target_res, then the block average),
+    "block_average" (the mean of each block) or "fourier" (the exact inverse of "fourier" upsampling, which the reference
+    does not have: a fine Nyquist component is the sum of the source at both signs).
+    "linear", "gaussian" and "block_average" need an integer ratio of the sizes; "fourier" and "mode_inject" do not.
+
+    Returns (target_res,) * 3 float32 of the input's kind."""
+    d, n, L = _field(delta, boxsize, "resize_density")
+    m = _size(target_res, "target_res")
+    method = _method(n, m, upsample_method, downsample_method)
+    if gaussian_sigma is not None:
+        gaussian_sigma = _real(gaussian_sigma, "gaussian_sigma", positive=True)
+    if method is None:
+        return d
+    table = seed_value = None
+    if method == "mode_inject":
+        table, seed_value = _validate_table(k_target, pk_target), _seed(seed)
+    dev = _device_of(d)
+    l = _lib.lib()
+    with torch.cuda.device(dev):
+        x = _to_device(d, dev, (torch.float32,))
+        if method == "fourier":
+            out = _real_field(_resize_spectrum(_half_spectrum(x), n, m), m)
+        elif method == "mode_inject":
+            out = _real_field(_inject_spectrum(_half_spectrum(x), n, m, table, L, seed_value), m)
+        elif method == "linear":
+            out = _real_pass(l.nbe_trilinear_upsample, x, n, m)
+        else:
+            if method == "gaussian":
+                x = _smooth(x, n, (L / m if gaussian_sigma is None else gaussian_sigma) / L)
+            out = _real_pass(l.nbe_block_average, x, n, m)
+    return _back(d, out)

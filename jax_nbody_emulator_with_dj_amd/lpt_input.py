@@ -1,0 +1,114 @@
+#!/usr/bin/env python
+"""Batch driver: linear density fields to the displacement files `run_emulator --displacement_files` reads.
+
+The reference does this inside its pipeline (`scripts/core.py:302-409`): read a cubic field, bring it to the particle
+grid with `resize_density_grid`, take the first-order LPT displacement.  Here both steps run on the GPU (lpt.py):
+
+    python -m jax_nbody_emulator_with_dj_amd.lpt_input \\
+        --delta_files '/path/to/sims/*/delta.npy' --output_dirs '/path/to/sims/*/' \\
+        --npart 512 --boxsize 1000 --scale 1.0 --upsample_method fourier --downsample_method gaussian
+
+    delta file       cubic (n, n, n) linear density contrast (any real dtype, read as float32)
+    output           <output_dir>/lpt_dis.npy, (3, N, N, N) float32: zeldovich_displacement(resize_density(delta, N), scale)
+
+`--scale S` multiplies the displacement (the growth factor between the field's epoch and the emulator's input).
+`--gaussian_sigma X` (Mpc/h) is the smoothing of `--downsample_method gaussian` (default boxsize / npart).
+`--upsample_method mode_inject` needs `--pk_table FILE`, the two columns k [h/Mpc] and P(k) [(Mpc/h)^3] that the
+reference writes with np.savetxt (`scripts/core.py:284-288`), and takes `--seed N`.
+"""
+
+import argparse
+import sys
+
+import numpy as np
+
+from .run_emulator import dirs_matching, files_matching
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(
+        description='Resize linear density fields to the particle grid and write their Zel\'dovich displacements.',
+        formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--delta_files', type=files_matching, required=True,
+                    help='Glob pattern for input density files (numpy arrays with shape [n, n, n])')
+    ap.add_argument('--output_dirs', type=dirs_matching, required=True, help='Glob pattern for output directories')
+    ap.add_argument('--npart', type=int, required=True, help='Particle grid size N: the output is (3, N, N, N)')
+    ap.add_argument('--boxsize', type=float, default=1000.0, help='Box size in Mpc/h (default: 1000.0, Quijote)')
+    ap.add_argument('--scale', type=float, default=1.0, help='Factor on the displacement, e.g. a growth factor (default: 1)')
+    ap.add_argument('--upsample_method', required=True, help="'fourier', 'linear' or 'mode_inject'")
+    ap.add_argument('--downsample_method', default='gaussian', help="'gaussian' (default), 'block_average' or 'fourier'")
+    ap.add_argument('--gaussian_sigma', type=float, default=None,
+                    help='Smoothing in Mpc/h for --downsample_method gaussian (default: boxsize / npart)')
+    ap.add_argument('--pk_table', type=str, default=None,
+                    help='Two-column text file k, P(k) for --upsample_method mode_inject')
+    ap.add_argument('--seed', type=int, default=0, help='Seed of the injected modes (default: 0)')
+    return ap
+
+
+def read_table(path):
+    """(k, pk) from the two columns np.savetxt(path, np.column_stack([k, pk]), header=...) writes."""
+    try:
+        t = np.loadtxt(path, dtype=np.float64, ndmin=2)
+    except Exception as e:
+        sys.exit(f'--pk_table {path} cannot be read: {e}')
+    if t.ndim != 2 or t.shape[1] != 2:
+        sys.exit(f'--pk_table {path}: expected two columns (k, P), got shape {t.shape}')
+    return t[:, 0], t[:, 1]
+
+
+def read_delta(path):
+    delta = np.load(path)
+    if delta.ndim != 3 or len(set(delta.shape)) != 1:
+        sys.exit(f'in file {path}: input field must be cubic 3D, got shape {delta.shape}')
+    if not (np.issubdtype(delta.dtype, np.floating) or np.issubdtype(delta.dtype, np.integer)):
+        sys.exit(f'in file {path}: input field must be real, got {delta.dtype}')
+    return np.ascontiguousarray(delta, dtype=np.float32)
+
+
+def run(args):
+    from . import lpt
+    if len(args.delta_files) != len(args.output_dirs):
+        sys.exit('Number of files must match:\n'
+                 f'  delta_files: {len(args.delta_files)}\n  output_dirs: {len(args.output_dirs)}')
+    k = pk = None
+    try:                                                     # every argument error before any file is read
+        lpt._size(args.npart, '--npart')
+        lpt._real(args.boxsize, '--boxsize', positive=True)
+        lpt._real(args.scale, '--scale')
+        lpt._method(args.npart, args.npart, args.upsample_method, args.downsample_method)
+        if args.gaussian_sigma is not None:
+            lpt._real(args.gaussian_sigma, '--gaussian_sigma', positive=True)
+        if args.upsample_method == 'mode_inject':
+            if args.pk_table is None:
+                raise ValueError('--upsample_method mode_inject needs --pk_table')
+            k, pk = read_table(args.pk_table)
+            lpt._validate_table(k, pk)
+            lpt._seed(args.seed)
+    except ValueError as e:
+        sys.exit(str(e))
+    import torch
+    from .density import _device
+    print(f'Processing {len(args.delta_files)} field(s) to {args.npart}^3 in a {args.boxsize} Mpc/h box')
+    for i, (path, out_dir) in enumerate(zip(args.delta_files, args.output_dirs)):
+        delta = read_delta(path)
+        try:
+            lpt._field(delta, args.boxsize, 'lpt_input')
+            lpt._method(delta.shape[0], args.npart, args.upsample_method, args.downsample_method)
+        except ValueError as e:
+            sys.exit(f'in file {path}: {e}')
+        x = torch.from_numpy(delta).to(_device())            # the resized field stays on the device
+        resized = lpt.resize_density(x, args.npart, boxsize=args.boxsize, upsample_method=args.upsample_method,
+                                     downsample_method=args.downsample_method, gaussian_sigma=args.gaussian_sigma,
+                                     k_target=k, pk_target=pk, seed=args.seed)
+        psi = lpt.zeldovich_displacement(resized, boxsize=args.boxsize, scale=args.scale)
+        np.save(out_dir / 'lpt_dis.npy', psi.cpu().numpy())
+        print(f'[{i + 1}/{len(args.delta_files)}] {delta.shape[0]}^3 -> {out_dir / "lpt_dis.npy"}')
+    print('\nDone!')
+
+
+def main(argv=None):
+    run(build_parser().parse_args(argv))
+
+
+if __name__ == '__main__':
+    main()
