@@ -12,7 +12,9 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NBE_LIB") or os.path.join(_HERE, "libnbe.so")   # NBE_LIB: timing-probe builds only
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("nbe_kernels.hip", "nbe_kernels_h3.hip", "nbe_density.hip", "nbe_lpt.hip", "nbe_engine.cpp")
+SOURCES = ("nbe_kernels.hip", "nbe_kernels_h3.hip", "nbe_density.hip", "nbe_lpt.hip",
+           "nbe_engine.cpp", "nbe_engine_net.cpp", "nbe_engine_weights.cpp", "nbe_engine_box.cpp", "nbe_engine_brick.cpp",
+           "nbe_engine_probe.cpp", "nbe_engine_test.cpp")
 
 
 class NBEError(RuntimeError):
@@ -136,21 +138,25 @@ SIGNATURES = {
 _lib = None
 
 
+def _source_files():
+    """Every source and header in csrc/, sorted: what source_hash() covers and what build() depends on."""
+    return [f for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".cpp", ".h"))]
+
+
 def source_hash():
     """sha256 (16 hex digits) over the kernel / engine sources: identifies what a measurement was taken on."""
     import hashlib
     h = hashlib.sha256()
-    for f in sorted(os.listdir(CSRC)):
-        if f.endswith((".hip", ".cpp", ".h")):
-            h.update(f.encode())
-            h.update(open(os.path.join(CSRC, f), "rb").read())
+    for f in _source_files():
+        h.update(f.encode())
+        h.update(open(os.path.join(CSRC, f), "rb").read())
     return h.hexdigest()[:16]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP sources for gfx950 into libnbe.so (in-tree)."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, "nbe_kernels.h"), os.path.join(CSRC, "nbe_kernels_internal.h"), os.path.join(CSRC, "nbe_kernels_wino.h"), os.path.join(CSRC, "nbe_kernels_head.h"), os.path.join(CSRC, "nbe_spectral.h"), os.path.join(_HERE, "..", "include", "nbe.h")]
+    deps = [os.path.join(CSRC, f) for f in _source_files()] + [os.path.join(_HERE, "..", "include", "nbe.h")]
     if not force and os.path.exists(LIB_PATH):
         if all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
             return LIB_PATH
