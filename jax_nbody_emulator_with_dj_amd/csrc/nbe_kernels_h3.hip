@@ -2100,8 +2100,8 @@ int launch_conv_h3(const PackedW& pw, const ConvKArgs& ka, bool vel, bool has_dx
     if (ka.beta) {                                               // gauged input tangent: only conv_h3g_kernel reads it
         if (!(pw.mode == MODE_FLAT3 && vel && has_dx && ka.in_off == 0 && ka.osz == 1)) return 1;   // no gauged kernel
         if (split) {
-            if (pw.cout_t == 16) {                              // the head convolution: four output planes per workgroup where the launch allows
-                if (launch_h3n4(ka, ct, s) == 0) return 0;
+            if (pw.cout_t == 16) {                              // the head convolution: one pass along z, dz in the MFMA rows, where the launch allows
+                if (launch_h3nz(ka, ct, pw.cout, s) == 0) return 0;
                 return launch_h3g<true>(ka, ct, s);
             }
             if (ka.ww && launch_h3w(ka, ka.ww, ka.wws, ka.wws_set_floats, ct, s) == 0) return 0;     // Winograd along z; 1: no such form for this launch

@@ -29,6 +29,7 @@ struct ConvKArgs {
     const float* bias; const float* w; const float* dw;
     int nchunk; int cout_groups; int flags; int ntiles;
     int tny, tnx;            // patch kernel: number of 8-row / 32-column tiles per output plane
+    int zrun;                // conv_h3nz_kernel: output planes per workgroup (set by its launcher)
     // tangent gauge (f16x3 style path, see conv_h3g_kernel): per-cout vectors, either may be NULL
     const float* gout;       // the stored tangent is dy + gout[o] * y
     const float* beta;       // the input tangent is in this layer's gauge: dy = W.dx~ + beta[o] * (W.x), no dW
