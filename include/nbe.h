@@ -292,6 +292,28 @@ int nbe_deconvolve_mas(void* field, const int64_t res[3], int worder, void* stre
  * sums[n/2+1 + s] = sum of (|k| / k_F - s) in units of 2^-36, sums[2 (n/2+1) + s] = sum of the terms in units of
  * 2^(e_s - 32).  Integer sums: reproducible bit for bit.  2 <= n <= 4096. */
 int nbe_power_spectrum(const void* a, const void* b, int64_t n, void* binmax, void* sums, void* stream);
+/* Anisotropic spectra about the array axis `los` (0 .. 2) of a cubic mesh.  Shells, full-grid
+ * weights, terms p = Re(a b*) and binmax are those of nbe_power_spectrum, whose first pass both calls run unchanged; every
+ * power sum of shell s is in units of 2^(e_s - 32).  mu^2 = m_los^2 / |m|^2 in float64; only even powers of mu enter, so
+ * the half spectrum's missing mirror modes do not matter.  2 <= n <= NBE_PK_ANISO_MAX_N. */
+#define NBE_PK_ANISO_MAX_N 2048
+#define NBE_PK_MAX_MU 64
+/* replaces the multipole columns Pk[:, 0..2] of Pk_library.Pk(delta, boxsize, axis, MAS) (scripts/utils.py:1083-1085,
+ * :1447-1449): binmax = (n/2+1) uint32, sums = 5 (n/2+1) int64, both zeroed by the caller.  Out: binmax as
+ * nbe_power_spectrum; sums[w (n/2+1) + s] for w = 0 modes, 1 the sum of (|k| / k_F - s) in units of 2^-36, and 2, 3, 4 the
+ * sums of rint(p L_l 2^(32 - e_s)) for L_0 = 1, L_2 = (3 mu^2 - 1) / 2, L_4 = (35 mu^4 - 30 mu^2 + 3) / 8 in float64.  Words
+ * 0 .. 2 are the bits of nbe_power_spectrum.  The caller applies 2 l + 1 and L^3 / n^6. */
+int nbe_power_multipoles(const void* a, const void* b, int64_t n, int los, void* binmax, void* sums, void* stream);
+/* replaces the 2-D spectrum Pk2D of Pk_library.Pk(delta, boxsize, axis, MAS) (scripts/utils.py:1083-1085, :1447-1449) with
+ * wedges of |mu|: for nmu (1 .. NBE_PK_MAX_MU) bins a mode falls into bin j = min(nmu - 1, #{ j' in 1 .. nmu-1 :
+ * j'^2 |m|^2 <= nmu^2 m_los^2 }), that is floor(nmu |mu|) with mu = 1 in the last bin, decided in 64-bit integers.
+ * binmax = (n/2+1) uint32, per shell and not per wedge; sums = 4 nmu (n/2+1) int64 laid out [word][mu][s], both zeroed by
+ * the caller.  Words: modes, the sum of (|k| / k_F - s) in units of 2^-36, the sum of |mu| = |m_los| / |m| in units of
+ * 2^-36, the sum of the terms in units of 2^(e_s - 32).  The mu bins are walked in chunks whose image fits 64 KiB of LDS,
+ * one launch each; max_bins (0: that limit) caps the (mu, s) bins of a launch and must hold one mu bin, n/2+1.  Integer
+ * sums: the same bits for every chunking. */
+int nbe_power_wedges(const void* a, const void* b, int64_t n, int los, int nmu, int max_bins, void* binmax, void* sums,
+                     void* stream);
 
 /* Minkowski functionals of an n^3 float32 field, replacing compute_minkowski_functionals and its
  * cubical-complex counting (scripts/utils.py:652-763).  For a threshold t the excursion set is the set M of voxels with
@@ -393,6 +415,11 @@ int nbe_field_histogram(const void* field, int64_t count, double lo, double hi, 
  * keeps the field real. */
 int nbe_zeldovich_spectrum(const void* spectrum, int64_t n, double boxsize, double scale, void* psi_spectrum,
                            void* stream);
+/* the divergence of a vector field, which the reference's pipeline does not take (its velocity has no spectral summary;
+ * the spectra it would feed are those of scripts/utils.py:1083-1085): spectra = (3, n, n, n/2+1), out = (n, n, n/2+1)
+ * receives theta_k = i (2 pi / L) ((m_0 v_0 + m_1 v_1) + m_2 v_2), added in float64 in that order.  Component c is left out
+ * where n is even and |m_c| = n/2, as in nbe_zeldovich_spectrum, which keeps the field real.  out must not alias spectra. */
+int nbe_divergence_spectrum(const void* spectra, int64_t n, double boxsize, void* out, void* stream);
 /* replaces the "fourier" method of upsample_density_with_discodj (scripts/utils.py:186-234), and is its inverse for
  * n_out < n_in: destination mode m = (n_out / n_in)^3 times the source value at m, where the source value at -m is the
  * conjugate of the stored mirror mode.  n_out > n_in: 0 if any |m_c| > n_in / 2, and a factor 1/2 per axis with

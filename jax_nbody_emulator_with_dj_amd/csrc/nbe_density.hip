@@ -1,8 +1,9 @@
 // Density fields from emulated displacements (include/nbe.h, "Density"): mass assignment of the displaced lattice onto
 // a periodic mesh (NGP / CIC / TSC / PCS), the inverse assignment window on the rfft of the mesh, shell-binned power
-// spectra, Minkowski functionals, the shell filter and triple sums of the bispectrum estimator and one-point statistics.
+// spectra with their multipoles and (k, mu) wedges, Minkowski functionals, the shell filter and triple sums of the
+// bispectrum estimator and one-point statistics.
 // Replaces the DISCO-DJ / Pylians step of the reference's pipeline (scripts/core.py:447-458, scripts/utils.py:136-148,
-// :652-763, :1083-1085, :1164-1187, :1248-1274, :1314-1399).  No context: these entry points need no weights.
+// :652-763, :1083-1085, :1164-1187, :1248-1274, :1314-1399, :1447-1449).  No context: these entry points need no weights.
 //
 // Paint.  One workgroup per Lagrangian tile of 8^3 particles.  Pass 1 reads the tile's
 // displacements once and bounds its Eulerian footprint (the nodes its particles touch, from the tile's own positions).
@@ -470,9 +471,14 @@ __device__ inline int power_exponent(unsigned binmax) {
     return isfinite(m) ? 32 - e : INT_MIN;
 }
 
+// a term in the shell's power unit 2^(e - 32); 0 in a non-finite shell
+__device__ inline long long power_units(double p, int pexp) {
+    return pexp == INT_MIN ? 0 : (long long)rint(ldexp(p, pexp));
+}
+
 // one mode into the LDS triple t[0], t[stride], t[2 stride] of its shell: weight, k, power
 __device__ inline void shell_add(unsigned long long* t, int stride, int w, long long kq, double p, int pexp) {
-    const long long pq = pexp == INT_MIN ? 0 : (long long)rint(ldexp(p, pexp));
+    const long long pq = power_units(p, pexp);
     atomicAdd(t, (unsigned long long)w);
     atomicAdd(t + stride, (unsigned long long)(w * kq));
     atomicAdd(t + 2 * stride, (unsigned long long)(w * pq));
@@ -481,8 +487,7 @@ __device__ inline void shell_add(unsigned long long* t, int stride, int w, long 
 // One mode of the half spectrum of an n^3 mesh: shell b (0 = not binned), full-grid weight, |k| / k_F, Re(a b*)
 struct Mode { int b; int w; double kk; double p; };
 
-__device__ inline Mode mode_at(const float2* a, const float2* bb, long long i, long long n) {
-    const HalfMode h = half_mode(i, n, n, n);
+__device__ inline Mode mode_of(const HalfMode& h, const float2* a, const float2* bb, long long i, long long n) {
     Mode m;
     m.kk = sqrt((double)h.q);
     m.b = (int)floor(m.kk + 0.5);
@@ -491,6 +496,10 @@ __device__ inline Mode mode_at(const float2* a, const float2* bb, long long i, l
     const float2 x = a[i], y = bb ? bb[i] : x;
     m.p = (double)x.x * y.x + (double)x.y * y.y;
     return m;
+}
+
+__device__ inline Mode mode_at(const float2* a, const float2* bb, long long i, long long n) {
+    return mode_of(half_mode(i, n, n, n), a, bb, i, n);
 }
 
 // pass 1: per-shell max |Re(a b*)|
@@ -528,6 +537,85 @@ __global__ void pk_sum_kernel(const float2* __restrict__ a, const float2* __rest
     __syncthreads();
     for (int i = threadIdx.x; i < 3 * nb; i += blockDim.x)
         if (ssum[i]) atomicAdd(&sums[i], ssum[i]);
+}
+
+// ---- Anisotropic shell sums -----------------------------------------------------------------
+// Multipoles and (k, mu) wedges about the array axis `los`: the shells, weights, terms and exponents of the two passes
+// above (pass 1 is pk_max_kernel itself), with mu^2 = m_los^2 / |m|^2.  Only even powers of mu enter, so neither the sign
+// of m_los nor the mirror modes the half spectrum leaves out along axis 2 matter.
+__device__ inline long long los_freq(const HalfMode& h, int los) { return los == 0 ? h.f0 : los == 1 ? h.f1 : h.f2; }
+
+// pass 2 of the multipoles: per shell the weights, k, and the terms times L_0 = 1, L_2 and L_4 in the shell's power unit
+__global__ void pk_multipole_kernel(const float2* __restrict__ a, const float2* __restrict__ b, long long n, int los,
+                                    const unsigned* __restrict__ binmax, unsigned long long* __restrict__ sums) {
+    extern __shared__ unsigned long long ssum[];           // [5][nb]: weight, k, L0, L2, L4
+    const int nb = (int)(n / 2) + 1;
+    int* sexp = (int*)(ssum + 5 * nb);
+    for (int i = threadIdx.x; i < 5 * nb; i += blockDim.x) ssum[i] = 0ull;
+    for (int i = threadIdx.x; i < nb; i += blockDim.x) sexp[i] = power_exponent(binmax[i]);
+    __syncthreads();
+    const long long total = n * n * (n / 2 + 1);
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const HalfMode h = half_mode(i, n, n, n);
+        const Mode m = mode_of(h, a, b, i, n);
+        if (!m.b) continue;
+        const long long f = los_freq(h, los);
+        const double mu2 = (double)(f * f) / (double)h.q;
+        const double l2 = (3.0 * mu2 - 1.0) / 2.0, l4 = (35.0 * (mu2 * mu2) - 30.0 * mu2 + 3.0) / 8.0;
+        unsigned long long* t = ssum + m.b;
+        const int pexp = sexp[m.b];
+        shell_add(t, nb, m.w, (long long)rint((m.kk - m.b) * kKUnit), m.p, pexp);
+        atomicAdd(t + 3 * nb, (unsigned long long)(m.w * power_units(m.p * l2, pexp)));
+        atomicAdd(t + 4 * nb, (unsigned long long)(m.w * power_units(m.p * l4, pexp)));
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 5 * nb; i += blockDim.x)
+        if (ssum[i]) atomicAdd(&sums[i], ssum[i]);
+}
+
+// The wedge of a mode: min(nmu - 1, #{ j in 1 .. nmu-1 : j^2 q <= nmu^2 f^2 }) = floor(nmu |mu|) with mu = 1 in the last
+// bin.  The float64 quotient is a first guess only; the integers decide (nmu <= 64, q < 2^23: every product < 2^35).
+__device__ inline int mu_bin(long long f, long long q, int nmu, double kk) {
+    const long long af = f < 0 ? -f : f, t = (long long)nmu * nmu * af * af;
+    int j = (int)((double)(nmu * af) / kk);
+    j = j > nmu - 1 ? nmu - 1 : j;
+    while (j > 0 && (long long)j * j * q > t) --j;
+    while (j < nmu - 1 && (long long)(j + 1) * (j + 1) * q <= t) ++j;
+    return j;
+}
+
+// pass 2 of the wedges, for the mu bins mu0 <= j < mu1 (an image of 4 (mu1 - mu0) nb words); a mode of another bin is
+// skipped once its bin is known.  sums is [word][mu][s] over all nmu bins.
+__global__ void pk_wedge_kernel(const float2* __restrict__ a, const float2* __restrict__ b, long long n, int los, int nmu,
+                                int mu0, int mu1, const unsigned* __restrict__ binmax,
+                                unsigned long long* __restrict__ sums) {
+    extern __shared__ unsigned long long ssum[];           // [4][mu1 - mu0][nb]: weight, k, |mu|, power
+    const int nb = (int)(n / 2) + 1, bins = (mu1 - mu0) * nb;
+    int* sexp = (int*)(ssum + 4 * bins);
+    for (int i = threadIdx.x; i < 4 * bins; i += blockDim.x) ssum[i] = 0ull;
+    for (int i = threadIdx.x; i < nb; i += blockDim.x) sexp[i] = power_exponent(binmax[i]);
+    __syncthreads();
+    const long long total = n * n * (n / 2 + 1);
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const HalfMode h = half_mode(i, n, n, n);
+        const Mode m = mode_of(h, a, b, i, n);
+        if (!m.b) continue;
+        const long long f = los_freq(h, los);
+        const int j = mu_bin(f, h.q, nmu, m.kk);
+        if (j < mu0 || j >= mu1) continue;
+        const double mu = (double)(f < 0 ? -f : f) / m.kk;
+        unsigned long long* t = ssum + (j - mu0) * nb + m.b;
+        atomicAdd(t, (unsigned long long)m.w);
+        atomicAdd(t + bins, (unsigned long long)(m.w * (long long)rint((m.kk - m.b) * kKUnit)));
+        atomicAdd(t + 2 * bins, (unsigned long long)(m.w * (long long)rint(mu * kKUnit)));
+        atomicAdd(t + 3 * bins, (unsigned long long)(m.w * power_units(m.p, sexp[m.b])));
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 4 * bins; i += blockDim.x)
+        if (ssum[i]) {
+            const int word = i / bins, r = i - word * bins;
+            atomicAdd(&sums[((long long)word * nmu + mu0) * nb + r], ssum[i]);
+        }
 }
 
 // ---- Minkowski functionals ------------------------------------------------------------------
@@ -1181,6 +1269,55 @@ int nbe_power_spectrum(const void* a, const void* b, int64_t n, void* binmax, vo
     hipLaunchKernelGGL(pk_sum_kernel, g, blk, nb * (3 * sizeof(unsigned long long) + sizeof(int)), s, (const float2*)a,
                        (const float2*)b, (long long)n, (const unsigned*)binmax, (unsigned long long*)sums);
     return launched("nbe_power_spectrum (sum)");
+}
+
+int nbe_power_multipoles(const void* a, const void* b, int64_t n, int los, void* binmax, void* sums, void* stream) {
+    if (!a || !binmax || !sums) return fail("nbe_power_multipoles: NULL argument");
+    if (n < 2 || n > NBE_PK_ANISO_MAX_N)
+        return fail("nbe_power_multipoles: mesh size %lld unsupported (2 .. %d)", (long long)n, NBE_PK_ANISO_MAX_N);
+    if (los < 0 || los > 2) return fail("nbe_power_multipoles: los %d is not an array axis (0 .. 2)", los);
+    const long long total = n * n * (n / 2 + 1);
+    const int nb = (int)(n / 2) + 1;
+    const dim3 g(grid_for(total, 256) < 2048 ? grid_for(total, 256) : 2048), blk(256);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(pk_max_kernel, g, blk, nb * sizeof(unsigned), s, (const float2*)a, (const float2*)b, (long long)n,
+                       (unsigned*)binmax);
+    if (int rc = launched("nbe_power_multipoles (max)")) return rc;
+    hipLaunchKernelGGL(pk_multipole_kernel, g, blk, nb * (5 * sizeof(unsigned long long) + sizeof(int)), s,
+                       (const float2*)a, (const float2*)b, (long long)n, los, (const unsigned*)binmax,
+                       (unsigned long long*)sums);
+    return launched("nbe_power_multipoles (sum)");
+}
+
+int nbe_power_wedges(const void* a, const void* b, int64_t n, int los, int nmu, int max_bins, void* binmax, void* sums,
+                     void* stream) {
+    if (!a || !binmax || !sums) return fail("nbe_power_wedges: NULL argument");
+    if (n < 2 || n > NBE_PK_ANISO_MAX_N)
+        return fail("nbe_power_wedges: mesh size %lld unsupported (2 .. %d)", (long long)n, NBE_PK_ANISO_MAX_N);
+    if (los < 0 || los > 2) return fail("nbe_power_wedges: los %d is not an array axis (0 .. 2)", los);
+    if (nmu < 1 || nmu > NBE_PK_MAX_MU) return fail("nbe_power_wedges: %d mu bins unsupported (1 .. %d)", nmu, NBE_PK_MAX_MU);
+    const long long total = n * n * (n / 2 + 1);
+    const int nb = (int)(n / 2) + 1;
+    // the (mu, s) bins of one launch: 4 words each and the shells' exponents in a 64 KiB image
+    constexpr int kImageBytes = 65536, kBinBytes = 4 * (int)sizeof(unsigned long long);
+    const int fit = (kImageBytes - nb * (int)sizeof(int)) / kBinBytes;
+    const int cap = max_bins > 0 && max_bins < fit ? max_bins : fit;
+    if (max_bins < 0 || cap < nb)
+        return fail("nbe_power_wedges: max_bins %d holds no mu bin of %d shells", max_bins, nb);
+    const int per = cap / nb;
+    const dim3 g(grid_for(total, 256) < 2048 ? grid_for(total, 256) : 2048), blk(256);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(pk_max_kernel, g, blk, nb * sizeof(unsigned), s, (const float2*)a, (const float2*)b, (long long)n,
+                       (unsigned*)binmax);
+    if (int rc = launched("nbe_power_wedges (max)")) return rc;
+    for (int mu0 = 0; mu0 < nmu; mu0 += per) {
+        const int mu1 = mu0 + per < nmu ? mu0 + per : nmu;
+        hipLaunchKernelGGL(pk_wedge_kernel, g, blk, (size_t)(mu1 - mu0) * nb * kBinBytes + nb * sizeof(int), s,
+                           (const float2*)a, (const float2*)b, (long long)n, los, nmu, mu0, mu1, (const unsigned*)binmax,
+                           (unsigned long long*)sums);
+        if (int rc = launched("nbe_power_wedges (sum)")) return rc;
+    }
+    return 0;
 }
 
 int nbe_field_moments(const void* field, int64_t n, void* moments, void* stream) {

@@ -1,7 +1,8 @@
 // The emulator's input (include/nbe.h, "Input fields"): a linear density field brought to the particle grid and turned
-// into the first-order LPT displacement.  Replaces resize_density_grid and its helpers (scripts/utils.py:186-234,
-// :261-346, :349-425, :531-555, :590-591) and dj.evaluate_lpt_psi_at_a(n_order=1) (scripts/core.py:396-397).  The
-// transforms are the caller's (rocFFT); these are the passes between them.  No context: no weights.
+// into the first-order LPT displacement, and the divergence of a vector field on the same grid.  Replaces
+// resize_density_grid and its helpers (scripts/utils.py:186-234, :261-346, :349-425, :531-555, :590-591) and
+// dj.evaluate_lpt_psi_at_a(n_order=1) (scripts/core.py:396-397); the divergence has no counterpart there.  The transforms
+// are the caller's (rocFFT); these are the passes between them.  No context: no weights.
 //
 // Every kernel walks rows: a (64, 4) workgroup takes four rows (i0, i1) of the destination at a time, decodes the row
 // once (the only 64-bit division) and strides its 64 lanes along the contiguous axis, so that a wave-instruction reads
@@ -49,6 +50,26 @@ __global__ __launch_bounds__(kLanes * kRows) void zeldovich_kernel(const float2*
             dst[i2] = make_float2((float)(-f0 * v.y), (float)(f0 * v.x));
             dst[plane + i2] = make_float2((float)(-f1 * v.y), (float)(f1 * v.x));
             dst[2 * plane + i2] = make_float2((float)(-f2 * v.y), (float)(f2 * v.x));
+        }
+    }
+}
+
+// theta = div v: theta_k = i (2 pi / L) ((m_0 v_0 + m_1 v_1) + m_2 v_2), with component c left out on its own Nyquist row
+// as zeldovich_kernel leaves it out.  The products of an integer below 2^11 and a float32 are exact in float64.
+__global__ __launch_bounds__(kLanes * kRows) void divergence_kernel(const float2* __restrict__ v,
+                                                                    float2* __restrict__ theta, long long n, double kf) {
+    const long long h = n / 2 + 1, rows = n * n, plane = rows * h;
+    const long long nyq = n % 2 == 0 ? n / 2 : -1;
+    NBE_FOR_ROWS(r, rows) {
+        const long long i0 = r / n, i1 = r - i0 * n;
+        const double c0 = i0 == nyq ? 0.0 : (double)freq(i0, n), c1 = i1 == nyq ? 0.0 : (double)freq(i1, n);
+        const float2* src = v + r * h;
+        float2* dst = theta + r * h;
+        for (long long i2 = threadIdx.x; i2 < h; i2 += kLanes) {
+            const double c2 = i2 == nyq ? 0.0 : (double)i2;
+            const float2 v0 = src[i2], v1 = src[plane + i2], v2 = src[2 * plane + i2];
+            const double re = (c0 * v0.x + c1 * v1.x) + c2 * v2.x, im = (c0 * v0.y + c1 * v1.y) + c2 * v2.y;
+            dst[i2] = make_float2((float)(-kf * im), (float)(kf * re));
         }
     }
 }
@@ -306,6 +327,15 @@ int nbe_zeldovich_spectrum(const void* spectrum, int64_t n, double boxsize, doub
     hipLaunchKernelGGL(zeldovich_kernel, row_grid(n), kBlock, 0, (hipStream_t)stream, (const float2*)spectrum,
                        (float2*)psi_spectrum, (long long)n, scale * boxsize / (2.0 * kPi));
     return launched("nbe_zeldovich_spectrum");
+}
+
+int nbe_divergence_spectrum(const void* spectra, int64_t n, double boxsize, void* out, void* stream) {
+    if (!spectra || !out || spectra == out) return fail("nbe_divergence_spectrum: NULL or aliased argument");
+    if (!size_ok(n)) return fail("nbe_divergence_spectrum: n %lld not in %d .. %d", (long long)n, NBE_LPT_MIN_N, NBE_LPT_MAX_N);
+    if (!(boxsize > 0.0) || !std::isfinite(boxsize)) return fail("nbe_divergence_spectrum: bad boxsize %g", boxsize);
+    hipLaunchKernelGGL(divergence_kernel, row_grid(n), kBlock, 0, (hipStream_t)stream, (const float2*)spectra,
+                       (float2*)out, (long long)n, 2.0 * kPi / boxsize);
+    return launched("nbe_divergence_spectrum");
 }
 
 int nbe_spectrum_resize(const void* src, int64_t n_in, void* dst, int64_t n_out, int sphere, void* stream) {

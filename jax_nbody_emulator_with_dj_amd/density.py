@@ -9,6 +9,8 @@ assignment window (`scripts/utils.py:136-148`) and measures P(k) (`scripts/utils
     delta = paint_density(displacement, boxsize=1000.0, res=512, worder=2, deconvolve=True)
     k, pk, nmodes = power_spectrum(delta, boxsize=1000.0)
     k, pk, nmodes = power_spectrum(delta_emu, boxsize=1000.0, other=delta_lpt)     # cross spectrum Re<a b*>
+    mp = power_spectrum_multipoles(delta_s, boxsize=1000.0, los=2)          # k, p0, p2, p4, nmodes
+    wd = power_spectrum_wedges(delta_s, boxsize=1000.0, los=2, nmu=5)       # k, mu, pk, nmodes (nmu, n // 2), mu_edges
     delta_c = deconvolve_mas(delta, worder=2)
     vmesh = paint_field(displacement, velocity, boxsize=1000.0, res=512)     # mass-weighted mean velocity, (3, res...)
     delta_s = paint_density(displacement, res=512, velocity=velocity, los=2, velocity_to_length=rsd_factor(z, Om))
@@ -37,7 +39,8 @@ Conventions (as DISCO-DJ / Pylians and the lattice of `scripts/halos.py:394-403`
   window alone, no alias sum).
 - `power_spectrum` uses the unnormalised forward FFT: P = |delta_k|^2 L^3 / n^6.  Shell b = 1 .. n/2 holds the modes
   with b - 1/2 <= |k| / k_F < b + 1/2, k_F = 2 pi / L, counted over the full complex grid; it returns the mean |k|, the
-  mean P and the number of modes per shell as float64 NumPy arrays.
+  mean P and the number of modes per shell as float64 NumPy arrays.  `power_spectrum_multipoles` and
+  `power_spectrum_wedges` split the same shells by mu = k_los / |k| about an array axis.
 - `minkowski_functionals` (reference `scripts/utils.py:652-763`) counts the elements of the periodic cubical complex of
   each excursion set {w >= t} in one pass over the field: see its docstring for the definition.
 - `bispectrum` (reference `scripts/utils.py:1314-1399`, Pylians `Bk`) is the FFT estimator of B(k1, k2, theta) and of the
@@ -63,11 +66,14 @@ except Exception:  # pragma: no cover
     torch = None
 
 __all__ = ["paint_density", "deconvolve_mas", "power_spectrum", "minkowski_functionals", "bispectrum",
-           "field_statistics", "field_pdf", "paint_field", "rsd_factor"]
+           "field_statistics", "field_pdf", "paint_field", "rsd_factor", "power_spectrum_multipoles",
+           "power_spectrum_wedges"]
 
 WORDERS = {1: "NGP", 2: "CIC", 3: "TSC", 4: "PCS"}
 _UNIT = 2.0 ** 22           # fixed-point units per particle mass (include/nbe.h, nbe_paint_mesh)
-_KEXP = 36                  # the |k| sums of nbe_power_spectrum are in units of 2^-36
+_KEXP = 36                  # the |k| sums of nbe_power_spectrum are in units of 2^-36, and the |mu| sums of nbe_power_wedges
+_PK_ANISO_MAX_N = 2048      # include/nbe.h: NBE_PK_ANISO_MAX_N, NBE_PK_MAX_MU
+_PK_MAX_MU = 64
 _MF_MAX_N = 2048            # include/nbe.h: NBE_MF_MAX_N, NBE_MF_MAX_THRESHOLDS, NBE_MOMENTS_WORDS
 _MF_MAX_T = 1024
 _MOMENT_WORDS = 2050
@@ -229,12 +235,17 @@ def _deconvolve(delta, worder):
     return torch.fft.irfftn(fk, s=res).contiguous()
 
 
-def _validate_shift(velocity, los, velocity_to_length, n, kind_of, what):
-    """The line-of-sight arguments: (velocity array or None, los, velocity_to_length as a float or None)."""
+def _check_los(los):
     if isinstance(los, (bool, np.bool_)) or not isinstance(los, numbers.Integral) or int(los) not in (0, 1, 2):
         raise ValueError("los must be the array axis 0, 1 or 2, got %r" % (los,))
+    return int(los)
+
+
+def _validate_shift(velocity, los, velocity_to_length, n, kind_of, what):
+    """The line-of-sight arguments: (velocity array or None, los, velocity_to_length as a float or None)."""
+    los = _check_los(los)
     if velocity is None:
-        return None, int(los), None
+        return None, los, None
     v = _check_array(velocity, "velocity")
     if tuple(v.shape) not in ((3,) + tuple(n), tuple(n)):
         raise ValueError("velocity must have shape %s or %s, got %s" % ((3,) + tuple(n), tuple(n), tuple(v.shape)))
@@ -243,7 +254,7 @@ def _validate_shift(velocity, los, velocity_to_length, n, kind_of, what):
     _same_kind(kind_of, v, what, "velocity")
     if velocity_to_length is None:
         raise ValueError("velocity_to_length is required with a velocity (rsd_factor(z, Om) for redshift space)")
-    return v, int(los), _real(velocity_to_length, "velocity_to_length")
+    return v, los, _real(velocity_to_length, "velocity_to_length")
 
 
 def _same_kind(a, b, name_a, name_b):
@@ -446,7 +457,22 @@ def power_spectrum(delta, boxsize=1000.0, other=None):
     delta / other: (n, n, n) float32, NumPy arrays or CUDA tensors on one device.  boxsize: L (scalar, or a 3-tuple of
     equal values).  Returns (k, pk, nmodes), float64 NumPy arrays of n // 2 shells: the mean |k| (h/Mpc for L in Mpc/h),
     the mean P = |delta_k|^2 L^3 / n^6 and the number of modes of the full complex grid."""
-    d, n, L = _cubic(delta, "delta", boxsize, "power_spectrum", "mesh", 2, 4096)
+    d, n, L, o = _validate_spectrum(delta, boxsize, other, "power_spectrum", 4096)
+    dev = _device_of(d)
+    nb = n // 2 + 1
+    with torch.cuda.device(dev):
+        a, b = _half_spectra(d, o, dev)
+        binmax = torch.zeros(nb, dtype=torch.int32, device=dev)
+        sums = torch.zeros(3 * nb, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().nbe_power_spectrum(_ptr(a), _ptr_or_null(b), n, _ptr(binmax), _ptr(sums), _stream(dev)))
+        bm = binmax.cpu().numpy()[1:]
+        sm = sums.cpu().numpy().reshape(3, nb)[:, 1:]
+    return _shell_means(bm, sm[0], sm[1], sm[2], np.arange(1, nb, dtype=np.float64), _KEXP, L, n)
+
+
+def _validate_spectrum(delta, boxsize, other, what, max_n):
+    """The inputs of the two-point calls: (delta, n, L, other or None)."""
+    d, n, L = _cubic(delta, "delta", boxsize, what, "mesh", 2, max_n)
     o = None
     if other is not None:
         o = _check_array(other, "other")
@@ -454,19 +480,86 @@ def power_spectrum(delta, boxsize=1000.0, other=None):
             raise ValueError("other must match delta: float32 %s, got %s %s"
                              % (tuple(d.shape), _dtype_name(o), tuple(o.shape)))
         _same_kind(d, o, "delta", "other")
+    return d, n, L, o
+
+
+def _half_spectra(d, o, dev):
+    """(a, b or None): the row-major half spectra of delta and, where given, of other, on the device."""
+    a = torch.fft.rfftn(_to_device(d, dev, (torch.float32,))).contiguous()
+    b = torch.fft.rfftn(_to_device(o, dev, (torch.float32,))).contiguous() if o is not None else None
+    return a, b
+
+
+def _ptr_or_null(t):
+    return _ptr(t) if t is not None else None
+
+
+def power_spectrum_multipoles(delta, boxsize=1000.0, los=2, other=None):
+    """Monopole, quadrupole and hexadecapole of the power spectrum about the array axis `los` (reference
+    scripts/utils.py:1083-1085, :1447-1449: the columns Pk[:, 0..2] of Pylians' Pk_library.Pk(delta, boxsize, axis));
+    with `other`, of the cross spectrum Re<delta other*>.
+
+    P_l(s) = (2 l + 1) sum(w p L_l(mu)) / sum(w) L^3 / n^6 over the shells, weights and terms p of `power_spectrum`, with
+    mu^2 = m_los^2 / |m|^2 and the Legendre polynomials L_0 = 1, L_2 = (3 mu^2 - 1) / 2, L_4 = (35 mu^4 - 30 mu^2 + 3) / 8.
+    For a redshift-space density, los is the axis the particles were moved along (paint_density's `los`).
+
+    delta / other: (n, n, n) float32, 2 <= n <= 2048, NumPy arrays or CUDA tensors on one device.  Returns a dict of
+    float64 NumPy arrays of n // 2 shells: k, p0, p2, p4, nmodes.  k, p0 and nmodes are the bits of `power_spectrum`;
+    values are NaN in a shell that holds a non-finite term."""
+    d, n, L, o = _validate_spectrum(delta, boxsize, other, "power_spectrum_multipoles", _PK_ANISO_MAX_N)
+    los = _check_los(los)
     dev = _device_of(d)
-    l = _lib.lib()
     nb = n // 2 + 1
     with torch.cuda.device(dev):
-        a = torch.fft.rfftn(_to_device(d, dev, (torch.float32,))).contiguous()
-        b = torch.fft.rfftn(_to_device(o, dev, (torch.float32,))).contiguous() if o is not None else None
+        a, b = _half_spectra(d, o, dev)
         binmax = torch.zeros(nb, dtype=torch.int32, device=dev)
-        sums = torch.zeros(3 * nb, dtype=torch.int64, device=dev)
-        _lib.check(l.nbe_power_spectrum(_ptr(a), _ptr(b) if b is not None else None, n, _ptr(binmax), _ptr(sums),
-                                        _stream(dev)))
+        sums = torch.zeros(5 * nb, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().nbe_power_multipoles(_ptr(a), _ptr_or_null(b), n, los, _ptr(binmax), _ptr(sums),
+                                                   _stream(dev)))
         bm = binmax.cpu().numpy()[1:]
-        sm = sums.cpu().numpy().reshape(3, nb)[:, 1:]
-    return _shell_means(bm, sm[0], sm[1], sm[2], np.arange(1, nb, dtype=np.float64), _KEXP, L, n)
+        sm = sums.cpu().numpy().reshape(5, nb)[:, 1:]
+    koff = np.arange(1, nb, dtype=np.float64)
+    k, p0, cnt = _shell_means(bm, sm[0], sm[1], sm[2], koff, _KEXP, L, n)
+    p2, p4 = (_shell_means(bm, sm[0], sm[1], sm[w], koff, _KEXP, L, n)[1] for w in (3, 4))
+    return dict(k=k, p0=p0, p2=5.0 * p2, p4=9.0 * p4, nmodes=cnt)
+
+
+def _check_nmu(nmu):
+    if isinstance(nmu, (bool, np.bool_)) or not isinstance(nmu, numbers.Integral) or not 1 <= int(nmu) <= _PK_MAX_MU:
+        raise ValueError("nmu must be an int in 1 .. %d, got %r" % (_PK_MAX_MU, nmu))
+    return int(nmu)
+
+
+def power_spectrum_wedges(delta, boxsize=1000.0, los=2, nmu=5, other=None, _max_bins=None):
+    """The power spectrum in wedges of |mu| = |k_los| / |k| about the array axis `los` (reference scripts/utils.py:1083-1085,
+    :1447-1449: the 2-D spectrum of Pylians' Pk_library.Pk(delta, boxsize, axis), here binned in (k, mu)); with `other`,
+    the cross spectrum Re<delta other*>.
+
+    The shells, weights and terms are those of `power_spectrum`.  Of `nmu` equal bins of |mu| in [0, 1], 1 <= nmu <= 64,
+    mode m falls into bin floor(nmu |mu|), and |mu| = 1 into the last: decided in integers as
+    min(nmu - 1, #{ j in 1 .. nmu-1 : j^2 |m|^2 <= nmu^2 m_los^2 }), so no bin edge depends on a rounding.
+
+    delta / other: (n, n, n) float32, 2 <= n <= 2048, NumPy arrays or CUDA tensors on one device.  Returns a dict of
+    float64 NumPy arrays: k, mu (the mean |k| and |mu| of the bin's modes), pk and nmodes of shape (nmu, n // 2), and
+    mu_edges = arange(nmu + 1) / nmu.  A bin without a mode, or in a shell that holds a non-finite term, is NaN.
+    `_max_bins` caps the (mu, k) bins of one launch (tests): the sums are integers, so the bits do not depend on it."""
+    d, n, L, o = _validate_spectrum(delta, boxsize, other, "power_spectrum_wedges", _PK_ANISO_MAX_N)
+    los, nmu = _check_los(los), _check_nmu(nmu)
+    dev = _device_of(d)
+    nb = n // 2 + 1
+    with torch.cuda.device(dev):
+        a, b = _half_spectra(d, o, dev)
+        binmax = torch.zeros(nb, dtype=torch.int32, device=dev)
+        sums = torch.zeros(4 * nmu * nb, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().nbe_power_wedges(_ptr(a), _ptr_or_null(b), n, los, nmu, int(_max_bins or 0), _ptr(binmax),
+                                               _ptr(sums), _stream(dev)))
+        bm = np.tile(binmax.cpu().numpy()[1:], (nmu, 1))
+        sm = sums.cpu().numpy().reshape(4, nmu, nb)[:, :, 1:]
+    koff = np.tile(np.arange(1, nb, dtype=np.float64), (nmu, 1))
+    k, pk, cnt = _shell_means(bm, sm[0], sm[1], sm[3], koff, _KEXP, L, n)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mu = np.ldexp(sm[2].astype(np.float64), -_KEXP) / cnt
+    return dict(k=k, mu=mu, pk=pk, nmodes=cnt, mu_edges=np.arange(nmu + 1) / nmu)
 
 
 def _shell_means(binmax, weight, ksum, psum, koff, kexp, L, n):

@@ -4,12 +4,13 @@ LPT displacement that `process_box` reads.
 The reference's pipeline does this before `process_box` with DISCO-DJ, JAX and Pylians (`scripts/core.py:302-409`:
 `resize_density_grid`, `scripts/utils.py:186-234`, `:261-425`, `:531-592`; `dj.evaluate_lpt_psi_at_a(n_order=1)`).
 
-    from jax_nbody_emulator_with_dj_amd.lpt import zeldovich_displacement, resize_density, gaussian_smooth
+    from jax_nbody_emulator_with_dj_amd.lpt import zeldovich_displacement, resize_density, gaussian_smooth, divergence
 
     delta512 = resize_density(delta256, 512, boxsize=1000.0, upsample_method="fourier")
     psi = zeldovich_displacement(delta512, boxsize=1000.0)                 # (3, 512, 512, 512), process_box's input
     delta128 = resize_density(delta256, 128, boxsize=1000.0, upsample_method="fourier", downsample_method="gaussian")
     smooth = gaussian_smooth(delta256, boxsize=1000.0, sigma=8.0)
+    theta = divergence(vmesh, boxsize=1000.0)                              # (3, n, n, n) -> (n, n, n)
 
 Conventions:
 
@@ -108,6 +109,36 @@ def zeldovich_displacement(delta, boxsize=1000.0, scale=1.0, _max_batch=None):
             for c in range(3):
                 psi[c:c + 1] = torch.fft.irfftn(psi_k[c:c + 1], s=(n, n, n), dim=(1, 2, 3))
     return _back(d, psi)
+
+
+def divergence(field, boxsize=1000.0):
+    """theta = div v of a vector field on a periodic grid, by the spectral derivative: what turns the mass-weighted
+    velocity mesh of density.paint_field into the field whose spectra P_theta-theta = power_spectrum(theta) and
+    P_delta-theta = power_spectrum(delta, other=theta) check an emulated velocity (the reference's pipeline has no such
+    step).
+
+    field: (3, n, n, n) float32, component c along array axis c, NumPy array or CUDA tensor, 2 <= n <= 2048.  boxsize: L
+    (scalar, or a 3-tuple of equal values); theta is in the field's unit per unit of L.  Returns (n, n, n) float32 of the
+    input's kind.
+
+    theta_k = i (2 pi / L) ((m_0 v_0 + m_1 v_1) + m_2 v_2), added in float64 in that order, each word rounded to float32
+    once.  Where n is even, component c contributes nothing on its own Nyquist row |m_c| = n/2, as in
+    `zeldovich_displacement`: the row has no sign, the field stays real and the axes are treated alike.  So
+    divergence(zeldovich_displacement(x)) = -x for an x without power on those rows.
+
+    One batched rfftn over the three components, one pass that reads them once, one irfftn."""
+    f = _check_array(field, "field")
+    if f.ndim != 4 or f.shape[0] != 3 or len(set(f.shape[1:])) != 1:
+        raise ValueError("divergence needs a (3, n, n, n) field, got shape %s" % (tuple(f.shape),))
+    _, n, L = _cubic(f[0], "field", boxsize, "divergence", "(3, n, n, n) field", MIN_N, MAX_N)
+    dev = _device_of(f)
+    with torch.cuda.device(dev):
+        spec = torch.fft.rfftn(_to_device(f, dev, (torch.float32,)), dim=(1, 2, 3)).contiguous()
+        theta_k = _empty_spectrum(n, dev)
+        _lib.check(_lib.lib().nbe_divergence_spectrum(_ptr(spec), n, L, _ptr(theta_k), _stream(dev)))
+        del spec
+        theta = _real_field(theta_k, n)
+    return _back(f, theta)
 
 
 # ---- resizing --------------------------------------------------------------------------------------------------------------

@@ -29,7 +29,10 @@ counts, pdf, outside, nonfinite).  With `--vel`, `--paint_vel` writes <output_di
 mass-weighted mean velocity on the same mesh (density.paint_field, normalize="density", not deconvolved), and `--rsd AXIS`
 writes <output_dir>/emu_delta_rsd.npy, the density with every particle moved by v_AXIS (1 + z) / H(z) along array axis
 AXIS (density.rsd_factor of the box's own redshift and Omega_m; `--mas_worder` and `--no-deconvolve` apply), and with
-`--pk` its power spectrum <output_dir>/emu_pk_rsd.npz.  Painting reads the float32 displacement on the device; the saved emu_dis.npy is
+`--pk` its power spectrum <output_dir>/emu_pk_rsd.npz.  With `--rsd`, `--pk_multipoles` writes
+<output_dir>/emu_pk_rsd_multipoles.npz (k, p0, p2, p4, nmodes: density.power_spectrum_multipoles of emu_delta_rsd about
+AXIS) and `--pk_wedges NMU` writes <output_dir>/emu_pk_rsd_wedges.npz (k, mu, pk, nmodes, mu_edges:
+density.power_spectrum_wedges in NMU bins of |mu|, 1 .. 64).  Painting reads the float32 displacement on the device; the saved emu_dis.npy is
 rounded to --output-precision afterwards.
 
 What differs from the reference: the engine, its weights and its ~100 GB workspace stay resident on the
@@ -186,6 +189,12 @@ def build_parser():
     ap.add_argument('--rsd', type=int, choices=(0, 1, 2), metavar='AXIS', default=argparse.SUPPRESS,
                     help='With --vel and --density_res: also write the redshift-space density along array axis AXIS to '
                          '<output_dir>/emu_delta_rsd.npy (and with --pk <output_dir>/emu_pk_rsd.npz)')
+    ap.add_argument('--pk_multipoles', action='store_true', default=argparse.SUPPRESS,
+                    help='With --rsd: also write the monopole, quadrupole and hexadecapole of the redshift-space density '
+                         'about AXIS to <output_dir>/emu_pk_rsd_multipoles.npz (k, p0, p2, p4, nmodes)')
+    ap.add_argument('--pk_wedges', type=int, metavar='NMU', default=argparse.SUPPRESS,
+                    help='With --rsd: also write the power spectrum of the redshift-space density in NMU wedges of |mu| '
+                         'about AXIS to <output_dir>/emu_pk_rsd_wedges.npz (k, mu, pk, nmodes, mu_edges)')
     return ap
 
 
@@ -247,9 +256,29 @@ def velocity_options(args):
     return paint_vel, (None if rsd is None else int(rsd))
 
 
-def velocity_fields(disp, vel, dens, paint_vel, rsd, z, Om):
-    """The arrays of emu_vel_mesh.npy, emu_delta_rsd.npy and emu_pk_rsd.npz for the device fields of one box."""
-    from .density import paint_density, paint_field, power_spectrum, rsd_factor
+MAX_WEDGES = 64                                          # density.power_spectrum_wedges: 1 <= nmu <= 64
+
+
+def anisotropy_options(args):
+    """(multipoles, wedges): whether --pk_multipoles was given, and the bin count of --pk_wedges or None (read apart from
+    density_options, whose dict they leave as it was).  Both measure emu_delta_rsd, so both need --rsd and --density_res."""
+    multipoles = bool(getattr(args, 'pk_multipoles', False))
+    wedges = getattr(args, 'pk_wedges', None)
+    for flag, name in ((multipoles, '--pk_multipoles'), (wedges is not None, '--pk_wedges')):
+        if flag and getattr(args, 'density_res', None) is None:
+            _die(f'{name} needs --density_res')
+        if flag and getattr(args, 'rsd', None) is None:
+            _die(f'{name} needs --rsd')
+    if wedges is not None and not 1 <= int(wedges) <= MAX_WEDGES:
+        _die(f'--pk_wedges must be in 1 .. {MAX_WEDGES}, got {wedges}')
+    return multipoles, (None if wedges is None else int(wedges))
+
+
+def velocity_fields(disp, vel, dens, paint_vel, rsd, z, Om, multipoles=False, wedges=None):
+    """The arrays of emu_vel_mesh.npy, emu_delta_rsd.npy, emu_pk_rsd.npz, emu_pk_rsd_multipoles.npz and
+    emu_pk_rsd_wedges.npz for the device fields of one box."""
+    from .density import (paint_density, paint_field, power_spectrum, power_spectrum_multipoles, power_spectrum_wedges,
+                          rsd_factor)
     out = {}
     if paint_vel:
         out['vel_mesh'] = paint_field(disp, vel, boxsize=dens['boxsize'], res=dens['res'], worder=dens['worder'],
@@ -261,6 +290,10 @@ def velocity_fields(disp, vel, dens, paint_vel, rsd, z, Om):
         out['delta_rsd'] = delta.cpu().numpy()
         if dens['pk']:
             out['pk_rsd'] = power_spectrum(delta, boxsize=dens['boxsize'])
+        if multipoles:
+            out['pk_rsd_multipoles'] = power_spectrum_multipoles(delta, boxsize=dens['boxsize'], los=rsd)
+        if wedges is not None:
+            out['pk_rsd_wedges'] = power_spectrum_wedges(delta, boxsize=dens['boxsize'], los=rsd, nmu=wedges)
     return out
 
 
@@ -314,6 +347,7 @@ def run(args):
     mink = minkowski_option(args)
     bispec, onepoint = summary_options(args)
     paint_vel, rsd = velocity_options(args)
+    multipoles, wedges = anisotropy_options(args)
     if bispec:
         for k1, k2 in BISPECTRUM_CONFIGS:                    # density.bispectrum's closure condition, before any work
             if 2.0 * (k1 + k2) * dens['boxsize'] / (2.0 * np.pi) + 1.5 >= dens['res']:
@@ -323,7 +357,8 @@ def run(args):
         print(f"  Density: {dens['res']}^3 mesh, worder {dens['worder']}, deconvolve {dens['deconvolve']}, "
               f"boxsize {dens['boxsize']}, P(k) {dens['pk']}" + (", Minkowski functionals" if mink else "")
               + (", bispectrum" if bispec else "") + (", one-point statistics" if onepoint else "")
-              + (", velocity mesh" if paint_vel else "") + (f", redshift space along axis {rsd}" if rsd is not None else ""))
+              + (", velocity mesh" if paint_vel else "") + (f", redshift space along axis {rsd}" if rsd is not None else "")
+              + (", multipoles" if multipoles else "") + (f", {wedges} wedges" if wedges is not None else ""))
     print()
 
     shape = None
@@ -369,6 +404,10 @@ def run(args):
             if 'pk_rsd' in extra:
                 k, pk, nmodes = extra['pk_rsd']
                 np.savez(out_dir / 'emu_pk_rsd.npz', k=k, pk=pk, nmodes=nmodes)
+            if 'pk_rsd_multipoles' in extra:
+                np.savez(out_dir / 'emu_pk_rsd_multipoles.npz', **extra['pk_rsd_multipoles'])
+            if 'pk_rsd_wedges' in extra:
+                np.savez(out_dir / 'emu_pk_rsd_wedges.npz', **extra['pk_rsd_wedges'])
 
     def with_density(dis_in, z, Om):
         """process_box on the device, the density field of its float32 displacement, host copies of the fields."""
@@ -387,7 +426,7 @@ def run(args):
         if bispec or onepoint:
             extra['bk'], extra['onepoint'] = density_summaries(delta, dens, bispec, onepoint)
         if paint_vel or rsd is not None:
-            extra.update(velocity_fields(disp, result[1], dens, paint_vel, rsd, z, Om))
+            extra.update(velocity_fields(disp, result[1], dens, paint_vel, rsd, z, Om, multipoles, wedges))
         out_dt = np.dtype(args.output_precision)
         host = tuple(t.cpu().numpy().astype(out_dt, copy=False) for t in (result if args.vel else (result,)))
         return (host if args.vel else host[0]), extra
