@@ -399,7 +399,50 @@ int nbe_field_moments4(const void* field, int64_t count, void* moments, void* st
 int nbe_field_histogram(const void* field, int64_t count, double lo, double hi, const void* edges, int nbins,
                         void* counts, void* stream);
 
-/* ---- Input fields (no context) ---------------------------------------------------------------------
+/* ---- Halos (no context) ------------------------------------------------------------------------------
+ * Friends-of-friends groups of the displaced lattice, the step of scripts/halos.py.  Pointers,
+ * `stream` and asynchrony as for "Density".  disp = (3, n, n, n) in a cubic periodic box of side boxsize.  Particle
+ * p = (i0 n + i1) n + i2 has the integer coordinates X_c = rint((i_c / n + psi_c / L) 2^30) mod 2^30 (float64); the
+ * minimum-image difference d_c(p, q) is (X_c(p) - X_c(q)) mod 2^30 in [-2^29, 2^29); p != q are linked iff
+ * d_0^2 + d_1^2 + d_2^2 <= r2 in 64-bit integers.  A group is a connected component, labelled by its smallest particle
+ * index.  Cells: (X_c ncell) >> 30 per axis, key (c0 ncell + c1) ncell + c2, with 3 <= ncell <= NBE_FOF_MAX_CELLS and
+ * ncell (isqrt(r2) + 1) <= 2^30 so that linked particles share a cell or sit in adjacent ones.  max_blocks > 0 caps the
+ * grid of a launch (tests); every result is made of integer sums and minima and does not depend on it.  The calls, in
+ * order: nbe_fof_cells, the caller's sort of `keys`, nbe_fof_gather, nbe_fof_link, nbe_fof_labels, the caller's choice of
+ * halos, nbe_fof_catalog. */
+#define NBE_FOF_MIN_N 2
+#define NBE_FOF_MAX_N 1024
+#define NBE_FOF_MAX_CELLS 4096
+/* replaces load_local_positions_from_displacement (scripts/halos.py:359-404): one read of the displacement.  coords =
+ * (3, n^3) int32 receives X; keys = n^3 int64 the cell keys; parent = n^3 int32 the identity; stats = 1 int32, zeroed by
+ * the caller, counts the particles with a non-finite displacement or |psi_c / L| >= 2^20 (their X and key are 0: the
+ * caller must not go on). */
+int nbe_fof_cells(const void* disp, int disp_dtype, int64_t n, double boxsize, int ncell, int max_blocks, void* coords,
+                  void* keys, void* parent, void* stats, void* stream);
+/* the neighbour structure of nbodykit's FOF (scripts/halos.py:407-432, run_fof): order = count int64, the particle
+ * indices in ascending order of their keys (ties in any order); sorted = count records of 4 int32 (X_0, X_1, X_2, p) in
+ * that order. */
+int nbe_fof_gather(const void* coords, const void* order, int64_t count, int max_blocks, void* sorted, void* stream);
+/* replaces the FOF(...) run of scripts/halos.py:426-432: sorted as above, sorted_keys = count int64 ascending (the sorted
+ * `keys`), parent as nbe_fof_cells left it.  One thread per particle tests each candidate pair of its own and 13 of its
+ * neighbour cells once and joins linked pairs in parent[] without locks.  Out: a forest with parent[x] <= x whose trees
+ * are the groups and whose roots are the labels. */
+int nbe_fof_link(const void* sorted, const void* sorted_keys, int64_t count, int ncell, int64_t r2, int max_blocks,
+                 void* parent, void* stream);
+/* replaces fof.labels and the Length column of fof_catalog (scripts/halos.py:433-448): parent[x] becomes the label (root)
+ * of x; sizes = count int32, zeroed by the caller, receives the group sizes at the labels and 0 elsewhere. */
+int nbe_fof_labels(void* parent, int64_t count, int max_blocks, void* sizes, void* stream);
+/* replaces the CMPosition / CMVelocity sums of fof_catalog (scripts/halos.py:433-448): slot = count int32, the halo's row
+ * at its label and -1 elsewhere.  sums = (rows, 3) int64 without a velocity, (rows, 6) with one, zeroed by the caller:
+ * every member x of row s adds d_c(x, label) to sums[s][c] and, with velocity = (3, count) float32 / float16 and
+ * exponents e_c (max |v_c| < 2^e_c, nbe_quantity_range), rint(v_c 2^(24 - e_c)) to sums[s][3 + c].  labels = count int32
+ * or NULL: receives slot[parent[x]].  wave_reduce != 0 adds runs of one row inside a wave with one atomic: the same
+ * integers; the Python caller passes 0, which measured faster. */
+int nbe_fof_catalog(const void* coords, const void* parent, const void* slot, const void* velocity, int velocity_dtype,
+                    const int exponents[3], int64_t count, int wave_reduce, int max_blocks, void* sums, void* labels,
+                    void* stream);
+
+/* ---- Input fields (no context)---------------------------------------------------------------------
  * The reference's pipeline brings a linear density field to the particle grid (resize_density_grid) and turns it into
  * the first-order LPT displacement before process_box (scripts/core.py:302-409).  These are the passes between the
  * caller's transforms.  Pointers, `stream` and asynchrony as for "Density".  A spectrum is torch's

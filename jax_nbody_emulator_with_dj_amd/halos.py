@@ -1,0 +1,351 @@
+"""Friends-of-friends halos of an emulated box, on the GPU: the step of the reference's `scripts/halos.py`.
+
+That script turns the saved displacement into particle positions (`:359-404`), runs nbodykit's MPI FoF finder on them
+(`run_fof`, `:407-450`), writes `fof_catalog.npz` (`:871-881`) and derives the empirical halo mass function (`:317-349`).
+Here the displacement stays where `process_box` left it:
+
+    from jax_nbody_emulator_with_dj_amd.halos import fof_halos, particle_mass, halo_mass_function, density_slab
+
+    cat = fof_halos(displacement, boxsize=1000.0, linking_length=0.2, nmin=20)      # CMPosition, Length, label, ...
+    m = particle_mass(0.3175, 1000.0, 512)
+    hmf = halo_mass_function(cat["Length"], 1000.0, m, np.linspace(12.5, 15.5, 31))
+    slab, ncells = density_slab(delta, 1000.0, axis=0, center=500.0, width=20.0)
+
+    python -m jax_nbody_emulator_with_dj_amd.halos --displacement_file emu_dis.npy --output_dir out/
+
+Definition (DESIGN.md section 12.5 has the proofs; tests/fof_ref.py restates it in NumPy).  With U = 2^30, particle
+p = (i0 n + i1) n + i2 of the (n, n, n) lattice has the integer coordinates X_c = rint((i_c / n + psi_c / L) U) mod U,
+formed in float64 from the stored float32 / float16 value: the lattice of `scripts/halos.py:394-403` in units of L / U.
+The linking length is l = linking_length L / n, or linking_length itself with absolute=True (nbodykit's meanings), and
+R2 = floor((l / L)^2 2^60).  The minimum-image difference d_c(p, q) is (X_c(p) - X_c(q)) mod U mapped to [-U/2, U/2);
+p != q are linked iff d_0^2 + d_1^2 + d_2^2 <= R2 in 64-bit integers, so no rounding decides a link and coincident
+particles link.  A group is a connected component of the links, its label its smallest particle index, Length its size; a
+halo is a group with Length >= nmin; halos are ordered by Length descending, then label ascending.  With S_c the integer
+sum of d_c(p, label) over the members, CMPosition_c = (((X_c(label) + S_c / Length) mod U) / U) L in float64: nbodykit's
+periodic convention (offsets from one member), meaningful for groups narrower than L / 2.  With a velocity, channel c has
+the exponent e_c of `paint_field` (max |v_c| < 2^e_c), a member adds rint(v 2^(24 - e_c)) to an integer sum, and
+CMVelocity_c = sum 2^(e_c - 24) / Length.  All sums are integers: every output is the same bits for every launch
+geometry, tie order of the sort and stream.
+
+Residency as in density.py: NumPy in gives NumPy out, a CUDA tensor in gives CUDA tensors on its device, on torch's
+current stream.  There is no CPU fallback.  Arguments are validated before any device work.
+"""
+
+import argparse
+import ctypes as C
+import math
+import numbers
+import os
+import sys
+
+import numpy as np
+
+from . import _lib
+from ._lib import NBEError
+from .density import (_back, _check_array, _device_of, _dtype_name, _is_torch, _ptr, _real, _same_kind, _stream,
+                      _to_device, _triple)
+
+try:
+    import torch
+except Exception:  # pragma: no cover
+    torch = None
+
+__all__ = ["fof_halos", "particle_mass", "halo_mass_function", "density_slab"]
+
+_U = 1 << 30                    # include/nbe.h, "Halos": coordinate units per box side
+_MIN_N, _MAX_N = 2, 1024        # NBE_FOF_MIN_N, NBE_FOF_MAX_N
+_MAX_CELLS = 4096               # NBE_FOF_MAX_CELLS
+BYTES_PER_PARTICLE = 72         # peak device memory of fof_halos beside its inputs
+RHO_CRIT = 2.77536627e11        # h^2 M_sun / Mpc^3 (scripts/halos.py, RHO_CRIT_H2_MSUN_MPC3)
+
+
+def _int(v, name, lo):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Integral) or int(v) < lo:
+        raise ValueError("fof_halos: %s must be an int >= %d, got %r" % (name, lo, v))
+    return int(v)
+
+
+def linking_geometry(n, boxsize, linking_length, absolute):
+    """(l, R2, ncell) of a call: the absolute linking length, floor((l / L)^2 2^60), and the cells per axis
+    min(4096, U // (isqrt(R2) + 1)).  ValueError for a length that is not positive or leaves fewer than 3 cells."""
+    b = _real(linking_length, "fof_halos: linking_length", positive=True)
+    ell = b if absolute else b * boxsize / n
+    if not ell < boxsize:
+        raise ValueError("fof_halos: the linking length %g must stay below L / 3 = %g (at least 3 cells per axis)"
+                         % (ell, boxsize / 3.0))
+    R2 = int(math.floor((ell / boxsize) ** 2 * 2.0 ** 60))
+    ncell = min(_MAX_CELLS, _U // (math.isqrt(R2) + 1))
+    if ncell < 3:
+        raise ValueError("fof_halos: the linking length %g must stay below L / 3 = %g (at least 3 cells per axis)"
+                         % (ell, boxsize / 3.0))
+    return ell, R2, ncell
+
+
+def _validate(displacement, boxsize, linking_length, nmin, absolute, velocity, max_blocks):
+    x = _check_array(displacement, "displacement")
+    if x.ndim != 4 or x.shape[0] != 3 or len(set(x.shape[1:])) != 1:
+        raise ValueError("fof_halos: displacement must have shape (3, n, n, n), got %s" % (tuple(x.shape),))
+    if _dtype_name(x) not in ("float32", "float16"):
+        raise ValueError("fof_halos: displacement must be float32 or float16, got %s" % _dtype_name(x))
+    n = int(x.shape[1])
+    if not _MIN_N <= n <= _MAX_N:
+        raise ValueError("fof_halos: lattice size %d unsupported (%d .. %d)" % (n, _MIN_N, _MAX_N))
+    L = _triple(boxsize, "boxsize", "a length")
+    if len(set(L)) != 1:
+        raise ValueError("fof_halos needs a cubic box, got boxsize %s" % (L,))
+    nmin = _int(nmin, "nmin", 1)
+    ell, R2, ncell = linking_geometry(n, L[0], linking_length, bool(absolute))
+    v = None
+    if velocity is not None:
+        v = _check_array(velocity, "velocity")
+        if tuple(v.shape) != tuple(x.shape):
+            raise ValueError("fof_halos: velocity must have the displacement's shape %s, got %s"
+                             % (tuple(x.shape), tuple(v.shape)))
+        if _dtype_name(v) not in ("float32", "float16"):
+            raise ValueError("fof_halos: velocity must be float32 or float16, got %s" % _dtype_name(v))
+        _same_kind(x, v, "fof_halos: displacement", "velocity")
+    blocks = 0 if max_blocks is None else _int(max_blocks, "_max_blocks", 1)
+    return x, n, L[0], nmin, ell, R2, ncell, v, blocks
+
+
+def _check_memory(dev, count):
+    free, _ = torch.cuda.mem_get_info(dev)
+    free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)      # cached blocks are reusable
+    need = BYTES_PER_PARTICLE * count
+    if need > free:
+        raise NBEError("fof_halos: %d particles need about %.1f GB of device memory (%d bytes each), %.1f GB are free"
+                       % (count, need / 1e9, BYTES_PER_PARTICLE, free / 1e9))
+
+
+def _velocity_exponents(l, vd, count, s, dev):
+    """(C int[3]) e_c with max |v_c| < 2^e_c, by nbe_quantity_range; ValueError for a non-finite value."""
+    rng = torch.zeros(4, dtype=torch.int32, device=dev)
+    _lib.check(l.nbe_quantity_range(_ptr(vd), 1 if vd.dtype == torch.float16 else 0, 3, count, _ptr(rng), s))
+    r = rng.cpu().numpy()
+    if int(r[3]):
+        raise ValueError("fof_halos: %d value(s) of the velocity are not finite" % int(r[3:].view(np.uint32)[0]))
+    exps = (C.c_int * 3)()
+    for c, e in enumerate(np.frexp(r[:3].view(np.float32).astype(np.float64))[1]):
+        exps[c] = int(e)
+    return exps
+
+
+def _stages(xd, vd, n, L, nmin, R2, ncell, blocks, want_labels, wave_reduce=False, timer=None):
+    """Device work of fof_halos on contiguous CUDA tensors.  Returns (label, length, X of the labels (H, 3), sums (H, 3 or 6)
+    -- all host int64 arrays --, velocity exponents or None, ngroups, labels tensor or None).  wave_reduce adds runs of one halo inside a
+    wave before the atomic: the same integers, slower where few particles belong to halos, so off.
+    `timer(name)` is called before every stage (cells, sort, gather, link, labels, select, catalog, finish) and timer(None) at the end
+    (tools/time_fof.py)."""
+    l = _lib.lib()
+    dev = xd.device
+    count = n ** 3
+    tick = timer or (lambda name: None)
+    with torch.cuda.device(dev):
+        s = _stream(dev)
+        exps = None if vd is None else _velocity_exponents(l, vd, count, s, dev)
+        tick("cells")
+        X = torch.empty((3, count), dtype=torch.int32, device=dev)
+        keys = torch.empty(count, dtype=torch.int64, device=dev)
+        parent = torch.empty(count, dtype=torch.int32, device=dev)
+        stats = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(l.nbe_fof_cells(_ptr(xd), 1 if xd.dtype == torch.float16 else 0, n, L, ncell, blocks, _ptr(X), _ptr(keys),
+                                   _ptr(parent), _ptr(stats), s))
+        tick("sort")
+        sk, order = torch.sort(keys)
+        del keys
+        tick("gather")
+        bad = int(stats.item())
+        if bad:
+            raise ValueError("fof_halos: %d particle(s) have a non-finite or out-of-range displacement" % bad)
+        P = torch.empty((count, 4), dtype=torch.int32, device=dev)
+        _lib.check(l.nbe_fof_gather(_ptr(X), _ptr(order), count, blocks, _ptr(P), s))
+        del order
+        tick("link")
+        _lib.check(l.nbe_fof_link(_ptr(P), _ptr(sk), count, ncell, R2, blocks, _ptr(parent), s))
+        tick("labels")
+        del P, sk
+        sizes = torch.zeros(count, dtype=torch.int32, device=dev)
+        _lib.check(l.nbe_fof_labels(_ptr(parent), count, blocks, _ptr(sizes), s))
+        tick("select")
+        ngroups = int(torch.count_nonzero(sizes))
+        label = torch.nonzero(sizes >= nmin).reshape(-1)
+        length = sizes[label].to(torch.int64)
+        rank = torch.argsort(((1 << 31) - length) * (1 << 31) + label)      # Length descending, then label ascending
+        label, length = label[rank], length[rank]
+        H = int(label.numel())
+        slot = sizes.fill_(-1)                                                # the sizes are spent: reuse their memory
+        slot[label] = torch.arange(H, dtype=torch.int32, device=dev)
+        nv = 3 if vd is None else 6
+        sums = torch.zeros((max(H, 1), nv), dtype=torch.int64, device=dev)
+        labels = torch.empty(count, dtype=torch.int32, device=dev) if want_labels else None
+        tick("catalog")
+        _lib.check(l.nbe_fof_catalog(_ptr(X), _ptr(parent), _ptr(slot), _ptr(vd) if vd is not None else None,
+                                     1 if vd is not None and vd.dtype == torch.float16 else 0, exps, count,
+                                     int(bool(wave_reduce)), blocks, _ptr(sums), _ptr(labels) if want_labels else None, s))
+        tick("finish")
+        Xl = X[:, label].t().to(torch.int64).cpu().numpy()
+        out = (label.cpu().numpy(), length.cpu().numpy(), Xl, sums[:H].cpu().numpy(),
+               None if exps is None else np.array(list(exps), np.int64), ngroups, labels)
+        tick(None)
+    return out
+
+
+def fof_halos(displacement, boxsize=1000.0, linking_length=0.2, nmin=20, absolute=False, velocity=None,
+              return_labels=False, _max_blocks=None):
+    """Friends-of-friends halos of the displaced lattice (reference scripts/halos.py:359-450: the positions, nbodykit's
+    FOF(linking_length, nmin, absolute, periodic=True) and fof_catalog).  The module docstring has the definition.
+
+    displacement: (3, n, n, n) float32 / float16, 2 <= n <= 1024, NumPy array or CUDA tensor (process_box's output).
+    boxsize: L (scalar, or a 3-tuple of equal values).  linking_length: in units of the mean particle spacing L / n, or
+    of the box with absolute=True; positive, below about L / 3 (the cell grid needs 3 cells per axis).  nmin >= 1.
+    velocity: (3, n, n, n) float32 / float16 of the same kind and device.  `_max_blocks` caps the grid of every launch
+    (tests): the results do not depend on it.
+
+    Returns a dict: CMPosition (H, 3) float64, Length (H,) int64, label (H,) int64, with a velocity CMVelocity (H, 3)
+    float64, with return_labels labels (n, n, n) int32 (the halo's row in the catalogue, or -1) -- NumPy arrays for a NumPy
+    input, tensors on the input's device for a tensor --, ngroups (int, the groups of any size) and linking_length (float,
+    the absolute length used).
+
+    Raises ValueError, before any device work, for bad shapes or kinds, nmin < 1, a non-positive or too large linking
+    length, n > 1024 and a mismatched velocity; ValueError for a non-finite displacement or velocity value or
+    |psi_c / L| >= 2^20 (no partial catalogue is returned); NBEError when the device's free memory cannot take
+    72 bytes per particle."""
+    x, n, L, nmin, ell, R2, ncell, v, blocks = _validate(displacement, boxsize, linking_length, nmin, absolute, velocity,
+                                                         _max_blocks)
+    dev = _device_of(x)
+    _check_memory(dev, n ** 3)
+    dtypes = (torch.float32, torch.float16)
+    xd = _to_device(x, dev, dtypes)
+    vd = None if v is None else _to_device(v, dev, dtypes)
+    label, length, Xl, sums, exps, ngroups, labels = _stages(xd, vd, n, L, nmin, R2, ncell, blocks, bool(return_labels))
+    lf = length.astype(np.float64)[:, None]
+    cm = np.mod(Xl + sums[:, :3].astype(np.float64) / lf, float(_U)) / float(_U) * L
+    kind = (lambda a: torch.from_numpy(a).to(dev)) if _is_torch(x) else (lambda a: a)
+    out = {"CMPosition": kind(cm), "Length": kind(length.astype(np.int64)), "label": kind(label.astype(np.int64))}
+    if v is not None:
+        out["CMVelocity"] = kind(np.ldexp(sums[:, 3:].astype(np.float64), (exps - 24)[None, :].astype(np.int32)) / lf)
+    out["ngroups"] = ngroups
+    out["linking_length"] = ell
+    if return_labels:
+        out["labels"] = _back(x, labels.reshape(n, n, n))
+    return out
+
+
+def particle_mass(Om, boxsize, n):
+    """Mass of one particle of an n^3 load in M_sun / h: Om rho_crit L^3 / n^3 with rho_crit = 2.77536627e11 h^2 M_sun /
+    Mpc^3 (reference scripts/halos.py:345-349)."""
+    return float(Om) * RHO_CRIT * float(boxsize) ** 3 / float(n) ** 3
+
+
+def halo_mass_function(npart, boxsize, particle_mass, log_edges, fof_correction=False):
+    """Empirical dn / dlog10 M of a halo catalogue in Pylians' convention (reference scripts/halos.py:317-342), on the
+    host in float64.  npart: particles per halo (fof_halos's Length); masses are particle_mass N, or
+    particle_mass N (1 - N^-0.6) with fof_correction (Warren et al. 2006); they are histogrammed over 10**log_edges and
+    the counts / (dM L^3) are multiplied by the geometric bin centres and ln 10.  NaN in every bin when there is no halo."""
+    if _is_torch(npart):
+        npart = npart.cpu().numpy()
+    n_h = np.asarray(npart, dtype=np.float64).ravel()
+    n_h = n_h[n_h > 0.0]
+    log_edges = np.asarray(log_edges, dtype=np.float64)
+    centres = 10.0 ** (0.5 * (log_edges[1:] + log_edges[:-1]))
+    if n_h.size == 0:
+        return np.full_like(centres, np.nan)
+    masses = float(particle_mass) * (n_h * (1.0 - n_h ** (-0.6)) if fof_correction else n_h)
+    edges = 10.0 ** log_edges
+    counts, _ = np.histogram(masses, bins=edges)
+    dndm = counts.astype(np.float64) / ((edges[1:] - edges[:-1]) * float(boxsize) ** 3)
+    return dndm * centres * np.log(10.0)
+
+
+def density_slab(delta, boxsize, axis, center, width):
+    """Mean of a cubic density field over a slab normal to `axis` (reference scripts/halos.py:468-501,
+    project_density_slab): the planes whose cell centres (j + 1/2) L / n lie within width / 2 of `center` in the periodic
+    distance, or the nearest plane if none does.  delta: (n, n, n) NumPy array or torch tensor, read where it is.  axis: 0,
+    1, 2 or 'x', 'y', 'z'.  Returns (map (n, n) float32 of the input's kind, number of planes)."""
+    if not (_is_torch(delta) or isinstance(delta, np.ndarray)) or delta.ndim != 3 or len(set(delta.shape)) != 1:
+        raise ValueError("density_slab needs a cubic (n, n, n) field, got %s"
+                         % (tuple(delta.shape) if hasattr(delta, "shape") else type(delta).__name__,))
+    axis = {"x": 0, "y": 1, "z": 2}.get(axis, axis)
+    if isinstance(axis, (bool, np.bool_)) or axis not in (0, 1, 2):
+        raise ValueError("density_slab: axis must be 0, 1, 2 or 'x', 'y', 'z', got %r" % (axis,))
+    L = _real(boxsize, "boxsize", positive=True)
+    n = int(delta.shape[0])
+    dist = np.abs((np.arange(n, dtype=np.float64) + 0.5) * (L / n) - _real(center, "center"))
+    dist = np.minimum(dist, L - dist)
+    planes = np.nonzero(dist <= 0.5 * _real(width, "width"))[0]
+    if planes.size == 0:
+        planes = np.array([int(np.argmin(dist))])
+    if _is_torch(delta):
+        idx = torch.from_numpy(planes).to(delta.device)
+        return delta.index_select(axis, idx).to(torch.float32).mean(dim=axis), int(planes.size)
+    return np.take(delta, planes, axis=axis).astype(np.float32).mean(axis=axis).astype(np.float32), int(planes.size)
+
+
+# ---- drivers -----------------------------------------------------------------------------------------------------------
+
+CATALOG_FILE = "fof_catalog.npz"
+
+
+def catalog_arrays(cat, n, boxsize, Om, linking_length, absolute, nmin):
+    """The arrays of the reference's fof_catalog.npz (scripts/halos.py:871-881), same keys and dtypes, from fof_halos's
+    dict.  LinkingLength and AbsoluteLinking are the command line's values, as there."""
+    to_np = lambda a: a.cpu().numpy() if _is_torch(a) else np.asarray(a)
+    length = to_np(cat["Length"])
+    return dict(CMPosition=to_np(cat["CMPosition"]).astype(np.float32).reshape(-1, 3),
+                Npart=length.astype(np.int32),
+                Mass=length.astype(np.float64) * particle_mass(Om, boxsize, n),
+                BoxSize=np.array([boxsize] * 3, dtype=np.float64),
+                NpartPerDim=np.int32(n),
+                LinkingLength=np.float64(linking_length),
+                AbsoluteLinking=np.bool_(absolute),
+                Nmin=np.int32(nmin))
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="Friends-of-friends halo catalogue of a saved displacement field, on the GPU.")
+    ap.add_argument("--displacement_file", required=True, help="(3, N, N, N) or (N, N, N, 3) array (.npy)")
+    ap.add_argument("--output_dir", required=True)
+    ap.add_argument("--boxsize", type=float, default=1000.0, help="box size in Mpc/h (default: 1000.0)")
+    ap.add_argument("--omega_m", "--omega-m", type=float, default=0.3175, dest="omega_m",
+                    help="Omega_m of the particle mass (default: 0.3175)")
+    ap.add_argument("--linking-length", type=float, default=0.2, dest="linking_length",
+                    help="linking length in units of the mean particle spacing (unless --absolute-linking)")
+    ap.add_argument("--absolute-linking", action=argparse.BooleanOptionalAction, default=False, dest="absolute_linking",
+                    help="treat --linking-length as an absolute length in Mpc/h")
+    ap.add_argument("--nmin", type=int, default=20, help="smallest particle count of a halo")
+    ap.add_argument("--catalog-file", default=CATALOG_FILE, dest="catalog_file",
+                    help="name of the catalogue inside --output_dir (default: %s)" % CATALOG_FILE)
+    return ap
+
+
+def load_displacement(path):
+    """A (3, N, N, N) float32 / float16 array from a (3, N, N, N) or (N, N, N, 3) file (scripts/halos.py:372-379)."""
+    disp = np.load(path, mmap_mode="r")
+    if disp.ndim != 4:
+        sys.exit("Displacement field must be 4D, got shape=%s." % (tuple(disp.shape),))
+    if disp.shape[0] == 3:
+        arr = np.asarray(disp)
+    elif disp.shape[-1] == 3:
+        arr = np.moveaxis(np.asarray(disp), -1, 0)
+    else:
+        sys.exit("Displacement shape must be (3,N,N,N) or (N,N,N,3), got %s." % (tuple(disp.shape),))
+    return np.ascontiguousarray(arr, dtype=arr.dtype if arr.dtype in (np.float32, np.float16) else np.float32)
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    disp = load_displacement(a.displacement_file)
+    try:
+        cat = fof_halos(disp, boxsize=a.boxsize, linking_length=a.linking_length, nmin=a.nmin, absolute=a.absolute_linking)
+    except ValueError as e:
+        sys.exit(str(e))
+    os.makedirs(a.output_dir, exist_ok=True)
+    path = os.path.join(a.output_dir, a.catalog_file)
+    np.savez_compressed(path, **catalog_arrays(cat, disp.shape[1], a.boxsize, a.omega_m, a.linking_length,
+                                               a.absolute_linking, a.nmin))
+    print("%d halos of %d groups (linking length %g) -> %s" % (len(cat["Length"]), cat["ngroups"], cat["linking_length"],
+                                                               path))
+
+
+if __name__ == "__main__":
+    main()

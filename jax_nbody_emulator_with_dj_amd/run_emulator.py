@@ -35,6 +35,12 @@ AXIS) and `--pk_wedges NMU` writes <output_dir>/emu_pk_rsd_wedges.npz (k, mu, pk
 density.power_spectrum_wedges in NMU bins of |mu|, 1 .. 64).  Painting reads the float32 displacement on the device; the saved emu_dis.npy is
 rounded to --output-precision afterwards.
 
+Halos (the fork's scripts/halos.py): `--fof` writes <output_dir>/fof_catalog.npz, the friends-of-friends catalogue of the
+emulated displacement (halos.fof_halos on the device tensor, no host copy of the field; the reference's keys CMPosition,
+Npart, Mass, BoxSize, NpartPerDim, LinkingLength, AbsoluteLinking, Nmin).  `--fof_linking_length B` (default 0.2, in units
+of the mean particle spacing) and `--fof_nmin N` (default 20) set the finder; the box size is `--boxsize` and Omega_m the
+cosmology file's.  It needs a cubic box and works with or without --density_res.
+
 What differs from the reference: the engine, its weights and its ~100 GB workspace stay resident on the
 GPU for the whole batch, and disk I/O overlaps compute -- the next displacement file is read and the
 previous results are written by a background thread while the GPU works on the current box.
@@ -195,6 +201,13 @@ def build_parser():
     ap.add_argument('--pk_wedges', type=int, metavar='NMU', default=argparse.SUPPRESS,
                     help='With --rsd: also write the power spectrum of the redshift-space density in NMU wedges of |mu| '
                          'about AXIS to <output_dir>/emu_pk_rsd_wedges.npz (k, mu, pk, nmodes, mu_edges)')
+    ap.add_argument('--fof', action='store_true', default=argparse.SUPPRESS,
+                    help='Also write the friends-of-friends halo catalogue of the emulated displacement to '
+                         '<output_dir>/fof_catalog.npz (box size from --boxsize, Omega_m from the cosmology file)')
+    ap.add_argument('--fof_linking_length', type=float, default=argparse.SUPPRESS,
+                    help='With --fof: linking length in units of the mean particle spacing (default: 0.2)')
+    ap.add_argument('--fof_nmin', type=int, default=argparse.SUPPRESS,
+                    help='With --fof: smallest particle count of a halo (default: 20)')
     return ap
 
 
@@ -297,6 +310,32 @@ def velocity_fields(disp, vel, dens, paint_vel, rsd, z, Om, multipoles=False, we
     return out
 
 
+def fof_options(args):
+    """The halo-finder settings of a parsed command line, or None without --fof (read apart from density_options, whose
+    dict they leave as it was)."""
+    if not getattr(args, 'fof', False):
+        for name in ('fof_linking_length', 'fof_nmin'):
+            if getattr(args, name, None) is not None:
+                _die(f'--{name} needs --fof')
+        return None
+    boxsize = float(getattr(args, 'boxsize', 1000.0))
+    if not boxsize > 0:
+        _die(f'--boxsize must be positive, got {boxsize}')
+    b, nmin = float(getattr(args, 'fof_linking_length', 0.2)), int(getattr(args, 'fof_nmin', 20))
+    if not b > 0:
+        _die(f'--fof_linking_length must be positive, got {b}')
+    if nmin < 1:
+        _die(f'--fof_nmin must be >= 1, got {nmin}')
+    return dict(boxsize=boxsize, linking_length=b, nmin=nmin)
+
+
+def fof_catalog(disp, fof, Om):
+    """The arrays of fof_catalog.npz for the device displacement of one box."""
+    from .halos import catalog_arrays, fof_halos
+    cat = fof_halos(disp, boxsize=fof['boxsize'], linking_length=fof['linking_length'], nmin=fof['nmin'])
+    return catalog_arrays(cat, int(disp.shape[1]), fof['boxsize'], Om, fof['linking_length'], False, fof['nmin'])
+
+
 def density_summaries(delta, dens, bispec, onepoint):
     """The arrays of emu_bispectrum.npz and emu_onepoint.npz for the device field `delta` (None where not asked for)."""
     from .density import bispectrum, field_pdf, field_statistics
@@ -348,6 +387,7 @@ def run(args):
     bispec, onepoint = summary_options(args)
     paint_vel, rsd = velocity_options(args)
     multipoles, wedges = anisotropy_options(args)
+    fof = fof_options(args)
     if bispec:
         for k1, k2 in BISPECTRUM_CONFIGS:                    # density.bispectrum's closure condition, before any work
             if 2.0 * (k1 + k2) * dens['boxsize'] / (2.0 * np.pi) + 1.5 >= dens['res']:
@@ -359,6 +399,8 @@ def run(args):
               + (", bispectrum" if bispec else "") + (", one-point statistics" if onepoint else "")
               + (", velocity mesh" if paint_vel else "") + (f", redshift space along axis {rsd}" if rsd is not None else "")
               + (", multipoles" if multipoles else "") + (f", {wedges} wedges" if wedges is not None else ""))
+    if fof is not None:
+        print(f"  Halos: FoF b = {fof['linking_length']}, nmin {fof['nmin']}, boxsize {fof['boxsize']}")
     print()
 
     shape = None
@@ -366,13 +408,21 @@ def run(args):
         shape = displacement_shape(f, shape)
     box = tuple(shape[1:])
     print(f'  Box size: {box}')
+    if fof is not None:
+        from .halos import linking_geometry
+        if len(set(box)) != 1 or not 2 <= box[0] <= 1024:
+            _die(f'--fof needs a cubic box of 2 .. 1024 particles per axis, got {box}')
+        try:
+            linking_geometry(box[0], fof['boxsize'], fof['linking_length'], False)
+        except ValueError as e:
+            _die(f'--fof: {e}')
     cosmologies = [read_cosmology(f) for f in args.cosmo_param_files]
 
     params = load_params(args.params)
     mid = int(params['params']['conv_l01']['conv_0']['weight'].shape[0])
     # density mode: float32 fields on the device (painted from), rounded to --output-precision for the files
     config = SubboxConfig(size=box, ndiv=args.ndiv, dtype=args.precision,
-                          output_dtype=args.output_precision if dens is None else np.float32)
+                          output_dtype=args.output_precision if dens is None and fof is None else np.float32)
     emu = create_emulator(premodulate=not args.style, compute_vel=args.vel, load_params=False,
                           processor_config=config, mid_chan=mid)
     if args.style:
@@ -384,7 +434,9 @@ def run(args):
             np.save(out_dir / 'emu_vel.npy', result[1])
         else:
             np.save(out_dir / 'emu_dis.npy', result)
-        if extra is not None:
+        if extra is not None and 'fof' in extra:
+            np.savez_compressed(out_dir / 'fof_catalog.npz', **extra['fof'])
+        if extra is not None and 'delta' in extra:
             np.save(out_dir / 'emu_delta.npy', extra['delta'])
             if 'pk' in extra:
                 k, pk, nmodes = extra['pk']
@@ -416,9 +468,14 @@ def run(args):
         box_t = torch.from_numpy(np.ascontiguousarray(dis_in)).to('cuda')
         result = emu.process_box(box_t, z=z, Om=Om, show_progress=not args.quiet)
         disp = result[0] if args.vel else result
+        extra = {} if fof is None else {'fof': fof_catalog(disp, fof, Om)}
+        out_dt = np.dtype(args.output_precision)
+        if dens is None:
+            host = tuple(t.cpu().numpy().astype(out_dt, copy=False) for t in (result if args.vel else (result,)))
+            return (host if args.vel else host[0]), extra
         delta = paint_density(disp, boxsize=dens['boxsize'], res=dens['res'], worder=dens['worder'],
                               deconvolve=dens['deconvolve'])
-        extra = {'delta': delta.cpu().numpy()}
+        extra['delta'] = delta.cpu().numpy()
         if dens['pk']:
             extra['pk'] = power_spectrum(delta, boxsize=dens['boxsize'])
         if mink:
@@ -427,7 +484,6 @@ def run(args):
             extra['bk'], extra['onepoint'] = density_summaries(delta, dens, bispec, onepoint)
         if paint_vel or rsd is not None:
             extra.update(velocity_fields(disp, result[1], dens, paint_vel, rsd, z, Om, multipoles, wedges))
-        out_dt = np.dtype(args.output_precision)
         host = tuple(t.cpu().numpy().astype(out_dt, copy=False) for t in (result if args.vel else (result,)))
         return (host if args.vel else host[0]), extra
 
@@ -445,7 +501,7 @@ def run(args):
                 emu.params = emu.processor.params = tree
             t0 = time.time()
             extra = None
-            if dens is None:
+            if dens is None and fof is None:
                 result = emu.process_box(dis_in, z=z, Om=Om, show_progress=not args.quiet)
             else:
                 result, extra = with_density(dis_in, z, Om)
