@@ -56,7 +56,7 @@
 #define NBE_WINO_LOU (NBE_XF_F32 ? 0 : 1)
 #endif
 constexpr int NBE_MAX_WSTAGES = 32;                // 4 * Cin / 16: Cin <= 128
-constexpr int NBE_MAX_WSKIP = 16;                  // fused skip: 2 planes x Cin_block / 16 raw stages after the transformed ones
+constexpr int NBE_MAX_WSKIP = 16;                  // fused skip: 2 planes x Cin_block / 16 source entries behind the transformed stages'
 constexpr float WINO_WSCALE = 16384.0f;            // 2^14
 constexpr float WINO_WSCALE_F16 = 256.0f;          // the float16 form: no lo part to keep out of the subnormals, 2^8 for the small weights
 
@@ -70,16 +70,27 @@ struct WinoKArgs {
     const float* bias; const float* gout; const float* beta;
     const float* r; const float* dr; long res_pstride;          // F16 with F_RES: the residual (geometry of the output)
     float inv_scale;
-    int nskip;                 // SKIP: 16-channel chunks of the block input (two raw stages each, plane z0 and plane z0 + 1)
+    int nskip;                 // SKIP: 16-channel chunks of the block input (two entries of st[] each, plane z0 and plane z0 + 1)
     long dws_delta;            // SKIP: bytes from the scaled W_s to the scaled dW_s~ of a chunk
     WinoSrc st[NBE_MAX_WSTAGES + NBE_MAX_WSKIP];
 };
 
-// SKIP: the block's 1x1x1 skip runs inside this, its last, convolution as in conv_h3g_kernel: after the transformed stages, two
-// RAW stages per 16-channel chunk of the block input (its plane under z0 into set A, the next one into set B), patches by
-// global -> LDS DMA (nothing to transform), weights [W_s | dW_s~] scaled by 2^14 like the layer's own:
+// SKIP: the block's 1x1x1 skip runs inside this, its last, convolution: after the transformed stages, one SKIP PHASE over
+// the 16-channel chunks of the block input (per chunk its plane under z0 into set A, the next one into set B), weights
+// [W_s | dW_s~] scaled by 2^14 like the layer's own:
 //     y += W_s.x      dy += W_s.dx~ + dW_s~.x          (dW_s~ = dW_s - W_s (.) a - beta_1 W_s, see conv_h3g_kernel)
-// on the centre tap, the K halves selecting the part: [wh | wh 2^-11] . [xh | xl] and [wl | 0] . [xh | xl].
+// on the voxel itself, the K halves selecting the part: [wh | wh 2^-11] . [xh | xl] and [wl | 0] . [xh | xl].
+// The phase has no barrier and stages nothing but its weights in LDS:
+// * the weights of ALL chunks (8 KB each, at most 64 KB) arrive by global -> LDS DMA in one burst under the last
+//   transformed stage, in the buffer pair that stage does not read; its barrier is the one barrier before the phase;
+// * a B operand is 16 bytes of one voxel row, contiguous over 16 lanes: each lane loads its own from global memory (no
+//   patch, no halo -- the skip reads the 8 x 32 centre only), one chunk (both planes) in use and one in flight, the first
+//   one requested under the last transformed stage;
+// * the A operands of a chunk are read from LDS and scaled once and serve both planes.
+// Per accumulator set the products and their order are those of the two-stages-per-chunk form this replaces (six products on
+// the centre tap of a 10 x 34 patch fetched by DMA, a barrier per plane): the sums are the same sums, bit for bit.
+// (The float16 form, F16, keeps that two-stages-per-chunk form: dma_raw / raw_stage below.  Its skip phase was built and gave
+// wrong results on two-chunk skips -- tests/test_gpu_blocks.py, conv_l01 at mid 64 -- for a reason not found; NOVEL moved.)
 //
 // NOVEL: the displacement-only layer (style_layers.py:86-99: y = conv(x, w) + b, no tangent) on the SAME instruction stream.
 // Without a tangent the second accumulator set and the second patch tensor are free, so they carry a second block of
@@ -143,7 +154,7 @@ __global__ __launch_bounds__(512, 2) void conv_h3w_kernel(WinoKArgs a) {
     struct Nxt { const char *xa, *xb, *w0; long dxd, psb; float sb; } nx;
     auto set_next = [&](int s) {
         const WinoSrc e = a.st[s];
-        nx.xa = e.xa + to; nx.xb = e.xb + to; nx.dxd = e.dxd; nx.psb = e.psb; nx.w0 = e.w + (SKIP && s >= nst ? wcs : wcm); nx.sb = e.sb;
+        nx.xa = e.xa + to; nx.xb = e.xb + to; nx.dxd = e.dxd; nx.psb = e.psb; nx.w0 = e.w + (SKIP && F16 && s >= nst ? wcs : wcm); nx.sb = e.sb;
     };
     unsigned lane16 = (unsigned)lane << 4;
     asm volatile("" : "+v"(lane16));
@@ -154,7 +165,7 @@ __global__ __launch_bounds__(512, 2) void conv_h3w_kernel(WinoKArgs a) {
         else asm volatile("v_lshlrev_b32 %0, 4, %0" : "+v"(l16));   // recomputed at every use: held in a register it is spilled
         if (n < G::NWI) dma16s(nx.w0 + (long)n * 1024, l16, lds + buf * WGU + n * 64);
     };
-    // ---- a raw stage (SKIP): 8 wave-instructions of weights (W_s, dW_s~ of the chunk: one per wave) and 24 + 24 of the x and
+    // ---- a raw stage (SKIP, F16 only: the float16 form keeps the two-stages-per-chunk skip, see the header): 8 wave-instructions of weights (W_s, dW_s~ of the chunk: one per wave) and 24 + 24 of the x and
     // dx~ patches of ONE plane (three + three per wave), straight into the buffers of the stage
     auto dma_raw = [&](int buf) {
         unsigned l16 = (unsigned)lane;
@@ -171,6 +182,38 @@ __global__ __launch_bounds__(512, 2) void conv_h3w_kernel(WinoKArgs a) {
                        lds + XBASE + buf * HQ_XB + tensor * HQ_XT + pl * HQ_PP + k * 64);
         }
     };
+    // ---- the skip phase (SKIP, not F16).  Weights: [W_s | dW_s~] of ALL chunks, 8 KB each, in one burst of nskip wave-instructions
+    // per wave (wave w: kilobyte w & 3 of W_s or, from w = 4, of dW_s~), issued under the last transformed stage into the
+    // buffers that stage does not read: chunks 0..3 into weight buffer 0, chunks 4..7 into patch buffer 0.
+    constexpr int SKU = 2 * TAPU;                                // units of one chunk's [W_s | dW_s~]
+    static_assert(4 * SKU <= WGU && (NBE_MAX_WSKIP / 2 - 4) * SKU <= HQ_XB, "the skip's weights fit the idle buffer pair");
+    auto sk_wbase = [&](int sc) { return sc < 4 ? sc * SKU : XBASE + (sc - 4) * SKU; };
+    auto sk_weights = [&] {
+        unsigned l16 = (unsigned)lane;
+        asm volatile("v_lshlrev_b32 %0, 4, %0" : "+v"(l16));
+        const char* w = a.st[nst].w + wcs + (wave < 4 ? 0 : a.dws_delta) + (long)(wave & 3) * 1024;
+        for (int sc = 0; sc < a.nskip; ++sc) dma16s(w + (long)sc * (TAPU * 16), l16, lds + sk_wbase(sc) + wave * 64);
+    };
+    // B operands: straight from global memory into registers, 16 bytes per lane and MFMA tile -- lane (c, q) of tile nt reads
+    // unit plane 2 kh + ks at row `wave`, column 16 nt + c of the 8 x 32 centre (row + 1, column + 1 of the patch whose corner
+    // the sources point to: a subset of what a patch of the main input reads).  No LDS, no halo.  One ring slot holds a
+    // chunk: both planes (under z0 -> set A, the next -> set B) of x and dx~.
+    struct SkB { half8 x[2][NT], d[2][NT]; };
+    const bool sk_dx = NOVEL || !(a.flags & F_SKIP_NODX);        // (conv_l00: the input field has no tangent)
+    auto sk_load = [&](SkB& b, int sc) {
+#pragma unroll
+        for (int ab = 0; ab < 2; ++ab) {
+            const WinoSrc& e = a.st[nst + 2 * sc + ab];
+            const char* p = e.xa + to + ((long)(2 * kh + ks) * e.psb + (long)(((wave + 1) * a.W + c + 1) * 16));
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) b.x[ab][nt] = *(const half8*)(p + 256 * nt);
+            // (a skip input without a tangent, F_SKIP_NODX, has dxd = 0: loaded all the same, so that the number of loads in
+            // flight is a constant of the code -- and not used)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) b.d[ab][nt] = *(const half8*)(p + e.dxd + 256 * nt);
+        }
+    };
+    SkB skP, skQ;                                                // the ring: the chunk in use and the one in flight
     // ---- the transformed patch of the next stage: 24 wave-items (tensor, channel half, 64 units of the 340) of a hi and a
     // lo plane each, three per wave; an item is four 16-byte loads per lane (a hi, a lo, b hi, b lo), 8 channels of
     // V = a + sb * b in float32, and two 16-byte LDS stores.
@@ -434,12 +477,12 @@ __global__ __launch_bounds__(512, 2) void conv_h3w_kernel(WinoKArgs a) {
     // (pxc: a stage follows -- a compile-time constant, so that the fetch of the next stage costs no branches; only the
     // last stage of a workgroup runs the other instantiation)
     auto stage = [&](f32x4 (&Y)[NTILE], f32x4 (&DY)[NTILE], int s, auto nxt) {
-        constexpr int NXT = decltype(nxt)::value;                // what follows: 0 nothing, 1 a transformed stage, 2 a raw stage (SKIP)
+        constexpr int NXT = decltype(nxt)::value;                // what follows: 0 nothing, 1 a transformed stage, 2 the skip phase (SKIP)
         constexpr bool px = NXT == 1;
         // the first operands of stage s+1 are requested under the last products of stage s -- except across the phase
         // boundary, where they would only be carried through the butterfly (registers): it requests them itself
         const bool pre = px && s + 1 != 2 * a.nchunk;
-        if (NXT) set_next(s + 1);
+        if (NXT == 1 || (NXT == 2 && F16)) set_next(s + 1);
         // (the buffer parity is a compile-time constant of each instantiation: hidden from the compiler, which would
         // otherwise precompute one address register per LDS read of the stage -- dozens, spilled)
         int par = s & 1;
@@ -454,7 +497,9 @@ __global__ __launch_bounds__(512, 2) void conv_h3w_kernel(WinoKArgs a) {
         Xf xf;
         auto hk = [&](int k) { xf_step(g, xf, k); };
         auto none = [] {};
-        if (NXT == 2) dma_raw(nb);                               // (its first operands are requested by the raw stage itself)
+        // the skip phase follows: its weights and the B operands of its first chunk travel under this stage
+        if (NXT == 2 && F16) dma_raw(nb);                        // (its first operands are requested by the raw stage itself)
+        if (NXT == 2 && !F16) { sk_weights(); sk_load(skP, 0); NBE_SB; }
         if (px) st_load(0, g);
         pair(Y, DY, 0, nb, px, wb, xb + bP1,                                              // taps (0,1) + the weight DMA of stage s+1
              [&] { LB(xl, xb + 2 + bP32 + HQ_PP); }, [&] { LA(wh, wb + 2 * TAPU + aP); }, [&] { LB(xh, xb + 2 + bP32); },
@@ -513,7 +558,9 @@ __global__ __launch_bounds__(512, 2) void conv_h3w_kernel(WinoKArgs a) {
              px, hk, [&] { if (px) st_write(2, nb, xf); });
     };
 
-    // ---- a raw stage of the fused skip: six products on the centre tap of the block input's patch
+    // ---- a raw stage of the float16 form's fused skip: three products on the centre tap of the block input's patch.  A chunk
+    // is 32 channels, the K halves their two 16-channel halves:
+    // [W_s0 | W_s1] . [x0 | x1] -> Y,  the same . [dx~0 | dx~1] -> DY,  [dW_s~0 | dW_s~1] . [x0 | x1] -> DY
     auto raw_stage = [&](f32x4 (&Y)[NTILE], f32x4 (&DY)[NTILE], int s, bool px) {
         if (px) set_next(s + 1);
         int par = s & 1;
@@ -522,42 +569,67 @@ __global__ __launch_bounds__(512, 2) void conv_h3w_kernel(WinoKArgs a) {
         asm volatile("" : "+s"(nb));
         const int wb = par * WGU, xb = XBASE + par * HQ_XB;
         if (px) dma_raw(nb);
-        half8 a1[MT], a2[MT], d1[MT], d2[MT], bx[NT], bd[NT];
-        const half8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
-        const _Float16 m1 = ks ? kInv : (_Float16)1.0f;
-        const int aS = wb + (2 * kh) * CT + c;
+        half8 a1[MT], d1[MT], bx[NT], bd[NT];
         const int bS = xb + (2 * kh + ks) * HQ_PP + rowp * HP_RS + c + SH4;
-        if (F16) {
-            // a chunk of the float16 model's skip is 32 channels, the K halves their two 16-channel halves: three products,
-            // [W_s0 | W_s1] . [x0 | x1] -> Y,  the same . [dx~0 | dx~1] -> DY,  [dW_s~0 | dW_s~1] . [x0 | x1] -> DY
-            const int aF = wb + (2 * kh + ks) * CT + c;
-            LA(a1, aF); LB(bx, bS); LB(bd, bS + HQ_XT); LA(d1, aF + TAPU);
-            NBE_SB; MM8(Y, a1, bx, -1, 0, false); NBE_SB;
-            MM8(DY, a1, bd, -1, 0, false); NBE_SB;
-            MM8(DY, d1, bx, -1, 0, false); NBE_SB;
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            return;
+        const int aF = wb + (2 * kh + ks) * CT + c;
+        LA(a1, aF); LB(bx, bS); LB(bd, bS + HQ_XT); LA(d1, aF + TAPU);
+        NBE_SB; MM8(Y, a1, bx, -1, 0, false); NBE_SB;
+        MM8(DY, a1, bd, -1, 0, false); NBE_SB;
+        MM8(DY, d1, bx, -1, 0, false); NBE_SB;
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    };
+
+    // ---- a chunk of the skip phase: the products of both planes on the A operands of one chunk, read from LDS and scaled
+    // once.  Per accumulator set the order is fixed (see the kernel's header) -- W_s hi, W_s lo on x (-> Y), the same
+    // two on dx~ (-> DY), dW_s~ hi, lo on x (-> DY) -- so every sum is the same sum.  wh / wl carry the operands: on entry
+    // [W_s hi | W_s hi] and [W_s lo | 0] of chunk sc are loaded (or in flight), on exit those of chunk sc + 1.  The B operands
+    // of the next chunk are requested before the first product.  No barrier: nothing is written to LDS any more.
+    const _Float16 skm1 = ks ? kInv : (_Float16)1.0f;            // the K halves select the part: [wh | wh 2^-11] . [xh | xl]
+    const half8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto sk_hi = [&](int wb_) { LA(wh, wb_ + (2 * kh) * CT + c); };
+    auto sk_lo = [&](int wb_) {                                  // [w lo | 0]: the K half of the lo plane reads zeros
+        if (NBE_WINO_ZROW) LA(wl, ks ? ZROW + c : wb_ + (2 * kh + 1) * CT + c);
+        else LA(wl, wb_ + (2 * kh + 1) * CT + c);
+    };
+    auto sk_scale = [&] {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) wh[mt] = wh[mt] * skm1;
+    };
+    auto sk_zero = [&] {
+        if (NBE_WINO_ZROW) return;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) wl[mt] = ks ? zero8 : wl[mt];
+    };
+    auto sk_chunk = [&](const SkB& b, SkB& bn, int sc, int ld) {    // ld: the chunk to request (< 0: none)
+        const bool more = ld >= 0;
+        const int wb_ = sk_wbase(sc), wbn_ = sk_wbase(sc + 1);
+        if (more) sk_load(bn, ld);
+        sk_scale();
+        NBE_SB; MM8(YA, wh, b.x[0], -1, 0, false, true); NBE_SB;                          // [W_s hi | W_s hi 2^-11] . [x hi | x lo]
+        MM8(YB, wh, b.x[1], -1, 0, false); NBE_SB;
+        if (sk_dx) {                                                                      // NOVEL: W_s . x of the second row block
+            MM8(DA, wh, b.d[0], -1, 0, false); NBE_SB;
+            MM8(DB, wh, b.d[1], -1, 0, false); NBE_SB;
         }
-        LA(a1, aS); LB(bx, bS); LA(a2, aS + CT); LB(bd, bS + HQ_XT);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) a1[mt] = a1[mt] * m1;
-        NBE_SB; MM8(Y, a1, bx, -1, 0, false, true); NBE_SB;                               // [W_s hi | W_s hi 2^-11] . [x hi | x lo]
-        if (!NOVEL) LA(d1, aS + TAPU);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) a2[mt] = ks ? zero : a2[mt];
-        NBE_SB; MM8(Y, a2, bx, -1, 0, false, true); NBE_SB;                               // [W_s lo | 0] . [x hi | x lo]
-        if (!NOVEL) LA(d2, aS + TAPU + CT);
-        if (NOVEL || !(a.flags & F_SKIP_NODX)) {                                         // (conv_l00: the input field has no tangent)
-            NBE_SB; MM8(DY, a1, bd, -1, 0, false); NBE_SB;                                // NOVEL: W_s . x of the second row block
-            MM8(DY, a2, bd, -1, 0, false); NBE_SB;
+        if (!NOVEL) sk_hi(wb_ + TAPU); else if (more) sk_hi(wbn_);
+        sk_zero();
+        NBE_SB; MM8(YA, wl, b.x[0], -1, 0, false, !NBE_WINO_ZROW); NBE_SB;                // [W_s lo | 0] . [x hi | x lo]
+        MM8(YB, wl, b.x[1], -1, 0, false); NBE_SB;
+        if (sk_dx) {
+            MM8(DA, wl, b.d[0], -1, 0, false); NBE_SB;
+            MM8(DB, wl, b.d[1], -1, 0, false); NBE_SB;
         }
         if (!NOVEL) {
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) { d1[mt] = d1[mt] * m1; d2[mt] = ks ? zero : d2[mt]; }
-            NBE_SB; MM8(DY, d1, bx, -1, 0, false, true); NBE_SB;                          // dW_s~ . x
-            MM8(DY, d2, bx, -1, 0, false, true); NBE_SB;
+            sk_lo(wb_ + TAPU);
+            sk_scale();
+            NBE_SB; MM8(DA, wh, b.x[0], -1, 0, false, true); NBE_SB;                      // dW_s~ . x
+            MM8(DB, wh, b.x[1], -1, 0, false); NBE_SB;
+            if (more) sk_hi(wbn_);
+            sk_zero();
+            NBE_SB; MM8(DA, wl, b.x[0], -1, 0, false, !NBE_WINO_ZROW); NBE_SB;
+            MM8(DB, wl, b.x[1], -1, 0, false); NBE_SB;
         }
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (more) sk_lo(wbn_);
     };
 
     // ---- prologue: stage 0
@@ -609,11 +681,28 @@ __global__ __launch_bounds__(512, 2) void conv_h3w_kernel(WinoKArgs a) {
     if (npairs - 1 == a.nchunk) butterfly();
     stage(YA, DA, 2 * npairs - 2, std::integral_constant<int, 1>());
     stage(YB, DB, 2 * npairs - 1, std::integral_constant<int, SKIP ? 2 : 0>());
-    if (SKIP) {
+    if (SKIP && F16) {
         for (int sc = 0; sc < a.nskip; ++sc) {
             raw_stage(YA, DA, nst + 2 * sc, true);
             raw_stage(YB, DB, nst + 2 * sc + 1, sc + 1 < a.nskip);
         }
+    }
+    if (SKIP && !F16) {
+        // (the last stage's barrier stands before the phase: every wave's share of the weights has landed)
+        sk_hi(sk_wbase(0));
+        sk_lo(sk_wbase(0));
+        // The compiler counts the loads in flight (vmcnt) only where their number is a constant of the code: every chunk of
+        // the loop requests exactly one chunk, the last one of an even nskip its own once more (32 KB per workgroup that
+        // the L2 has just served, against a wait for everything in flight at every chunk).  The wait tells the compiler
+        // what the barrier's asm statement has done: nothing is in flight -- behind a DMA it takes for pending it would not
+        // count either.
+        __builtin_amdgcn_s_waitcnt(0x0F70);                      // vmcnt(0)
+        int sc = 0;
+        for (; sc + 1 < a.nskip; sc += 2) {
+            sk_chunk(skP, skQ, sc, sc + 1);
+            sk_chunk(skQ, skP, sc + 1, sc + 2 < a.nskip ? sc + 2 : sc + 1);
+        }
+        if (sc < a.nskip) sk_chunk(skP, skQ, sc, -1);
     }
 #undef NBE_SB
 #undef SNAKE
@@ -848,8 +937,9 @@ static int launch_h3w(const ConvKArgs& ka_in, const float* ww, const float* wws,
                 e.xa = x + off + PA[xi] * plane; e.xb = x + off + PB[xi] * plane; e.dxd = novel ? rows8 : dx - x;
                 e.w = (const char*)ww + (long)(chunk * 4 + xi) * G::WG * 16; e.psb = ps * 16; e.sb = SB[xi]; e.pad_ = 0;
             }
-    // raw stages of the fused skip: chunk sc of the block input, plane z0 (-> A) and plane z0 + 1 (-> B); ka.xs is already
-    // offset so that the centre tap of the patch of output tile (z, y0, x0) is the skip's voxel
+    // sources of the skip phase: chunk sc of the block input, plane z0 (-> A) and plane z0 + 1 (-> B); ka.xs is already
+    // offset so that the centre tap of the patch of output tile (z, y0, x0) is the skip's voxel (the kernel reads that
+    // voxel alone, through 64-bit addresses: no bound on the skip tensors' plane strides)
     for (int sc = 0; sc < ka.nskip; ++sc)
         for (int ab = 0; ab < 2; ++ab) {
             const bool second = sc >= ka.s_csplit;
