@@ -483,6 +483,33 @@ int nbe_spectrum_resize(const void* src, int64_t n_in, void* dst, int64_t n_out,
 int nbe_spectrum_inject(const void* src, int64_t n_in, void* dst, int64_t n_out, const void* k_table,
                         const void* pk_table, int ntable, double tail_slope, double tail_intercept, double boxsize,
                         uint64_t seed, void* stream);
+/* replaces the draw of run_lpt_emulator_pipeline(seed=...) (scripts/core.py:263-302: white noise coloured with a tabulated
+ * linear P(k)): dst = (n, n, n/2+1) receives the whole half spectrum of a Gaussian field, Hermitian by construction, one
+ * seed being one universe at every n.  Pairing as in nbe_spectrum_inject: on the planes i2 = 0 and
+ * (n even) i2 = n/2 the rows (i0, i1) and ((n - i0) % n, (n - i1) % n) form a pair, the one with the smaller i0 n + i1
+ * draws, the other takes the complex conjugate, and a row that is its own mirror is a self mode.  Philox4x32-10 with key
+ * (seed low word, seed high word) and counter ((uint32) m0, (uint32) m1, (uint32) m2, 1): the two's-complement signed wave
+ * numbers of the drawing row, each in (-n/2, n/2], so the counter does not depend on n and never equals one of
+ * nbe_spectrum_inject (last word 0).  U1 = (x0 + 1/2) 2^-32, U2 = (x1 + 1/2) 2^-32, g = sqrt(-2 ln U1) (cospi(2 U2) +
+ * i sinpi(2 U2)) in float64.  sigma = scale n^3 sqrt(P(|k|) / L^3), multiplied in that order, with P as in
+ * nbe_spectrum_inject; F(0) = +0, a self mode gets sigma Re g (imaginary word +0), every other mode sigma g / sqrt(2); each
+ * float32 word is rounded once.  Only products follow sigma, so the words at n and 2n differ by exactly 8.
+ * flags: NBE_IC_FIXED_AMPLITUDE: a non-self mode gets sigma (cospi(2 U2) + i sinpi(2 U2)), a self mode +sigma if
+ * cospi(2 U2) >= 0 and -sigma otherwise.  NBE_IC_INVERT_PHASE: F -> -F for every mode (words that are +0 stay +0).
+ * NBE_IC_WHITE_NOISE: sigma = n^(3/2), a real field of unit variance; the table pointers may be NULL and ntable, the tail,
+ * boxsize and scale are not read.  max_blocks <= 0: the default grid; a positive value caps the number of workgroups (the
+ * same bits: a test makes the row loop wrap on a small mesh with it). */
+#define NBE_IC_FIXED_AMPLITUDE 1
+#define NBE_IC_INVERT_PHASE 2
+#define NBE_IC_WHITE_NOISE 4
+int nbe_gaussian_spectrum(void* dst, int64_t n, const void* k_table, const void* pk_table, int ntable,
+                          double tail_slope, double tail_intercept, double boxsize, double scale, uint64_t seed, int flags,
+                          int max_blocks, void* stream);
+/* colours somebody else's white noise as scripts/core.py:263-302 colours its own: in place, spectrum (the half spectrum of
+ * a real field w of unit variance) becomes delta_k = w_k scale sqrt(n^3 P(|k|) / L^3), the multiplier in float64, each
+ * word of the product rounded once, delta_0 = +0.  P as in nbe_spectrum_inject; scale finite and > 0. */
+int nbe_spectrum_colour(void* spectrum, int64_t n, const void* k_table, const void* pk_table, int ntable,
+                        double tail_slope, double tail_intercept, double boxsize, double scale, void* stream);
 /* replaces Pylians' FT_filter(boxsize, sigma, n, "Gaussian") and field_smoothing (scripts/utils.py:590-591): in place,
  * spectrum *= exp(-|k|^2 sigma^2 / 2) = exp(-2 pi^2 |m|^2 sigma_over_L^2) */
 int nbe_gaussian_filter(void* spectrum, int64_t n, double sigma_over_L, void* stream);

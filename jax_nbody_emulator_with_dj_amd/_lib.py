@@ -114,6 +114,10 @@ SIGNATURES = {
     "nbe_spectrum_resize": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "nbe_spectrum_inject": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
                                       C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_void_p]),
+    "nbe_gaussian_spectrum": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                        C.c_double, C.c_double, C.c_uint64, C.c_int, C.c_int, C.c_void_p]),
+    "nbe_spectrum_colour": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                      C.c_double, C.c_double, C.c_void_p]),
     "nbe_gaussian_filter": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_void_p]),
     "nbe_block_average": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "nbe_trilinear_upsample": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

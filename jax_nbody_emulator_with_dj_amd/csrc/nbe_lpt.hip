@@ -2,7 +2,8 @@
 // into the first-order LPT displacement, and the divergence of a vector field on the same grid.  Replaces
 // resize_density_grid and its helpers (scripts/utils.py:186-234, :261-346, :349-425, :531-555, :590-591) and
 // dj.evaluate_lpt_psi_at_a(n_order=1) (scripts/core.py:396-397); the divergence has no counterpart there.  The transforms
-// are the caller's (rocFFT); these are the passes between them.  No context: no weights.
+// are the caller's (rocFFT); these are the passes between them.  The last section draws the linear field itself from a
+// seed and a tabulated P(k), or colours somebody else's white noise (scripts/core.py:263-302).  No context: no weights.
 //
 // Every kernel walks rows: a (64, 4) workgroup takes four rows (i0, i1) of the destination at a time, decodes the row
 // once (the only 64-bit division) and strides its 64 lanes along the contiguous axis, so that a wave-instruction reads
@@ -168,25 +169,30 @@ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
     }
 }
 
+// A tabulated P(k) in device memory and its fitted log-log tail: carried by every argument block that evaluates it
+struct PkTable {
+    const double* k; const double* pk; int n;
+    double tail_slope, tail_intercept;
+};
+
 struct InjectArgs {
     const float2* src; float2* dst;
     long long n_in, n_out;
-    const double* k_table; const double* pk_table; int ntable;
-    double tail_slope, tail_intercept;
+    PkTable table;
     double kf;                  // 2 pi / L
     double amp;                 // n_out^3 / sqrt(L^3): sigma = amp sqrt(P)
     double scale;               // (n_out / n_in)^3
     uint32_t key0, key1;
 };
 
-// P(k): np.interp inside the table, pk_table[0] below it, the fitted power law above it, clamped at 0
-__device__ inline double table_power(const InjectArgs& A, double k) {
-    const double* kt = A.k_table;
-    const double* pt = A.pk_table;
-    const int last = A.ntable - 1;
+// P(k): np.interp inside the table, pk[0] below it, the fitted power law above it, clamped at 0
+__device__ inline double table_power(const PkTable& T, double k) {
+    const double* kt = T.k;
+    const double* pt = T.pk;
+    const int last = T.n - 1;
     double p;
     if (k < kt[0]) p = pt[0];
-    else if (k > kt[last]) p = exp(A.tail_intercept + A.tail_slope * log(k));
+    else if (k > kt[last]) p = exp(T.tail_intercept + T.tail_slope * log(k));
     else if (k == kt[last]) p = pt[last];
     else {
         int lo = 0, hi = last;                              // kt[lo] <= k < kt[hi]
@@ -198,6 +204,15 @@ __device__ inline double table_power(const InjectArgs& A, double k) {
         p = slope * (k - kt[lo]) + pt[lo];
     }
     return p > 0.0 ? p : 0.0;
+}
+
+// the two uniforms of a counter: U = (x + 1/2) 2^-32 from the first two words of Philox4x32-10
+__device__ inline void philox_uniforms(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                       double* u1, double* u2) {
+    uint32_t x[4] = {c0, c1, c2, c3};
+    philox4x32_10(x, k0, k1);
+    *u1 = ((double)x[0] + 0.5) * 0x1p-32;
+    *u2 = ((double)x[1] + 0.5) * 0x1p-32;
 }
 
 __global__ __launch_bounds__(kLanes * kRows) void spectrum_inject_kernel(InjectArgs A) {
@@ -217,12 +232,11 @@ __global__ __launch_bounds__(kLanes * kRows) void spectrum_inject_kernel(InjectA
             }
             const bool paired = i2 == 0 || i2 == nyq;
             const bool second = paired && mirror < r, self = paired && mirror == r;
-            uint32_t x[4] = {(uint32_t)(second ? p0 : i0), (uint32_t)(second ? p1 : i1), (uint32_t)i2, 0u};
-            philox4x32_10(x, A.key0, A.key1);
-            const double u1 = ((double)x[0] + 0.5) * 0x1p-32, u2 = ((double)x[1] + 0.5) * 0x1p-32;
-            double s, c;
+            double u1, u2, s, c;
+            philox_uniforms((uint32_t)(second ? p0 : i0), (uint32_t)(second ? p1 : i1), (uint32_t)i2, 0u, A.key0, A.key1,
+                            &u1, &u2);
             sincospi(2.0 * u2, &s, &c);
-            const double sigma = A.amp * sqrt(table_power(A, A.kf * sqrt((double)q)));
+            const double sigma = A.amp * sqrt(table_power(A.table, A.kf * sqrt((double)q)));
             const double mag = sigma * sqrt(-2.0 * log(u1));
             if (self) {
                 out[i2] = make_float2((float)(mag * c), 0.0f);
@@ -230,6 +244,87 @@ __global__ __launch_bounds__(kLanes * kRows) void spectrum_inject_kernel(InjectA
                 const double g = mag * 0.7071067811865476;
                 out[i2] = make_float2((float)(g * c), (float)(second ? -(g * s) : g * s));
             }
+        }
+    }
+}
+
+// ---- the linear field from a seed ------------------------------------------------------------------------------------------
+
+constexpr int kFixedAmplitude = NBE_IC_FIXED_AMPLITUDE, kInvertPhase = NBE_IC_INVERT_PHASE, kWhiteNoise = NBE_IC_WHITE_NOISE;
+
+struct GaussianArgs {
+    float2* dst;
+    long long n;
+    PkTable table;              // unused for white noise
+    double kf;                  // 2 pi / L
+    double amp;                 // scale n^3, or n^(3/2) for white noise
+    double volume;              // L^3: sigma = amp sqrt(P / volume)
+    uint32_t key0, key1;
+    int flags;
+};
+
+// The whole half spectrum of a Gaussian field.  The pairing of spectrum_inject_kernel; the
+// counter is the drawing row's signed wave vector and a last word of 1, so that a mode draws the same numbers on every mesh
+// that holds it and never shares a counter with the injection.  Products only, so sigma for n and 2n, and with it every
+// word, differ by exactly 8.
+__global__ __launch_bounds__(kLanes * kRows) void gaussian_spectrum_kernel(GaussianArgs A) {
+    const long long n = A.n, h = n / 2 + 1;
+    const long long nyq = n % 2 == 0 ? n / 2 : -1;
+    const double sign = A.flags & kInvertPhase ? -1.0 : 1.0;
+    NBE_FOR_ROWS(r, n * n) {
+        const long long i0 = r / n, i1 = r - i0 * n;
+        const long long p0 = i0 ? n - i0 : 0, p1 = i1 ? n - i1 : 0, mirror = p0 * n + p1;
+        const long long m0 = freq(i0, n), m1 = freq(i1, n), q01 = m0 * m0 + m1 * m1;
+        const long long w0 = freq(p0, n), w1 = freq(p1, n);          // the mirror row's wave numbers
+        float2* out = A.dst + r * h;
+        for (long long i2 = threadIdx.x; i2 < h; i2 += kLanes) {
+            const long long q = q01 + i2 * i2;
+            if (q == 0) {
+                out[i2] = make_float2(0.0f, 0.0f);
+                continue;
+            }
+            const bool paired = i2 == 0 || i2 == nyq;
+            const bool second = paired && mirror < r, self = paired && mirror == r;
+            double u1, u2, s, c;
+            philox_uniforms((uint32_t)(int32_t)(second ? w0 : m0), (uint32_t)(int32_t)(second ? w1 : m1), (uint32_t)i2, 1u,
+                            A.key0, A.key1, &u1, &u2);
+            sincospi(2.0 * u2, &s, &c);
+            const double sigma = A.flags & kWhiteNoise ? A.amp
+                                                       : A.amp * sqrt(table_power(A.table, A.kf * sqrt((double)q)) / A.volume);
+            if (A.flags & kFixedAmplitude) {
+                if (self) out[i2] = make_float2((float)(sign * (c >= 0.0 ? sigma : -sigma)), 0.0f);
+                else out[i2] = make_float2((float)(sign * (sigma * c)), (float)(sign * (second ? -(sigma * s) : sigma * s)));
+                continue;
+            }
+            const double mag = sigma * sqrt(-2.0 * log(u1));
+            if (self) {
+                out[i2] = make_float2((float)(sign * (mag * c)), 0.0f);
+            } else {
+                const double g = mag * 0.7071067811865476;
+                out[i2] = make_float2((float)(sign * (g * c)), (float)(sign * (second ? -(g * s) : g * s)));
+            }
+        }
+    }
+}
+
+// in place: the spectrum of a white-noise field times amp sqrt(n^3 P(|k|) / L^3), 0 at m = 0
+__global__ __launch_bounds__(kLanes * kRows) void spectrum_colour_kernel(float2* __restrict__ f, long long n, PkTable T,
+                                                                         double kf, double amp, double cells,
+                                                                         double volume) {
+    const long long h = n / 2 + 1;
+    NBE_FOR_ROWS(r, n * n) {
+        const long long i0 = r / n, i1 = r - i0 * n;
+        const long long m0 = freq(i0, n), m1 = freq(i1, n), q01 = m0 * m0 + m1 * m1;
+        float2* row = f + r * h;
+        for (long long i2 = threadIdx.x; i2 < h; i2 += kLanes) {
+            const long long q = q01 + i2 * i2;
+            if (q == 0) {
+                row[i2] = make_float2(0.0f, 0.0f);
+                continue;
+            }
+            const double w = amp * sqrt(cells * table_power(T, kf * sqrt((double)q)) / volume);
+            const float2 v = row[i2];
+            row[i2] = make_float2((float)(v.x * w), (float)(v.y * w));
         }
     }
 }
@@ -361,14 +456,60 @@ int nbe_spectrum_inject(const void* src, int64_t n_in, void* dst, int64_t n_out,
     InjectArgs A;
     A.src = (const float2*)src; A.dst = (float2*)dst;
     A.n_in = n_in; A.n_out = n_out;
-    A.k_table = (const double*)k_table; A.pk_table = (const double*)pk_table; A.ntable = ntable;
-    A.tail_slope = tail_slope; A.tail_intercept = tail_intercept;
+    A.table = PkTable{(const double*)k_table, (const double*)pk_table, ntable, tail_slope, tail_intercept};
     A.kf = 2.0 * kPi / boxsize;
     A.amp = cube((double)n_out) / sqrt(cube(boxsize));
     A.scale = cube((double)n_out / (double)n_in);
     A.key0 = (uint32_t)seed; A.key1 = (uint32_t)(seed >> 32);
     hipLaunchKernelGGL(spectrum_inject_kernel, row_grid(n_out), kBlock, 0, (hipStream_t)stream, A);
     return launched("nbe_spectrum_inject");
+}
+
+int nbe_gaussian_spectrum(void* dst, int64_t n, const void* k_table, const void* pk_table, int ntable,
+                          double tail_slope, double tail_intercept, double boxsize, double scale, uint64_t seed, int flags,
+                          int max_blocks, void* stream) {
+    const bool white = flags & kWhiteNoise;
+    if (!dst || (!white && (!k_table || !pk_table))) return fail("nbe_gaussian_spectrum: NULL argument");
+    if (!size_ok(n)) return fail("nbe_gaussian_spectrum: n %lld not in %d .. %d", (long long)n, NBE_LPT_MIN_N, NBE_LPT_MAX_N);
+    if (flags & ~(kFixedAmplitude | kInvertPhase | kWhiteNoise)) return fail("nbe_gaussian_spectrum: unknown flags %d", flags);
+    if (!white) {
+        if (ntable < 2) return fail("nbe_gaussian_spectrum: a table of %d points (at least 2)", ntable);
+        if (!(boxsize > 0.0) || !std::isfinite(boxsize) || !(scale > 0.0) || !std::isfinite(scale) ||
+            !std::isfinite(tail_slope) || !std::isfinite(tail_intercept))
+            return fail("nbe_gaussian_spectrum: bad boxsize %g, scale %g or tail (%g, %g)", boxsize, scale, tail_slope,
+                        tail_intercept);
+    }
+    GaussianArgs A;
+    A.dst = (float2*)dst; A.n = n; A.flags = flags;
+    A.key0 = (uint32_t)seed; A.key1 = (uint32_t)(seed >> 32);
+    if (white) {
+        A.table = PkTable{nullptr, nullptr, 0, 0.0, 0.0};
+        A.kf = 0.0; A.volume = 1.0;
+        A.amp = sqrt(cube((double)n));
+    } else {
+        A.table = PkTable{(const double*)k_table, (const double*)pk_table, ntable, tail_slope, tail_intercept};
+        A.kf = 2.0 * kPi / boxsize; A.volume = cube(boxsize);
+        A.amp = scale * cube((double)n);
+    }
+    dim3 grid = row_grid(n);
+    if (max_blocks > 0 && grid.x > (unsigned)max_blocks) grid.x = (unsigned)max_blocks;
+    hipLaunchKernelGGL(gaussian_spectrum_kernel, grid, kBlock, 0, (hipStream_t)stream, A);
+    return launched("nbe_gaussian_spectrum");
+}
+
+int nbe_spectrum_colour(void* spectrum, int64_t n, const void* k_table, const void* pk_table, int ntable,
+                        double tail_slope, double tail_intercept, double boxsize, double scale, void* stream) {
+    if (!spectrum || !k_table || !pk_table) return fail("nbe_spectrum_colour: NULL argument");
+    if (!size_ok(n)) return fail("nbe_spectrum_colour: n %lld not in %d .. %d", (long long)n, NBE_LPT_MIN_N, NBE_LPT_MAX_N);
+    if (ntable < 2) return fail("nbe_spectrum_colour: a table of %d points (at least 2)", ntable);
+    if (!(boxsize > 0.0) || !std::isfinite(boxsize) || !(scale > 0.0) || !std::isfinite(scale) ||
+        !std::isfinite(tail_slope) || !std::isfinite(tail_intercept))
+        return fail("nbe_spectrum_colour: bad boxsize %g, scale %g or tail (%g, %g)", boxsize, scale, tail_slope,
+                    tail_intercept);
+    const PkTable T{(const double*)k_table, (const double*)pk_table, ntable, tail_slope, tail_intercept};
+    hipLaunchKernelGGL(spectrum_colour_kernel, row_grid(n), kBlock, 0, (hipStream_t)stream, (float2*)spectrum, (long long)n,
+                       T, 2.0 * kPi / boxsize, scale, cube((double)n), cube(boxsize));
+    return launched("nbe_spectrum_colour");
 }
 
 int nbe_gaussian_filter(void* spectrum, int64_t n, double sigma_over_L, void* stream) {

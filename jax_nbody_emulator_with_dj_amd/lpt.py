@@ -25,6 +25,13 @@ Conventions:
 - "mode_inject" keeps the modes inside the sphere |m| <= n_in/2 and draws the others from a tabulated P(k) with a
   counter-based generator: `inject_spectrum` has the definition.
 
+- `gaussian_field`, `white_noise`, `colour_noise` and `linear_ics` make the linear field itself from a seed and a tabulated
+  P(k), one seed being one universe at every resolution: `gaussian_spectrum` has the definition.
+
+    delta, psi = linear_ics(512, 1000.0, k, pk, seed=7, scale=D)          # seed -> delta, process_box's input
+    delta = gaussian_field(512, 1000.0, k, pk, seed=7)                    # the field alone: one draw pass, one irfftn
+    delta = colour_noise(white, 1000.0, k, pk)                            # somebody else's white noise, coloured
+
 Residency: NumPy in gives NumPy out; a CUDA torch tensor in gives a CUDA tensor on the same device, with no host copy,
 enqueued on torch's current stream of that device.  There is no CPU fallback: without a device the first device call
 raises NBEError.  Arguments are validated before any device work.
@@ -35,6 +42,7 @@ import numbers
 import numpy as np
 
 from . import _lib
+from . import density
 from .density import _back, _bk_batch, _check_array, _cubic, _device_of, _ptr, _real, _stream, _to_device
 
 try:
@@ -97,18 +105,31 @@ def zeldovich_displacement(delta, boxsize=1000.0, scale=1.0, _max_batch=None):
     dev = _device_of(d)
     with torch.cuda.device(dev):
         spec = _half_spectrum(_to_device(d, dev, (torch.float32,)))
-        psi_k = _empty_spectrum(n, dev, (3,))
-        _lib.check(_lib.lib().nbe_zeldovich_spectrum(_ptr(spec), n, L, scale, _ptr(psi_k), _stream(dev)))
+        psi_k = _psi_spectrum(spec, n, L, scale)
         del spec
-        if _bk_batch(dev, n, 3, _max_batch) >= 3:
-            psi = torch.fft.irfftn(psi_k, s=(n, n, n), dim=(1, 2, 3)).contiguous()
-        else:
-            psi = torch.empty((3, n, n, n), dtype=torch.float32, device=dev)
-            # A batch of one through the same call: torch gives a transform with a leading batch axis to one 3-D
-            # complex-to-real plan, and a bare 3-D tensor to a 2-D complex plan plus 1-D real ones, which rounds differently.
-            for c in range(3):
-                psi[c:c + 1] = torch.fft.irfftn(psi_k[c:c + 1], s=(n, n, n), dim=(1, 2, 3))
+        psi = _inverse_components(psi_k, n, _max_batch)
     return _back(d, psi)
+
+
+def _psi_spectrum(spec, n, L, scale):
+    """nbe_zeldovich_spectrum on a contiguous complex64 half spectrum on the device: (3, n, n, n // 2 + 1)."""
+    psi_k = _empty_spectrum(n, spec.device, (3,))
+    _lib.check(_lib.lib().nbe_zeldovich_spectrum(_ptr(spec), n, L, scale, _ptr(psi_k), _stream(spec.device)))
+    return psi_k
+
+
+def _inverse_components(psi_k, n, max_batch):
+    """The (3, n, n, n) float32 field of three half spectra: one batched irfftn, or one component at a time where
+    `_bk_batch` finds memory short (the same bits)."""
+    dev = psi_k.device
+    if _bk_batch(dev, n, 3, max_batch) >= 3:
+        return torch.fft.irfftn(psi_k, s=(n, n, n), dim=(1, 2, 3)).contiguous()
+    psi = torch.empty((3, n, n, n), dtype=torch.float32, device=dev)
+    # A batch of one through the same call: torch gives a transform with a leading batch axis to one 3-D
+    # complex-to-real plan, and a bare 3-D tensor to a 2-D complex plan plus 1-D real ones, which rounds differently.
+    for c in range(3):
+        psi[c:c + 1] = torch.fft.irfftn(psi_k[c:c + 1], s=(n, n, n), dim=(1, 2, 3))
+    return psi
 
 
 def divergence(field, boxsize=1000.0):
@@ -315,3 +336,199 @@ def resize_density(delta, target_res, boxsize=1000.0, upsample_method=_REQUIRED,
                 x = _smooth(x, n, (L / m if gaussian_sigma is None else gaussian_sigma) / L)
             out = _real_pass(l.nbe_block_average, x, n, m)
     return _back(d, out)
+
+
+# ---- the linear field from a seed ------------------------------------------------------------------------------------------
+
+FIXED_AMPLITUDE, INVERT_PHASE, WHITE_NOISE = 1, 2, 4      # include/nbe.h: NBE_IC_FIXED_AMPLITUDE, _INVERT_PHASE, _WHITE_NOISE
+
+
+def _flag(v, name):
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError("%s must be a bool, got %r" % (name, v))
+    return bool(v)
+
+
+def _flags(fixed_amplitude, invert_phase):
+    return (FIXED_AMPLITUDE if _flag(fixed_amplitude, "fixed_amplitude") else 0) | \
+        (INVERT_PHASE if _flag(invert_phase, "invert_phase") else 0)
+
+
+def _cuda_device(device):
+    """`device` as a torch.device of type cuda, or None for the current one (resolved when the device work starts)."""
+    if device is None:
+        return None
+    try:
+        dev = torch.device("cuda", device) if isinstance(device, numbers.Integral) and not isinstance(device, bool) \
+            else torch.device(device)
+    except (TypeError, RuntimeError, ValueError):
+        raise ValueError("device must be a CUDA (HIP) device, got %r" % (device,))
+    if dev.type != "cuda":
+        raise ValueError("device must be a CUDA (HIP) device, got %r: there is no CPU fallback" % (device,))
+    return dev
+
+
+def _resolve(dev):
+    cur = density._device()
+    return cur if dev is None or dev.index is None else dev
+
+
+def _out_kind(out):
+    if out not in ("torch", "numpy"):
+        raise ValueError("out must be 'torch' or 'numpy', got %r" % (out,))
+    return out
+
+
+def _max_blocks(v):
+    if v is None:
+        return 0
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Integral) or int(v) < 1:
+        raise ValueError("_max_blocks must be a positive int, got %r" % (v,))
+    return int(v)
+
+
+def _validate_draw(n, boxsize, k_table, pk_table, seed, scale, fixed_amplitude, invert_phase, device, max_blocks, what):
+    """Every argument of a draw, before any device work: (n, L, table, seed, scale, flags, device or None, max_blocks)."""
+    n = _size(n, "n")
+    L = density._triple(boxsize, "boxsize", "a length")
+    if len(set(L)) != 1:
+        raise ValueError("%s needs a cubic box, got boxsize %s" % (what, L))
+    return (n, L[0], _validate_table(k_table, pk_table), _seed(seed), _real(scale, "scale", positive=True),
+            _flags(fixed_amplitude, invert_phase), _cuda_device(device), _max_blocks(max_blocks))
+
+
+def _draw_spectrum(n, L, table, seed, scale, flags, dev, max_blocks=0):
+    """nbe_gaussian_spectrum on device `dev`; table from _validate_table, or None with the WHITE_NOISE flag."""
+    out = _empty_spectrum(n, dev)
+    if flags & WHITE_NOISE:
+        kp = pp = None
+        nt, slope, intercept = 0, 0.0, 0.0
+    else:
+        k, pk, slope, intercept = table
+        kd, pd = torch.from_numpy(k).to(dev), torch.from_numpy(pk).to(dev)
+        kp, pp, nt = _ptr(kd), _ptr(pd), int(k.size)
+    _lib.check(_lib.lib().nbe_gaussian_spectrum(_ptr(out), n, kp, pp, nt, slope, intercept, L, scale, seed, flags,
+                                                max_blocks, _stream(dev)))
+    return out
+
+
+def _colour_spectrum(spec, n, table, L, scale):
+    """nbe_spectrum_colour, in place, on a contiguous complex64 half spectrum on the device."""
+    k, pk, slope, intercept = table
+    dev = spec.device
+    kd, pd = torch.from_numpy(k).to(dev), torch.from_numpy(pk).to(dev)
+    _lib.check(_lib.lib().nbe_spectrum_colour(_ptr(spec), n, _ptr(kd), _ptr(pd), int(k.size), slope, intercept, L, scale,
+                                              _stream(dev)))
+    return spec
+
+
+def gaussian_spectrum(n, boxsize=1000.0, k_table=None, pk_table=None, seed=0, scale=1.0, fixed_amplitude=False,
+                      invert_phase=False, device=None, _max_blocks=None):
+    """The complex64 half spectrum (n, n, n // 2 + 1) of a Gaussian random field with the tabulated linear P(k), drawn on
+    the device from a seed: the draw of the reference's run_lpt_emulator_pipeline(seed=...) (scripts/core.py:263-302, white
+    noise coloured with a tabulated P(k)).  Returns a CUDA tensor on `device` (default: the current one).
+
+    One seed is one universe at every resolution.  For a mesh of n^3, 2 <= n <= 2048, the half spectrum has index
+    (i0, i1, i2), 0 <= i2 <= n/2, and signed wave numbers m_c = i_c for i_c <= n/2 and i_c - n above, so an even Nyquist
+    row is +n/2.
+
+    Pairing (that of `inject_spectrum`): on the planes i2 = 0 and (n even) i2 = n/2 the rows (i0, i1) and
+    ((n - i0) % n, (n - i1) % n) form a pair; the row with the smaller i0 n + i1 draws, the other takes the complex
+    conjugate, and a row that is its own mirror is a self mode.
+
+    Counter: Philox4x32-10 with key (seed low word, seed high word) and counter ((uint32) m0, (uint32) m1, (uint32) m2, 1),
+    where m0 and m1 are the two's-complement signed wave numbers of the drawing row.  `inject_spectrum` uses mesh indices
+    and a last word of 0, so the two streams never share a counter, and this counter does not depend on n.
+
+    Uniforms and the Gaussian (as in `inject_spectrum`): U1 = (x0 + 1/2) 2^-32, U2 = (x1 + 1/2) 2^-32,
+    g = sqrt(-2 ln U1) (cospi(2 U2) + i sinpi(2 U2)) in float64; no draw exceeds 6.8 sigma.
+
+    Amplitude: sigma = scale n^3 sqrt(P(|k|) / L^3), multiplied in that order, |k| = (2 pi / L) sqrt(|m|^2) with the integer
+    |m|^2.  P is evaluated as `inject_spectrum` documents: np.interp inside the table, pk_table[0] below it, the fitted
+    log-log tail above it, clamped at 0.  Only products follow, so sigma and every word for n and 2n differ by exactly 8.
+
+    Modes: F(0) = +0; a self mode gets F = sigma Re g (imaginary word +0); every other mode F = sigma g / sqrt(2).  Each
+    float32 word is rounded once.  `fixed_amplitude=True` (the Quijote "fixed" fields): a non-self mode gets
+    F = sigma (cospi(2 U2) + i sinpi(2 U2)), a self mode +sigma if cospi(2 U2) >= 0 and -sigma otherwise.
+    `invert_phase=True` (the "paired" partner): F -> -F for every mode; words that are +0 stay +0.
+
+    What nesting covers: modes with every |m_c| < n/2 and i2 > 0 are the same draws at every n, and so are the drawing
+    rows of the plane i2 = 0 (which row of a pair draws does not depend on n either).  Modes on a Nyquist row of an even n
+    are not the same draws at other resolutions: at n such a mode is constrained (paired or self), at 2n it is an ordinary
+    mode.
+
+    `scale` (finite, > 0) multiplies the field, e.g. the growth factor D(a) / D(a_0) for a table given at a_0; the paired
+    field is `invert_phase`, not a negative scale.  N-GenIC's own random stream is not matched, and DISCO-DJ cannot be
+    imported where this library is developed; a reference run is reproduced through `colour_noise` from the two files it
+    writes (white_noise_ngenic.npy and class_linear_pk_*_table.txt).  The table is required: CLASS is not available
+    here, and the table is taken as given (no sigma_8 normalisation)."""
+    n, L, table, seed, scale, flags, dev, mb = _validate_draw(n, boxsize, k_table, pk_table, seed, scale, fixed_amplitude,
+                                                              invert_phase, device, _max_blocks, "gaussian_spectrum")
+    dev = _resolve(dev)
+    with torch.cuda.device(dev):
+        return _draw_spectrum(n, L, table, seed, scale, flags, dev, mb)
+
+
+def gaussian_field(n, boxsize=1000.0, k_table=None, pk_table=None, seed=0, scale=1.0, fixed_amplitude=False,
+                   invert_phase=False, device=None, _max_blocks=None, out="torch"):
+    """The (n, n, n) float32 linear density field of `gaussian_spectrum` (same arguments and definition; reference
+    scripts/core.py:263-302): one draw pass and one irfftn.  out: "torch" (a CUDA tensor on `device`) or "numpy"."""
+    n, L, table, seed, scale, flags, dev, mb = _validate_draw(n, boxsize, k_table, pk_table, seed, scale, fixed_amplitude,
+                                                              invert_phase, device, _max_blocks, "gaussian_field")
+    out = _out_kind(out)
+    dev = _resolve(dev)
+    with torch.cuda.device(dev):
+        x = _real_field(_draw_spectrum(n, L, table, seed, scale, flags, dev, mb), n)
+    return x if out == "torch" else x.cpu().numpy()
+
+
+def white_noise(n, seed=0, fixed_amplitude=False, invert_phase=False, device=None, out="torch"):
+    """A real (n, n, n) float32 white-noise field of unit variance: the draw of `gaussian_spectrum` with sigma = n^(3/2)
+    under torch's unnormalised forward transform, so colour_noise(white_noise(n, seed), ...) is gaussian_field(n, ...,
+    seed=seed) up to the rounding of the two extra transforms.  out: "torch" (a CUDA tensor on `device`) or "numpy"."""
+    n, seed, flags, dev, out = _size(n, "n"), _seed(seed), _flags(fixed_amplitude, invert_phase), _cuda_device(device), \
+        _out_kind(out)
+    dev = _resolve(dev)
+    with torch.cuda.device(dev):
+        x = _real_field(_draw_spectrum(n, 1.0, None, seed, 1.0, flags | WHITE_NOISE, dev), n)
+    return x if out == "torch" else x.cpu().numpy()
+
+
+def colour_noise(white, boxsize, k_table, pk_table, scale=1.0):
+    """The linear density field of somebody else's white noise (reference scripts/core.py:263-302, which colours N-GenIC's
+    white noise with the CLASS table; both are written by a reference run as white_noise_ngenic.npy and
+    class_linear_pk_*_table.txt).
+
+    white: cubic (n, n, n) float32 of unit variance, NumPy array or CUDA tensor, 2 <= n <= 2048.  With w_k its unnormalised
+    forward transform, delta_k = w_k scale sqrt(n^3 P(|k|) / L^3): the multiplier in float64, each word of the product
+    rounded once, delta_0 = 0; P as `inject_spectrum` documents.  One rfftn, the colour pass in place, one irfftn.  Returns
+    (n, n, n) float32 of the input's kind."""
+    w, n, L = _cubic(white, "white", boxsize, "colour_noise", "(n, n, n) field", MIN_N, MAX_N)
+    table, scale = _validate_table(k_table, pk_table), _real(scale, "scale", positive=True)
+    dev = _device_of(w)
+    with torch.cuda.device(dev):
+        spec = _colour_spectrum(_half_spectrum(_to_device(w, dev, (torch.float32,))), n, table, L, scale)
+        return _back(w, _real_field(spec, n))
+
+
+def linear_ics(n, boxsize, k_table, pk_table, seed, scale=1.0, fixed_amplitude=False, invert_phase=False,
+               return_delta=True, device=None, _max_batch=None):
+    """Initial conditions from a seed: (delta, psi) on the device, the linear field of `gaussian_spectrum` (reference
+    scripts/core.py:263-302) and its first-order LPT displacement (scripts/core.py:396-397), without a forward transform.
+
+    The drawn spectrum goes straight into nbe_zeldovich_spectrum and through the inverse path of `zeldovich_displacement`
+    (batched, or one component at a time where memory is short), so psi has the bits zeldovich_displacement's inverse path
+    gives for that spectrum; delta does not pass through real space on its way to psi.  delta: (n, n, n) float32, or None
+    with return_delta=False (three irfftn instead of four).  psi: (3, n, n, n) float32, psi_k = i k / |k|^2 delta_k, valid
+    process_box input.  `scale` enters through the field: delta and psi both carry it.  Both are CUDA tensors."""
+    n, L, table, seed, scale, flags, dev, _ = _validate_draw(n, boxsize, k_table, pk_table, seed, scale, fixed_amplitude,
+                                                             invert_phase, device, None, "linear_ics")
+    return_delta = _flag(return_delta, "return_delta")
+    dev = _resolve(dev)
+    with torch.cuda.device(dev):
+        spec = _draw_spectrum(n, L, table, seed, scale, flags, dev)
+        psi_k = _psi_spectrum(spec, n, L, 1.0)
+        delta = _real_field(spec, n) if return_delta else None
+        del spec
+        psi = _inverse_components(psi_k, n, _max_batch)
+    return delta, psi
