@@ -40,7 +40,7 @@ typedef struct nbe_layer_desc {
     const float* dweight;       /* premodulated velocity trees only, same shape as weight */
 } nbe_layer_desc;
 
-enum { NBE_F32 = 0, NBE_F16 = 1 };
+enum { NBE_F32 = 0, NBE_F16 = 1, NBE_F64 = 2 };   /* NBE_F64: particle positions only (nbe_paint_particles) */
 
 const char* nbe_last_error(void);
 int nbe_version(void);
@@ -277,6 +277,29 @@ int nbe_paint_fields(const void* disp, int disp_dtype, const void* quantity, int
                      const int exponents[], const void* shift, int shift_dtype, int shift_axis, double shift_scale,
                      const int64_t n[3], const double boxsize[3], const int64_t res[3], int worder, void* mesh,
                      void* qmesh, void* stats, void* stream);
+/* Particle catalogues: the integer scheme of nbe_paint_fields for explicit positions.  Replaces
+ * nbodykit's catalogue-to-mesh step (ArrayCatalog(...).to_mesh(Nmesh, resampler, position, value).compute(), the way the
+ * halos of scripts/halos.py:407-450 reach a mesh) and the particle-to-mesh step of project_field_from_particles for
+ * positions that are not a displaced lattice.  pos = (count, 3) row-major, float32 or float64 (pos_dtype NBE_F32 /
+ * NBE_F64), any number of boxes away; the mesh coordinate is u_c = x_c (res_c / L_c) in float64, plus shift * (shift_scale
+ * * res / L) along shift_axis (shift = (count,) float32 / float16, or NULL).  order = (count,) int64, a permutation of
+ * 0 .. count-1, or NULL for the identity: a workgroup paints 512 consecutive entries of it through an 8192-cell LDS image
+ * of their footprint, or straight into the meshes where the footprint is larger.  quantity = (nchan, count), exponents,
+ * mesh, qmesh and the integers added are those of nbe_paint_fields: the meshes are the same bits for every order.  stats =
+ * 4 int32, zeroed: [0] chunks of 512 entries on the direct path, [1] particles with a non-finite or out-of-range position
+ * (or an entry of order outside 0 .. count-1), NOT painted; [2] is written by nbe_mesh_to_field.  1 <= count < 2^31. */
+int nbe_paint_particles(const void* pos, int pos_dtype, const void* order, const void* quantity, int quantity_dtype,
+                        int nchan, const int exponents[], const void* shift, int shift_dtype, int shift_axis,
+                        double shift_scale, int64_t count, const double boxsize[3], const int64_t res[3], int worder,
+                        void* mesh, void* qmesh, void* stats, void* stream);
+/* the order worth passing to nbe_paint_particles (no counterpart in the reference; nbodykit sorts nothing): keys = (count,)
+ * int64, keys[p] = the index of the mesh tile of tile_edge^3 cells that holds node floor(u) mod res of particle p (u as
+ * above, same shift arguments): row-major over the ceil(res / tile_edge) tiles per axis, or with morton != 0 the
+ * interleaved bits of the three tile indices.  A particle nbe_paint_particles would reject gets INT64_MAX.  The caller
+ * sorts the keys and passes the permutation as `order`. */
+int nbe_particle_keys(const void* pos, int pos_dtype, const void* shift, int shift_dtype, int shift_axis,
+                      double shift_scale, int64_t count, const double boxsize[3], const int64_t res[3], int tile_edge,
+                      int morton, void* keys, void* stream);
 /* second half of project_field_from_particles (normalize_by_density): the meshes of nbe_paint_fields -> field = (nchan,
  * res) float32, in float64 with one rounding.  NBE_FIELD_MEAN: S 2^(e_c - 46) n_cells / nparticles.  NBE_FIELD_DENSITY:
  * S 2^(e_c - 24) / M, and `fill` where M = 0.  stats[2] += the cells with M >= 2^39, whose S may have wrapped. */

@@ -84,6 +84,11 @@ SIGNATURES = {
     "nbe_paint_fields": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p,
                                    C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nbe_paint_particles": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                      C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int64, C.POINTER(C.c_double),
+                                      C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nbe_particle_keys": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int64,
+                                    C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nbe_mesh_to_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.c_int64,
                                     C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nbe_deconvolve_mas": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),

@@ -261,6 +261,85 @@ __device__ inline float load_real(const void* p, int half, long long i) {
     return half ? (float)((const _Float16*)p)[i] : ((const float*)p)[i];
 }
 
+// What paint_field_kernel and paint_particles_kernel do once the positions u, the integers V and the footprint of a
+// workgroup's 512 particles are known (two per thread): the meshes, and the two ways into them.
+struct FieldMeshes {
+    unsigned long long* mesh;
+    unsigned long long* qmesh;
+    long long cells;
+    int r0, r1, r2, nchan;
+};
+
+// (each extent is tested first: the product of three extents of up to 2^31 cells does not fit 64 bits)
+__device__ inline bool beyond_image(long long e0, long long e1, long long e2) {
+    return e0 > kFieldCells || e1 > kFieldCells || e2 > kFieldCells || e0 * e1 * e2 > kFieldCells;
+}
+
+// a thread's node bounds mn, mx (INT_MAX: no live particle) into the workgroup's lo, hi; false if nothing is live (uniform)
+__device__ inline bool merge_footprint(const int* mn, const int* mx, int* lo, int* hi) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (mn[c] != INT_MAX) { atomicMin(&lo[c], mn[c]); atomicMax(&hi[c], mx[c]); }
+    }
+    __syncthreads();
+    return hi[0] >= lo[0];
+}
+
+// footprint larger than the image: one particle's integers straight into the meshes
+template <int P>
+__device__ inline void direct_add(const FieldMeshes& M, const double* uk, const int* Vk) {
+    const int r0 = M.r0, r1 = M.r1, r2 = M.r2, nchan = M.nchan;
+    const long long cells = M.cells;
+    int j0[3];
+    particle_weights<P>(uk, j0, [&](int a, int b, int c, unsigned q) {
+        const long long g = ((long long)wrap(j0[0] + a, r0) * r1 + wrap(j0[1] + b, r1)) * r2 + wrap(j0[2] + c, r2);
+        atomicAdd(&M.mesh[g], (unsigned long long)q);
+        if (0 < nchan && Vk[0]) atomicAdd(&M.qmesh[g], (unsigned long long)((long long)q * Vk[0]));
+        if (1 < nchan && Vk[1]) atomicAdd(&M.qmesh[cells + g], (unsigned long long)((long long)q * Vk[1]));
+        if (2 < nchan && Vk[2]) atomicAdd(&M.qmesh[2 * cells + g], (unsigned long long)((long long)q * Vk[2]));
+        if (3 < nchan && Vk[3]) atomicAdd(&M.qmesh[3 * cells + g], (unsigned long long)((long long)q * Vk[3]));
+    });
+}
+
+// the mass, then one channel per pass through the one image of the footprint lo .. hi (at most kFieldCells cells), each
+// flushed row-major with 64-bit atomics
+template <int P>
+__device__ inline void image_passes(const FieldMeshes& M, unsigned long long* img, const int* lo, const int* hi,
+                                    double (*u)[3], const int (*V)[NBE_PAINT_MAX_CHANNELS], const bool* live) {
+    static_assert(kPerThread == 2, "the scatter steps below name both particles of a thread");
+    const int tid = threadIdx.x;
+    const int r0 = M.r0, r1 = M.r1, r2 = M.r2;
+    const int l0 = lo[0], l1 = lo[1], l2 = lo[2];
+    const int E1 = hi[1] - l1 + 1, E2 = hi[2] - l2 + 1, vol = (hi[0] - l0 + 1) * E1 * E2;
+    for (int pass = 0; pass <= M.nchan; ++pass) {
+        for (int i = tid; i < vol; i += kPaintThreads) img[i] = 0ull;
+        __syncthreads();
+        auto scatter = [&](double* uk, const int* Vk) {
+            const int v = pass == 0 ? 1 : pass == 1 ? Vk[0] : pass == 2 ? Vk[1] : pass == 3 ? Vk[2] : Vk[3];
+            if (!v) return;
+            // keeps the weights from being computed ahead of the pass loop and held in ~2 P^3 registers
+            asm volatile("" : "+v"(uk[0]), "+v"(uk[1]), "+v"(uk[2]));
+            int j0[3];
+            particle_weights<P>(uk, j0, [&](int a, int b, int c, unsigned q) {
+                atomicAdd(&img[((j0[0] + a - l0) * E1 + (j0[1] + b - l1)) * E2 + (j0[2] + c - l2)],
+                          (unsigned long long)((long long)q * v));
+            });
+        };
+        if (live[0]) scatter(u[0], V[0]);
+        if (live[1]) scatter(u[1], V[1]);
+        __syncthreads();
+        unsigned long long* dst = pass == 0 ? M.mesh : M.qmesh + (pass - 1) * M.cells;
+        for (int i = tid; i < vol; i += kPaintThreads) {
+            const unsigned long long v = img[i];
+            if (!v) continue;
+            const int c2 = i % E2, r = i / E2, c1 = r % E1, c0 = r / E1;
+            const long long g = ((long long)wrap(l0 + c0, r0) * r1 + wrap(l1 + c1, r1)) * r2 + wrap(l2 + c2, r2);
+            atomicAdd(&dst[g], v);
+        }
+        __syncthreads();
+    }
+}
+
 template <int P>
 __global__ __launch_bounds__(kPaintThreads) void paint_field_kernel(FieldArgs A) {
     __shared__ unsigned long long img[kFieldCells];
@@ -275,7 +354,6 @@ __global__ __launch_bounds__(kPaintThreads) void paint_field_kernel(FieldArgs A)
 
     const long long ncell = A.n0 * A.n1 * A.n2;
     const int nchan = A.nchan;
-    static_assert(kPerThread == 2, "the scatter steps below name both particles of a thread");
     double u[kPerThread][3];
     int V[kPerThread][NBE_PAINT_MAX_CHANNELS];
     bool live[kPerThread];
@@ -321,65 +399,143 @@ __global__ __launch_bounds__(kPaintThreads) void paint_field_kernel(FieldArgs A)
             mx[c] = max(mx[c], j + P - 1);
         }
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (mn[c] != INT_MAX) { atomicMin(&lo[c], mn[c]); atomicMax(&hi[c], mx[c]); }
-    }
-    __syncthreads();
-    if (hi[0] < lo[0]) return;                             // no live particle in this tile (uniform)
+    if (!merge_footprint(mn, mx, lo, hi)) return;          // no live particle in this tile
 
-    const long long e0 = (long long)hi[0] - lo[0] + 1, e1 = (long long)hi[1] - lo[1] + 1,
-                    e2 = (long long)hi[2] - lo[2] + 1;
-    const int r0 = A.r0, r1 = A.r1, r2 = A.r2;
-    const long long cells = (long long)r0 * r1 * r2;
-    // (each extent is tested first: the product of three extents of up to 2^31 cells does not fit 64 bits)
-    if (e0 > kFieldCells || e1 > kFieldCells || e2 > kFieldCells || e0 * e1 * e2 > kFieldCells) {
-        // footprint larger than the image: the same integers straight into the meshes
+    const FieldMeshes M = {A.mesh, A.qmesh, (long long)A.r0 * A.r1 * A.r2, A.r0, A.r1, A.r2, nchan};
+    if (beyond_image((long long)hi[0] - lo[0] + 1, (long long)hi[1] - lo[1] + 1, (long long)hi[2] - lo[2] + 1)) {
         if (tid == 0) atomicAdd(&A.stats[0], 1);
-        auto direct = [&](const double* uk, const int* Vk) {
-            int j0[3];
-            particle_weights<P>(uk, j0, [&](int a, int b, int c, unsigned q) {
-                const long long g = ((long long)wrap(j0[0] + a, r0) * r1 + wrap(j0[1] + b, r1)) * r2 + wrap(j0[2] + c, r2);
-                atomicAdd(&A.mesh[g], (unsigned long long)q);
-                if (0 < nchan && Vk[0]) atomicAdd(&A.qmesh[g], (unsigned long long)((long long)q * Vk[0]));
-                if (1 < nchan && Vk[1]) atomicAdd(&A.qmesh[cells + g], (unsigned long long)((long long)q * Vk[1]));
-                if (2 < nchan && Vk[2]) atomicAdd(&A.qmesh[2 * cells + g], (unsigned long long)((long long)q * Vk[2]));
-                if (3 < nchan && Vk[3]) atomicAdd(&A.qmesh[3 * cells + g], (unsigned long long)((long long)q * Vk[3]));
-            });
-        };
-        if (live[0]) direct(u[0], V[0]);
-        if (live[1]) direct(u[1], V[1]);
+        if (live[0]) direct_add<P>(M, u[0], V[0]);
+        if (live[1]) direct_add<P>(M, u[1], V[1]);
         return;
     }
+    image_passes<P>(M, img, lo, hi, u, V, live);
+}
 
-    const int E1 = (int)e1, E2 = (int)e2, vol = (int)(e0 * e1 * e2);
-    const int l0 = lo[0], l1 = lo[1], l2 = lo[2];
-    for (int pass = 0; pass <= nchan; ++pass) {            // the mass, then one channel per pass through the one image
-        for (int i = tid; i < vol; i += kPaintThreads) img[i] = 0ull;
-        __syncthreads();
-        auto scatter = [&](double* uk, const int* Vk) {
-            const int v = pass == 0 ? 1 : pass == 1 ? Vk[0] : pass == 2 ? Vk[1] : pass == 3 ? Vk[2] : Vk[3];
-            if (!v) return;
-            // keeps the weights from being computed ahead of the pass loop and held in ~2 P^3 registers
-            asm volatile("" : "+v"(uk[0]), "+v"(uk[1]), "+v"(uk[2]));
-            int j0[3];
-            particle_weights<P>(uk, j0, [&](int a, int b, int c, unsigned q) {
-                atomicAdd(&img[((j0[0] + a - l0) * E1 + (j0[1] + b - l1)) * E2 + (j0[2] + c - l2)],
-                          (unsigned long long)((long long)q * v));
-            });
-        };
-        if (live[0]) scatter(u[0], V[0]);
-        if (live[1]) scatter(u[1], V[1]);
-        __syncthreads();
-        unsigned long long* dst = pass == 0 ? A.mesh : A.qmesh + (pass - 1) * cells;
-        for (int i = tid; i < vol; i += kPaintThreads) {
-            const unsigned long long v = img[i];
-            if (!v) continue;
-            const int c2 = i % E2, r = i / E2, c1 = r % E1, c0 = r / E1;
-            const long long g = ((long long)wrap(l0 + c0, r0) * r1 + wrap(l1 + c1, r1)) * r2 + wrap(l2 + c2, r2);
-            atomicAdd(&dst[g], v);
+// ---- Particle catalogues --------------------------------------------------------------------
+// The integer scheme of paint_field_kernel for explicit positions: halos, a subsample, an N-body snapshot.  A workgroup
+// takes a chunk of kChunk consecutive entries of `order` (the last chunk is ragged) and follows the three passes above:
+// its footprint from its own particles, the LDS image where that fits, the direct path where it does not.  Which chunk a
+// particle falls into changes the path only, never an integer that is added: the meshes are the same bits for every
+// order.  particle_keys_kernel gives the order that keeps consecutive chunks compact.
+constexpr int kChunk = kPaintThreads * kPerThread;
+
+struct PositionArgs {
+    const void* pos;            // (count, 3) float32 or float64
+    const void* shift;          // (count,) added along axis `los` after scaling by vs, or NULL
+    int pos_f64, shift_half, los;
+    double vs;                  // mesh cells per unit of the shift
+    double s0, s1, s2;          // mesh cells per unit of length (res_i / L_i)
+    long long count;
+};
+
+struct ParticleArgs {
+    PositionArgs pos;
+    const long long* order;     // (count,) permutation, or NULL: the identity
+    const void* qty;            // (nchan, count)
+    int qty_half, nchan;
+    int r0, r1, r2;
+    int qexp[NBE_PAINT_MAX_CHANNELS];   // 24 - e_c
+    unsigned long long* mesh;   // as FieldArgs
+    unsigned long long* qmesh;
+    int* stats;                 // [0] chunks on the direct path, [1] particles with a non-finite or huge position
+};
+
+// u = x (res / L) in float64, plus the shift along its axis; false for a position that is not painted
+__device__ inline bool particle_position(const PositionArgs& A, long long idx, double* u) {
+    if (A.pos_f64) {
+        const double* x = (const double*)A.pos + 3 * idx;
+        u[0] = x[0] * A.s0; u[1] = x[1] * A.s1; u[2] = x[2] * A.s2;
+    } else {
+        const float* x = (const float*)A.pos + 3 * idx;
+        u[0] = (double)x[0] * A.s0; u[1] = (double)x[1] * A.s1; u[2] = (double)x[2] * A.s2;
+    }
+    if (A.shift) {
+        const double d = (double)load_real(A.shift, A.shift_half, idx) * A.vs;
+        if (A.los == 0) u[0] += d;
+        else if (A.los == 1) u[1] += d;
+        else u[2] += d;
+    }
+    return fabs(u[0]) < kUMax && fabs(u[1]) < kUMax && fabs(u[2]) < kUMax;
+}
+
+template <int P>
+__global__ __launch_bounds__(kPaintThreads) void paint_particles_kernel(ParticleArgs A) {
+    __shared__ unsigned long long img[kFieldCells];
+    __shared__ int lo[3], hi[3];
+    const int tid = threadIdx.x;
+    if (tid < 3) { lo[tid] = INT_MAX; hi[tid] = INT_MIN; }
+    __syncthreads();
+
+    const long long count = A.pos.count;
+    const int nchan = A.nchan;
+    double u[kPerThread][3];
+    int V[kPerThread][NBE_PAINT_MAX_CHANNELS];
+    bool live[kPerThread];
+    int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
+#pragma unroll
+    for (int k = 0; k < kPerThread; ++k) {
+        const long long e = (long long)blockIdx.x * kChunk + tid + k * kPaintThreads;
+        live[k] = e < count;
+#pragma unroll
+        for (int c = 0; c < NBE_PAINT_MAX_CHANNELS; ++c) V[k][c] = 0;
+        if (!live[k]) continue;
+        const long long idx = A.order ? A.order[e] : e;
+        // (an entry of `order` outside 0 .. count-1 reads nothing and is counted with the rejected particles)
+        if (idx < 0 || idx >= count || !particle_position(A.pos, idx, u[k])) {
+            live[k] = false;
+            atomicAdd(&A.stats[1], 1);
+            continue;
         }
-        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < NBE_PAINT_MAX_CHANNELS; ++c)
+            if (c < nchan)
+                V[k][c] = (int)rint(ldexp((double)load_real(A.qty, A.qty_half, c * count + idx), A.qexp[c]));
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int j = (int)floor(u[k][c] + 1.0 - 0.5 * P);
+            mn[c] = min(mn[c], j);
+            mx[c] = max(mx[c], j + P - 1);
+        }
+    }
+    if (!merge_footprint(mn, mx, lo, hi)) return;          // no live particle in this chunk
+
+    const FieldMeshes M = {A.mesh, A.qmesh, (long long)A.r0 * A.r1 * A.r2, A.r0, A.r1, A.r2, nchan};
+    if (beyond_image((long long)hi[0] - lo[0] + 1, (long long)hi[1] - lo[1] + 1, (long long)hi[2] - lo[2] + 1)) {
+        if (tid == 0) atomicAdd(&A.stats[0], 1);
+        if (live[0]) direct_add<P>(M, u[0], V[0]);
+        if (live[1]) direct_add<P>(M, u[1], V[1]);
+        return;
+    }
+    image_passes<P>(M, img, lo, hi, u, V, live);
+}
+
+// bits of x spread to every third position (x < 2^20)
+__device__ inline unsigned long long spread3(unsigned long long x) {
+    x = (x | x << 32) & 0x1f00000000ffffull;
+    x = (x | x << 16) & 0x1f0000ff0000ffull;
+    x = (x | x << 8) & 0x100f00f00f00f00full;
+    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
+    x = (x | x << 2) & 0x1249249249249249ull;
+    return x;
+}
+
+// keys[p] = the index of the mesh tile (edge^3 cells) that holds the periodically reduced node floor(u) of particle p:
+// row-major over the tiles, or with MORTON their interleaved bits; LLONG_MAX for a particle that would not be painted.
+// (A template, so that it is emitted after the painters: a kernel emitted ahead of paint_kernel moves that kernel in the
+// code object, and its PCS instance then measured 1 % slower with the same instructions)
+template <bool MORTON>
+__global__ __launch_bounds__(256) void particle_keys_kernel(PositionArgs A, int r0, int r1, int r2, int edge,
+                                                            long long* __restrict__ keys) {
+    const long long T1 = (r1 + edge - 1) / edge, T2 = (r2 + edge - 1) / edge;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < A.count; i += (long long)gridDim.x * blockDim.x) {
+        double u[3];
+        long long key = LLONG_MAX;
+        if (particle_position(A, i, u)) {
+            const long long t0 = wrap((int)floor(u[0]), r0) / edge, t1 = wrap((int)floor(u[1]), r1) / edge,
+                            t2 = wrap((int)floor(u[2]), r2) / edge;
+            key = MORTON ? (long long)(spread3(t0) << 2 | spread3(t1) << 1 | spread3(t2)) : (t0 * T1 + t1) * T2 + t2;
+        }
+        keys[i] = key;
     }
 }
 
@@ -1219,6 +1375,87 @@ int nbe_paint_fields(const void* disp, int disp_dtype, const void* quantity, int
     const dim3 grid((unsigned)tiles), block(kPaintThreads);
     with_worder(worder, [&](auto P) { hipLaunchKernelGGL(paint_field_kernel<decltype(P)::value>, grid, block, 0, s, A); });
     return launched("nbe_paint_fields");
+}
+
+// the position arguments both particle entry points share; false (with the error set) when they are not valid
+static bool position_args(const char* who, PositionArgs& P, const void* pos, int pos_dtype, const void* shift,
+                          int shift_dtype, int shift_axis, double shift_scale, int64_t count, const double boxsize[3],
+                          const int64_t res[3]) {
+    if (!pos || !boxsize || !res) return fail("%s: NULL argument", who), false;
+    if (pos_dtype != NBE_F32 && pos_dtype != NBE_F64) return fail("%s: position dtype %d unsupported", who, pos_dtype), false;
+    if (shift && shift_dtype != NBE_F32 && shift_dtype != NBE_F16)
+        return fail("%s: shift dtype %d unsupported", who, shift_dtype), false;
+    if (shift && (shift_axis < 0 || shift_axis > 2 || !std::isfinite(shift_scale)))
+        return fail("%s: bad shift (axis %d, scale %g)", who, shift_axis, shift_scale), false;
+    if (count < 1 || count > INT_MAX) return fail("%s: %lld particles unsupported (1 .. 2^31 - 1)", who, (long long)count), false;
+    for (int c = 0; c < 3; ++c) {
+        if (res[c] < 1 || res[c] > (1 << 20) || !(boxsize[c] > 0.0) || !std::isfinite(boxsize[c]))
+            return fail("%s: bad geometry on axis %d (res %lld, boxsize %g)", who, c, (long long)res[c], boxsize[c]), false;
+    }
+    P.pos = pos;
+    P.shift = shift;
+    P.pos_f64 = pos_dtype == NBE_F64;
+    P.shift_half = shift_dtype == NBE_F16;
+    P.los = shift ? shift_axis : 0;
+    P.s0 = res[0] / boxsize[0]; P.s1 = res[1] / boxsize[1]; P.s2 = res[2] / boxsize[2];
+    P.vs = shift ? shift_scale * (res[P.los] / boxsize[P.los]) : 0.0;
+    P.count = count;
+    return true;
+}
+
+int nbe_paint_particles(const void* pos, int pos_dtype, const void* order, const void* quantity, int quantity_dtype,
+                        int nchan, const int exponents[], const void* shift, int shift_dtype, int shift_axis,
+                        double shift_scale, int64_t count, const double boxsize[3], const int64_t res[3], int worder,
+                        void* mesh, void* qmesh, void* stats, void* stream) {
+    if (!mesh || !stats) return fail("nbe_paint_particles: NULL argument");
+    if (nchan < 0 || nchan > NBE_PAINT_MAX_CHANNELS)
+        return fail("nbe_paint_particles: %d channels unsupported (0 .. %d)", nchan, NBE_PAINT_MAX_CHANNELS);
+    if (nchan && (!quantity || !qmesh || !exponents)) return fail("nbe_paint_particles: NULL quantity argument");
+    if (nchan && quantity_dtype != NBE_F32 && quantity_dtype != NBE_F16)
+        return fail("nbe_paint_particles: quantity dtype %d unsupported", quantity_dtype);
+    if (worder < 1 || worder > 4) return fail("nbe_paint_particles: worder %d not in 1..4", worder);
+    ParticleArgs A;
+    if (!position_args("nbe_paint_particles", A.pos, pos, pos_dtype, shift, shift_dtype, shift_axis, shift_scale, count,
+                       boxsize, res))
+        return 1;
+    A.order = (const long long*)order;
+    A.qty = quantity;
+    A.qty_half = quantity_dtype == NBE_F16;
+    A.nchan = nchan;
+    A.r0 = (int)res[0]; A.r1 = (int)res[1]; A.r2 = (int)res[2];
+    for (int c = 0; c < NBE_PAINT_MAX_CHANNELS; ++c) {
+        A.qexp[c] = 0;
+        if (c < nchan) {
+            if (exponents[c] < -200 || exponents[c] > 200)
+                return fail("nbe_paint_particles: exponent %d of channel %d out of range", exponents[c], c);
+            A.qexp[c] = 24 - exponents[c];
+        }
+    }
+    A.mesh = (unsigned long long*)mesh;
+    A.qmesh = (unsigned long long*)qmesh;
+    A.stats = (int*)stats;
+    const dim3 grid((unsigned)((count + kChunk - 1) / kChunk)), block(kPaintThreads);
+    hipStream_t s = (hipStream_t)stream;
+    with_worder(worder, [&](auto P) { hipLaunchKernelGGL(paint_particles_kernel<decltype(P)::value>, grid, block, 0, s, A); });
+    return launched("nbe_paint_particles");
+}
+
+int nbe_particle_keys(const void* pos, int pos_dtype, const void* shift, int shift_dtype, int shift_axis,
+                      double shift_scale, int64_t count, const double boxsize[3], const int64_t res[3], int tile_edge,
+                      int morton, void* keys, void* stream) {
+    if (!keys) return fail("nbe_particle_keys: NULL argument");
+    if (tile_edge < 1 || tile_edge > (1 << 20)) return fail("nbe_particle_keys: tile edge %d unsupported", tile_edge);
+    PositionArgs P;
+    if (!position_args("nbe_particle_keys", P, pos, pos_dtype, shift, shift_dtype, shift_axis, shift_scale, count, boxsize,
+                       res))
+        return 1;
+    const int g = grid_for(count, 256);
+    const dim3 grid(g < 4096 ? g : 4096), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    const int r0 = (int)res[0], r1 = (int)res[1], r2 = (int)res[2];
+    if (morton) hipLaunchKernelGGL(particle_keys_kernel<true>, grid, block, 0, s, P, r0, r1, r2, tile_edge, (long long*)keys);
+    else hipLaunchKernelGGL(particle_keys_kernel<false>, grid, block, 0, s, P, r0, r1, r2, tile_edge, (long long*)keys);
+    return launched("nbe_particle_keys");
 }
 
 int nbe_mesh_to_field(const void* mesh, const void* qmesh, int nchan, const int exponents[], const int64_t res[3],

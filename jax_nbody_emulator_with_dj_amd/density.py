@@ -15,6 +15,8 @@ assignment window (`scripts/utils.py:136-148`) and measures P(k) (`scripts/utils
     vmesh = paint_field(displacement, velocity, boxsize=1000.0, res=512)     # mass-weighted mean velocity, (3, res...)
     delta_s = paint_density(displacement, res=512, velocity=velocity, los=2, velocity_to_length=rsd_factor(z, Om))
     mf = minkowski_functionals(delta, boxsize=1000.0)    # v0 .. v3 at 41 thresholds of the standardized field
+    delta_h = paint_particles(positions, boxsize=1000.0, res=512)           # a catalogue: halos, a subsample, a snapshot
+    cc = cross_correlation(delta_h, delta, boxsize=1000.0)                  # k, p_aa, p_bb, p_ab, r, transfer, bias, nmodes
     bk = bispectrum(delta, boxsize=1000.0, k1=0.1, k2=0.1, theta=np.linspace(0, np.pi, 25))    # B, Q, ntriangles, ...
     st = field_statistics(delta)                         # mean, std, skewness, kurtosis_excess
     pdf = field_pdf(delta, lo=-1.0, hi=8.0, nbins=120)   # np.histogram's counts and density
@@ -35,6 +37,9 @@ Conventions (as DISCO-DJ / Pylians and the lattice of `scripts/halos.py:394-403`
   sums are 64-bit integers, so the fields are bitwise reproducible too (its docstring has the arithmetic).  `velocity`,
   `los` and `velocity_to_length` move the particles along one axis first: redshift space for
   velocity_to_length = `rsd_factor(z, Om)`.
+- `paint_particles` (nbodykit's catalogue-to-mesh step) paints explicit positions, (count, 3) float32 / float64, with the
+  same integers: position x_c sits at mesh coordinate x_c res_c / L_c in float64, wrapped like a lattice particle.  The
+  result does not depend on the order of the rows nor on `sort`.
 - Deconvolution divides the rfft of the mesh by prod_c sinc(k_c L_c / (2 res_c))^worder, sinc(x) = sin(x) / x (the
   window alone, no alias sum).
 - `power_spectrum` uses the unnormalised forward FFT: P = |delta_k|^2 L^3 / n^6.  Shell b = 1 .. n/2 holds the modes
@@ -67,7 +72,7 @@ except Exception:  # pragma: no cover
 
 __all__ = ["paint_density", "deconvolve_mas", "power_spectrum", "minkowski_functionals", "bispectrum",
            "field_statistics", "field_pdf", "paint_field", "rsd_factor", "power_spectrum_multipoles",
-           "power_spectrum_wedges"]
+           "power_spectrum_wedges", "paint_particles", "cross_correlation", "shot_noise"]
 
 WORDERS = {1: "NGP", 2: "CIC", 3: "TSC", 4: "PCS"}
 _UNIT = 2.0 ** 22           # fixed-point units per particle mass (include/nbe.h, nbe_paint_mesh)
@@ -425,6 +430,274 @@ def paint_field(displacement, quantity, boxsize=1000.0, res=512, worder=2, norma
     if single:
         field = field[0]
     return (_back(q, field), _back(q, delta)) if return_delta else _back(q, field)
+
+
+# ---- particle catalogues --------------------------------------------------------------------
+
+_KEY_EDGES = (4, 8)             # nbe_particle_keys: mesh cells per tile edge below / from _KEY_SPARSE cells per particle,
+_KEY_SPARSE = 4                 # row-major tiles: about 64 particles per tile (DESIGN.md section 12.6 has the runs)
+_KEY_MORTON = False
+_AUTO_MIN_COUNT = 1 << 18       # sort="auto" sorts from this many particles on, if the mesh has at most
+_AUTO_MAX_CELLS_PER_PARTICLE = 8    # this many cells per particle: sparser chunks do not fit the LDS image, sorted or not
+_MAX_PARTICLES = (1 << 31) - 1
+
+
+def _check_sort(sort):
+    if not (isinstance(sort, (bool, np.bool_)) or sort == "auto"):
+        raise ValueError("sort must be True, False or 'auto', got %r" % (sort,))
+    return sort if isinstance(sort, str) else bool(sort)
+
+
+def _validate_particles(positions, boxsize, res, worder, weights, quantity, normalize, fill, velocity, los,
+                        velocity_to_length, sort):
+    x = _check_array(positions, "positions")
+    if x.ndim != 2 or x.shape[1] != 3:
+        raise ValueError("positions must have shape (count, 3), got %s" % (tuple(x.shape),))
+    if _dtype_name(x) not in ("float32", "float64"):
+        raise ValueError("positions must be float32 or float64, got %s" % _dtype_name(x))
+    count = int(x.shape[0])
+    if count < 1:
+        raise ValueError("paint_particles: the catalogue is empty (positions has shape %s)" % (tuple(x.shape),))
+    if count > _MAX_PARTICLES:
+        raise ValueError("paint_particles: %d particles exceed one call (2^31 - 1)" % count)
+    boxsize, res, worder = _triple(boxsize, "boxsize", "a length"), _triple(res, "res", "an int"), _check_worder(worder)
+    if weights is not None and quantity is not None:
+        raise ValueError("paint_particles: weights together with a quantity are not supported (pass one of them)")
+    w = q = None
+    if weights is not None:
+        w = _check_array(weights, "weights")
+        if tuple(w.shape) != (count,):
+            raise ValueError("weights must have shape (%d,), got %s" % (count, tuple(w.shape)))
+        if _dtype_name(w) not in ("float32", "float64"):
+            raise ValueError("weights must be float32 or float64, got %s" % _dtype_name(w))
+        _same_kind(x, w, "positions", "weights")
+        if not _is_torch(w):
+            _check_weights(bool(np.isfinite(w).all() and (w >= 0).all()), float(np.sum(w, dtype=np.float64)))
+    if quantity is not None:
+        q = _check_array(quantity, "quantity")
+        if tuple(q.shape) != (count,) and not (q.ndim == 2 and 1 <= q.shape[0] <= _MAX_CHANNELS and q.shape[1] == count):
+            raise ValueError("quantity must have shape (%d,) or (C, %d) with 1 <= C <= %d, got %s"
+                             % (count, count, _MAX_CHANNELS, tuple(q.shape)))
+        if _dtype_name(q) not in ("float32", "float16"):
+            raise ValueError("quantity must be float32 or float16, got %s" % _dtype_name(q))
+        _same_kind(x, q, "positions", "quantity")
+    if normalize not in _NORMALIZE:
+        raise ValueError("normalize must be 'density' or 'mean', got %r" % (normalize,))
+    _real(fill, "fill")
+    los = _check_los(los)
+    v = f = None
+    if velocity is not None:
+        v = _check_array(velocity, "velocity")
+        if tuple(v.shape) not in ((count,), (count, 3)):
+            raise ValueError("velocity must have shape (%d,) or (%d, 3), got %s" % (count, count, tuple(v.shape)))
+        if _dtype_name(v) not in ("float32", "float64", "float16"):
+            raise ValueError("velocity must be float32, float64 or float16, got %s" % _dtype_name(v))
+        _same_kind(x, v, "positions", "velocity")
+        if velocity_to_length is None:
+            raise ValueError("velocity_to_length is required with a velocity (rsd_factor(z, Om) for redshift space)")
+        f = _real(velocity_to_length, "velocity_to_length")
+    return x, count, boxsize, res, worder, w, q, v, los, f, _check_sort(sort)
+
+
+def _check_weights(valid, total):
+    if not valid:
+        raise ValueError("weights must be finite and non-negative")
+    if not total > 0:
+        raise ValueError("paint_particles: the total weight is zero")
+
+
+def _exact_sum(t):
+    """The sum of an int64 tensor as a Python int: exact where torch.sum over all of it would wrap."""
+    return (int(torch.sum(t >> 32)) << 32) + int(torch.sum(t & 0xFFFFFFFF))
+
+
+def _paint_particles(p, q, v, los, scale, boxsize, res, worder, sort="auto", normalize="density", fill=0.0,
+                     want_delta=False, weighted=False, tile_edge=None, morton=None, timer=None):
+    """Device work of paint_particles.  p: contiguous CUDA (count, 3) float32 / float64 tensor; q: contiguous (C, count)
+    float32 / float16 tensor or None (masses only); v: contiguous (count,) float32 / float16 tensor or None.  With
+    `weighted`, q is the (1, count) weights and delta is their density contrast.  tile_edge and morton override the key of
+    the sort (measurements).  `timer(name)` is called before every stage (range, keys, sort, paint, convert) and
+    timer(None) at the end (tools/time_particles.py).  Returns (field (C,) + res or None, delta or None, stats):
+    stats[0] chunks of 512 particles on the direct path, stats[1] particles not painted, stats[2] cells at the overflow
+    limit.  Raises NBEError for a non-finite quantity."""
+    l = _lib.lib()
+    dev = p.device
+    half = lambda t: 1 if t is not None and t.dtype == torch.float16 else 0
+    pdt = 2 if p.dtype == torch.float64 else 0              # include/nbe.h: NBE_F64, NBE_F32
+    nchan = 0 if q is None else int(q.shape[0])
+    count = int(p.shape[0])
+    cells = res[0] * res[1] * res[2]
+    tick = timer or (lambda name: None)
+    if sort == "auto":
+        sort = count >= _AUTO_MIN_COUNT and cells <= _AUTO_MAX_CELLS_PER_PARTICLE * count
+    with torch.cuda.device(dev):
+        s = _stream(dev)
+        L3, r3 = (C.c_double * 3)(*boxsize), _i64(res)
+        shift = (_ptr(v) if v is not None else None, half(v), los, float(scale) if v is not None else 0.0)
+        tick("range")
+        exps = (C.c_int * _MAX_CHANNELS)()
+        if nchan:
+            rng = torch.zeros(nchan + 1, dtype=torch.int32, device=dev)
+            _lib.check(l.nbe_quantity_range(_ptr(q), half(q), nchan, count, _ptr(rng), s))
+            r = rng.cpu().numpy()
+            if int(r[nchan]):
+                raise NBEError("paint_particles: %d value(s) of the %s are not finite"
+                               % (int(r[nchan].view(np.uint32)), "weights" if weighted else "quantity"))
+            for c, e in enumerate(np.frexp(r[:nchan].view(np.float32).astype(np.float64))[1]):
+                exps[c] = int(e)
+        order = None
+        if sort:
+            tick("keys")
+            keys = torch.empty(count, dtype=torch.int64, device=dev)
+            edge = tile_edge or _KEY_EDGES[cells >= _KEY_SPARSE * count]
+            _lib.check(l.nbe_particle_keys(_ptr(p), pdt, *shift, count, L3, r3, int(edge),
+                                           int(_KEY_MORTON if morton is None else morton), _ptr(keys), s))
+            tick("sort")
+            order = torch.sort(keys)[1]
+            del keys
+        tick("paint")
+        mesh = torch.zeros(res, dtype=torch.int64, device=dev)
+        qmesh = torch.zeros((nchan,) + tuple(res), dtype=torch.int64, device=dev) if nchan else None
+        stats = torch.zeros(4, dtype=torch.int32, device=dev)
+        _lib.check(l.nbe_paint_particles(_ptr(p), pdt, _ptr_or_null(order), _ptr(q) if nchan else None, half(q), nchan,
+                                         exps, *shift, count, L3, r3, worder, _ptr(mesh),
+                                         _ptr(qmesh) if nchan else None, _ptr(stats), s))
+        tick("convert")
+        field = delta = None
+        if weighted:
+            # every painted particle's weights sum to exactly 2^22: the total is 2^22 sum(V), and sum(V) takes the place of
+            # the particle count in the mean
+            total = max(_exact_sum(qmesh[0]) >> 22, 1)
+            delta = torch.empty(res, dtype=torch.float32, device=dev)
+            _lib.check(l.nbe_mesh_to_delta(_ptr(qmesh[0]), r3, total, _ptr(delta), s))
+            stats[2] = torch.count_nonzero(mesh >= (1 << 39)).to(torch.int32)     # nbe_mesh_to_field's overflow guard
+        else:
+            if nchan:
+                field = torch.empty((nchan,) + tuple(res), dtype=torch.float32, device=dev)
+                _lib.check(l.nbe_mesh_to_field(_ptr(mesh), _ptr(qmesh), nchan, exps, r3, count, _NORMALIZE[normalize],
+                                               float(fill), _ptr(field), _ptr(stats), s))
+            if want_delta:
+                delta = torch.empty(res, dtype=torch.float32, device=dev)
+                _lib.check(l.nbe_mesh_to_delta(_ptr(mesh), r3, count, _ptr(delta), s))
+        tick(None)
+    return field, delta, stats
+
+
+def paint_particles(positions, boxsize=1000.0, res=512, worder=2, deconvolve=True, weights=None, velocity=None, los=2,
+                    velocity_to_length=None, sort="auto", quantity=None, normalize="density", fill=0.0,
+                    return_delta=False):
+    """Mass assignment of a particle catalogue onto a periodic mesh: halos, a subsample, an N-body snapshot (nbodykit's
+    catalogue-to-mesh step, ArrayCatalog(...).to_mesh(Nmesh, resampler).compute(); the positions the reference builds in
+    scripts/halos.py:394-403 reach a mesh this way).  paint_density and paint_field for positions that are not a lattice.
+
+    positions: (count, 3) float32 / float64, NumPy array or CUDA tensor, in the units of the box; any number of boxes away,
+    negative values included.  Particle p sits at the mesh coordinate x_c res_c / L_c (float64), wrapped periodically.
+    boxsize, res, worder, deconvolve: as paint_density.
+    weights: (count,) non-negative float32 / float64 (read as float32), same kind and device.  The call then returns
+    sum(w m) / mean - 1, m the assignment weights: the weights ride as a quantity channel, and the mean is the exact
+    integer total of that channel's mesh over the number of cells.
+    quantity: (count,) or (C, count), C <= 4, float32 / float16: paint_field's two normalisations (`normalize`, `fill`,
+    `return_delta`, and `deconvolve` divides every channel by the window) with unit masses.  The call returns the field
+    (res, or (C,) + res), and with return_delta also the density contrast of the same pass, not deconvolved.
+    weights together with a quantity raise ValueError: a weighted mean of a quantity is not built.
+    velocity, los, velocity_to_length: velocity (count,) or (count, 3), of which component `los` is read (as float32),
+    moves every particle by velocity_to_length * v along array axis los first (paint_density's redshift-space shift).
+    sort: True sorts the particles by the mesh tile they fall into before painting (nbe_particle_keys, torch.sort), so
+    that the 512 particles a workgroup paints share an LDS image; False paints them in the order given; "auto" sorts
+    from 2^18 particles on where the mesh has at most 8 cells per particle.  The sums are
+    integers: the result is the same bits for every `sort` and every order of the rows.
+
+    Returns float32, NumPy for NumPy input, CUDA tensors on the input's device (torch's current stream) for tensors.
+    Raises ValueError, before any device work, for an empty catalogue, wrong shapes, kinds or devices, and for NumPy
+    weights that are negative, not finite or sum to zero (tensor weights are checked on the device first); NBEError for a
+    non-finite or out-of-range position or velocity (the message names their number), a non-finite quantity, and a cell
+    that holds 2^17 particle masses or more under a quantity or weights (paint_field's limit)."""
+    x, count, boxsize, res, worder, w, q, v, los, f, sort = _validate_particles(
+        positions, boxsize, res, worder, weights, quantity, normalize, fill, velocity, los, velocity_to_length, sort)
+    dev = _device_of(x)
+    pd = _to_device(x, dev, (torch.float32, torch.float64))
+    vd = None
+    if v is not None:
+        vd = _to_device(v, dev, (torch.float32, torch.float64, torch.float16))
+        vd = (vd[:, los] if vd.ndim == 2 else vd)
+        vd = (vd if vd.dtype == torch.float16 else vd.to(torch.float32)).contiguous()
+    qd, single = None, False
+    if w is not None:
+        wd = _to_device(w, dev, (torch.float32, torch.float64))
+        if _is_torch(w):
+            _check_weights(bool((torch.isfinite(wd) & (wd >= 0)).all()), float(wd.sum(dtype=torch.float64)))
+        qd = wd.to(torch.float32).reshape(1, count).contiguous()
+    elif q is not None:
+        qd = _to_device(q, dev, (torch.float32, torch.float16))
+        single = qd.ndim == 1
+        qd = qd.reshape(-1, count)
+    field, delta, stats = _paint_particles(pd, qd, vd, los, f, boxsize, res, worder, sort, normalize, float(fill),
+                                           want_delta=q is None or bool(return_delta), weighted=w is not None)
+    _check_stats(stats, "paint_particles", qd is not None)
+    with torch.cuda.device(dev):
+        if q is None:
+            return _back(x, _deconvolve(delta, worder) if deconvolve else delta)
+        if deconvolve:
+            field = torch.stack([_deconvolve(field[c], worder) for c in range(field.shape[0])])
+    if single:
+        field = field[0]
+    return (_back(x, field), _back(x, delta)) if return_delta else _back(x, field)
+
+
+def shot_noise(boxsize, count=None, weights=None):
+    """Poisson shot noise of a catalogue's power spectrum, on the host: L^3 / count, or L^3 sum(w^2) / sum(w)^2 with
+    weights.  A float, in the units of power_spectrum's P."""
+    L = _triple(boxsize, "boxsize", "a length")
+    vol = L[0] * L[1] * L[2]
+    if weights is not None:
+        w = weights.cpu().numpy() if _is_torch(weights) else np.asarray(weights)
+        w = w.astype(np.float64).ravel()
+        if w.size == 0 or not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0:
+            raise ValueError("shot_noise: weights must be finite, non-negative and not all zero")
+        return float(vol * np.sum(w * w) / np.sum(w) ** 2)
+    if isinstance(count, (bool, np.bool_)) or not isinstance(count, numbers.Integral) or int(count) < 1:
+        raise ValueError("shot_noise needs weights or a count >= 1, got %r" % (count,))
+    return float(vol / int(count))
+
+
+def correlation_arrays(k, p_aa, p_bb, p_ab, nmodes):
+    """cross_correlation's dict from the three spectra (host float64 arithmetic): r = p_ab / sqrt(p_aa p_bb),
+    transfer = sqrt(p_aa / p_bb), bias = p_ab / p_bb; NaN, without a warning, where a denominator is 0."""
+    k, p_aa, p_bb, p_ab, nmodes = (np.asarray(v, dtype=np.float64) for v in (k, p_aa, p_bb, p_ab, nmodes))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        den = np.sqrt(p_aa * p_bb)
+        r = np.where(den > 0, p_ab / den, np.nan)
+        transfer = np.where(p_bb > 0, np.sqrt(p_aa / p_bb), np.nan)
+        bias = np.where(p_bb > 0, p_ab / p_bb, np.nan)
+    return dict(k=k, p_aa=p_aa, p_bb=p_bb, p_ab=p_ab, nmodes=nmodes, r=r, transfer=transfer, bias=bias)
+
+
+def cross_correlation(a, b, boxsize=1000.0):
+    """Cross-correlation coefficient, transfer function and bias of two fields per shell (Pylians' Pk_library.XPk as the
+    reference uses it, scripts/utils.py:1451-1470 and scripts/test_upsampling.py:159-183: XPk / sqrt(Pk_a Pk_b) of the
+    emulated against the target field).
+
+    a, b: (n, n, n) float32, NumPy arrays or CUDA tensors on one device.  boxsize: L (scalar, or a 3-tuple of equal
+    values).  Returns a dict of float64 NumPy arrays of n // 2 shells: k, p_aa, p_bb, p_ab, nmodes -- bit for bit what
+    power_spectrum(a), power_spectrum(b) and power_spectrum(a, other=b) return, from one rfftn per field --, and
+    r = p_ab / sqrt(p_aa p_bb), transfer = sqrt(p_aa / p_bb), bias = p_ab / p_bb (NaN where a denominator is 0).  For
+    halos against matter (a = delta_h, b = delta_m) `bias` is the cross bias P_hm / P_mm; nothing is subtracted."""
+    if b is None:
+        raise ValueError("cross_correlation needs two fields, got b = None")
+    d, n, L, o = _validate_spectrum(a, boxsize, b, "cross_correlation", 4096)
+    dev = _device_of(d)
+    nb = n // 2 + 1
+    koff = np.arange(1, nb, dtype=np.float64)
+    with torch.cuda.device(dev):
+        fa, fb = _half_spectra(d, o, dev)
+        out = []
+        for x, y in ((fa, None), (fb, None), (fa, fb)):
+            binmax = torch.zeros(nb, dtype=torch.int32, device=dev)
+            sums = torch.zeros(3 * nb, dtype=torch.int64, device=dev)
+            _lib.check(_lib.lib().nbe_power_spectrum(_ptr(x), _ptr_or_null(y), n, _ptr(binmax), _ptr(sums), _stream(dev)))
+            sm = sums.cpu().numpy().reshape(3, nb)[:, 1:]
+            out.append(_shell_means(binmax.cpu().numpy()[1:], sm[0], sm[1], sm[2], koff, _KEXP, L, n))
+    return correlation_arrays(out[0][0], out[0][1], out[1][1], out[2][1], out[0][2])
 
 
 def rsd_factor(z, Om):

@@ -10,8 +10,10 @@ Here the displacement stays where `process_box` left it:
     m = particle_mass(0.3175, 1000.0, 512)
     hmf = halo_mass_function(cat["Length"], 1000.0, m, np.linspace(12.5, 15.5, 31))
     slab, ncells = density_slab(delta, 1000.0, axis=0, center=500.0, width=20.0)
+    delta_h, info = paint_halos(cat, 1000.0, res=512, min_length=100)               # the halo density contrast
+    hb = halo_bias(cat, delta_m, 1000.0, min_length=100)                            # P_hh, P_mm, P_hm, r(k), bias, shot noise
 
-    python -m jax_nbody_emulator_with_dj_amd.halos --displacement_file emu_dis.npy --output_dir out/
+    python -m jax_nbody_emulator_with_dj_amd.halos --displacement_file emu_dis.npy --output_dir out/ [--halo_pk 256]
 
 Definition (DESIGN.md section 12.5 has the proofs; tests/fof_ref.py restates it in NumPy).  With U = 2^30, particle
 p = (i0 n + i1) n + i2 of the (n, n, n) lattice has the integer coordinates X_c = rint((i_c / n + psi_c / L) U) mod U,
@@ -50,7 +52,7 @@ try:
 except Exception:  # pragma: no cover
     torch = None
 
-__all__ = ["fof_halos", "particle_mass", "halo_mass_function", "density_slab"]
+__all__ = ["fof_halos", "particle_mass", "halo_mass_function", "density_slab", "paint_halos", "halo_bias"]
 
 _U = 1 << 30                    # include/nbe.h, "Halos": coordinate units per box side
 _MIN_N, _MAX_N = 2, 1024        # NBE_FOF_MIN_N, NBE_FOF_MAX_N
@@ -281,6 +283,98 @@ def density_slab(delta, boxsize, axis, center, width):
     return np.take(delta, planes, axis=axis).astype(np.float32).mean(axis=axis).astype(np.float32), int(planes.size)
 
 
+# ---- halo fields ----------------------------------------------------------------------------
+
+_HALO_WEIGHTS = (None, "Length")
+
+
+def _select_halos(cat, weight, min_length, max_length, redshift_space):
+    """(rows mask or None for all, count) of a paint_halos call, validated."""
+    if not isinstance(cat, dict) or "CMPosition" not in cat or "Length" not in cat:
+        raise ValueError("paint_halos needs fof_halos's dict (CMPosition, Length), got %s" % type(cat).__name__)
+    if weight not in _HALO_WEIGHTS:
+        raise ValueError("paint_halos: weight must be None (number-weighted) or 'Length', got %r" % (weight,))
+    if redshift_space and "CMVelocity" not in cat:
+        raise ValueError("paint_halos: redshift_space needs a catalogue with CMVelocity (fof_halos(..., velocity=v))")
+    for name, v in (("min_length", min_length), ("max_length", max_length)):
+        if v is not None and (isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Real) or not v == v):
+            raise ValueError("paint_halos: %s must be a number or None, got %r" % (name, v))
+    length = cat["Length"]
+    keep = None
+    if min_length is not None:
+        keep = length >= min_length
+    if max_length is not None:
+        keep = (length <= max_length) if keep is None else keep & (length <= max_length)
+    count = int(length.shape[0]) if keep is None else int(keep.sum())
+    if count == 0:
+        raise ValueError("paint_halos: no halo is left by the selection (%d in the catalogue, min_length %r, max_length %r)"
+                         % (int(length.shape[0]), min_length, max_length))
+    return keep, count
+
+
+def paint_halos(cat, boxsize, res=512, worder=2, deconvolve=True, weight=None, min_length=None, max_length=None,
+                redshift_space=False, los=2, velocity_to_length=None):
+    """The density contrast of a halo catalogue (density.paint_particles of fof_halos's CMPosition; nbodykit's
+    catalogue-to-mesh step on the reference's fof_catalog).
+
+    cat: fof_halos's dict, NumPy arrays or CUDA tensors.  min_length, max_length: keep the halos with min_length <= Length
+    <= max_length (None: no bound).  weight: None counts halos, "Length" weights each by its particle count (its mass).
+    redshift_space: move every halo by velocity_to_length * CMVelocity[:, los] along array axis los first (rsd_factor(z,
+    Om) for velocity_to_length; the catalogue needs fof_halos(..., velocity=v)).  boxsize, res, worder, deconvolve: as
+    paint_particles.  Returns (delta_h, info): delta_h float32 of shape res in the catalogue's kind, info = {"count": the
+    halos painted, "shot_noise": density.shot_noise of them (L^3 / count, or L^3 sum(w^2) / sum(w)^2 Length-weighted)}.
+    A selection that leaves no halo raises ValueError."""
+    from .density import paint_particles, shot_noise
+    keep, count = _select_halos(cat, weight, min_length, max_length, redshift_space)
+    rows = (lambda a: a) if keep is None else (lambda a: a[keep])
+    pos, length = rows(cat["CMPosition"]), rows(cat["Length"])
+    w = None
+    if weight == "Length":
+        w = length.to(torch.float64) if _is_torch(length) else np.asarray(length, dtype=np.float64)
+    vel = rows(cat["CMVelocity"]) if redshift_space else None
+    if redshift_space and velocity_to_length is None:
+        raise ValueError("velocity_to_length is required with redshift_space (rsd_factor(z, Om))")
+    delta = paint_particles(pos, boxsize=boxsize, res=res, worder=worder, deconvolve=deconvolve, weights=w, velocity=vel,
+                            los=los, velocity_to_length=velocity_to_length if redshift_space else None)
+    return delta, {"count": count, "shot_noise": shot_noise(boxsize, count=count, weights=w)}
+
+
+def halo_bias(cat, delta_m, boxsize, **kwargs):
+    """Halo auto spectrum, halo-matter cross spectrum, r(k) and bias: paint_halos(cat, boxsize, res=n, **kwargs) on the mesh
+    of the (n, n, n) float32 matter field delta_m, then density.cross_correlation(delta_h, delta_m).  Returns that dict
+    (a = halos, b = matter: bias = P_hm / P_mm) with shot_noise and count added.  Nothing is subtracted for the caller:
+    p_aa still holds the shot noise."""
+    from .density import cross_correlation
+    if "res" in kwargs:
+        raise ValueError("halo_bias takes the mesh size from delta_m")
+    if not hasattr(delta_m, "shape") or len(delta_m.shape) != 3:
+        raise ValueError("halo_bias needs a cubic (n, n, n) matter field")
+    delta_h, info = paint_halos(cat, boxsize, res=int(delta_m.shape[0]), **kwargs)
+    out = cross_correlation(delta_h, delta_m, boxsize=boxsize)
+    out.update(shot_noise=info["shot_noise"], count=info["count"])
+    return out
+
+
+HALO_DELTA_FILE, HALO_PK_FILE = "halo_delta.npy", "halo_pk.npz"
+HALO_WEIGHT_NAMES = {"number": None, "length": "Length"}
+
+
+def halo_spectra(cat, disp, boxsize, res, worder=2, weight=None):
+    """The arrays of halo_delta.npy and halo_pk.npz for a catalogue and the displacement it was found in: the matter field
+    is paint_density(disp, boxsize, res, worder), the halos are painted onto the same mesh with the same order.  Returns
+    (delta_h as a NumPy array, dict with k, p_hh, p_mm, p_hm, r, bias, nmodes, shot_noise, count), or None for a
+    catalogue without a halo."""
+    from .density import cross_correlation, paint_density
+    if int(cat["Length"].shape[0]) == 0:
+        return None
+    delta_m = paint_density(disp, boxsize=boxsize, res=res, worder=worder)
+    delta_h, info = paint_halos(cat, boxsize, res=res, worder=worder, weight=weight)
+    cc = cross_correlation(delta_h, delta_m, boxsize=boxsize)
+    host = delta_h.cpu().numpy() if _is_torch(delta_h) else delta_h
+    return host, dict(k=cc["k"], p_hh=cc["p_aa"], p_mm=cc["p_bb"], p_hm=cc["p_ab"], r=cc["r"], bias=cc["bias"],
+                      nmodes=cc["nmodes"], shot_noise=np.float64(info["shot_noise"]), count=np.int64(info["count"]))
+
+
 # ---- drivers -----------------------------------------------------------------------------------------------------------
 
 CATALOG_FILE = "fof_catalog.npz"
@@ -315,7 +409,23 @@ def build_parser():
     ap.add_argument("--nmin", type=int, default=20, help="smallest particle count of a halo")
     ap.add_argument("--catalog-file", default=CATALOG_FILE, dest="catalog_file",
                     help="name of the catalogue inside --output_dir (default: %s)" % CATALOG_FILE)
+    ap.add_argument("--halo_pk", type=int, default=None, metavar="RES",
+                    help="also paint the halos and the matter onto a RES^3 mesh: %s and %s (k, p_hh, p_mm, p_hm, r, bias, "
+                         "nmodes, shot_noise, count) inside --output_dir" % (HALO_DELTA_FILE, HALO_PK_FILE))
+    ap.add_argument("--mas_worder", type=int, choices=(1, 2, 3, 4), default=2,
+                    help="with --halo_pk: 1 NGP, 2 CIC, 3 TSC, 4 PCS (default: 2)")
+    ap.add_argument("--halo_weight", choices=sorted(HALO_WEIGHT_NAMES), default="number",
+                    help="with --halo_pk: count halos, or weight each by its particle count (default: number)")
     return ap
+
+
+def save_halo_spectra(out_dir, spectra):
+    """Write halo_delta.npy and halo_pk.npz, or print the one line that says why not (halo_spectra's None)."""
+    if spectra is None:
+        print("no halo in the catalogue: %s and %s are not written" % (HALO_DELTA_FILE, HALO_PK_FILE))
+        return
+    np.save(os.path.join(str(out_dir), HALO_DELTA_FILE), spectra[0])
+    np.savez(os.path.join(str(out_dir), HALO_PK_FILE), **spectra[1])
 
 
 def load_displacement(path):
@@ -334,6 +444,8 @@ def load_displacement(path):
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
+    if a.halo_pk is not None and a.halo_pk < 1:
+        sys.exit("--halo_pk must be >= 1, got %d" % a.halo_pk)
     disp = load_displacement(a.displacement_file)
     try:
         cat = fof_halos(disp, boxsize=a.boxsize, linking_length=a.linking_length, nmin=a.nmin, absolute=a.absolute_linking)
@@ -345,6 +457,9 @@ def main(argv=None):
                                                a.absolute_linking, a.nmin))
     print("%d halos of %d groups (linking length %g) -> %s" % (len(cat["Length"]), cat["ngroups"], cat["linking_length"],
                                                                path))
+    if a.halo_pk is not None:
+        save_halo_spectra(a.output_dir, halo_spectra(cat, disp, a.boxsize, a.halo_pk, a.mas_worder,
+                                                     HALO_WEIGHT_NAMES[a.halo_weight]))
 
 
 if __name__ == "__main__":

@@ -39,7 +39,13 @@ Halos (the fork's scripts/halos.py): `--fof` writes <output_dir>/fof_catalog.npz
 emulated displacement (halos.fof_halos on the device tensor, no host copy of the field; the reference's keys CMPosition,
 Npart, Mass, BoxSize, NpartPerDim, LinkingLength, AbsoluteLinking, Nmin).  `--fof_linking_length B` (default 0.2, in units
 of the mean particle spacing) and `--fof_nmin N` (default 20) set the finder; the box size is `--boxsize` and Omega_m the
-cosmology file's.  It needs a cubic box and works with or without --density_res.
+cosmology file's.  It needs a cubic box and works with or without --density_res.  With `--fof`, `--halo_pk RES` paints the
+halos (halos.paint_halos; `--halo_weight number|length`) and the matter (density.paint_density of the same displacement,
+`--mas_worder`) onto one RES^3 mesh and writes <output_dir>/halo_delta.npy and <output_dir>/halo_pk.npz (k, p_hh, p_mm,
+p_hm, r, bias, nmodes, shot_noise, count: density.cross_correlation of the two fields); a box without a halo writes
+neither and says so.  `--xcorr FILE` (with --density_res) writes <output_dir>/emu_xcorr.npz, density.cross_correlation of
+emu_delta against the saved (N, N, N) field FILE (k, p_aa, p_bb, p_ab, nmodes, r, transfer, bias): the reference's
+emulator-against-target check (scripts/utils.py:1451-1470).
 
 What differs from the reference: the engine, its weights and its ~100 GB workspace stay resident on the
 GPU for the whole batch, and disk I/O overlaps compute -- the next displacement file is read and the
@@ -208,6 +214,14 @@ def build_parser():
                     help='With --fof: linking length in units of the mean particle spacing (default: 0.2)')
     ap.add_argument('--fof_nmin', type=int, default=argparse.SUPPRESS,
                     help='With --fof: smallest particle count of a halo (default: 20)')
+    ap.add_argument('--halo_pk', type=mesh_size, metavar='RES', default=argparse.SUPPRESS,
+                    help='With --fof: also write the halo density on a RES^3 mesh to <output_dir>/halo_delta.npy and its '
+                         'spectra against the matter field to <output_dir>/halo_pk.npz')
+    ap.add_argument('--halo_weight', choices=('number', 'length'), default=argparse.SUPPRESS,
+                    help='With --halo_pk: count halos, or weight each by its particle count (default: number)')
+    ap.add_argument('--xcorr', type=Path, metavar='FILE', default=argparse.SUPPRESS,
+                    help='With --density_res: also write r(k), transfer and bias of emu_delta against the saved (N, N, N) '
+                         'float32 field FILE to <output_dir>/emu_xcorr.npz')
     return ap
 
 
@@ -329,11 +343,44 @@ def fof_options(args):
     return dict(boxsize=boxsize, linking_length=b, nmin=nmin)
 
 
-def fof_catalog(disp, fof, Om):
-    """The arrays of fof_catalog.npz for the device displacement of one box."""
-    from .halos import catalog_arrays, fof_halos
+def halo_options(args):
+    """The settings of --halo_pk, or None without it (read apart from fof_options, whose dict they leave as it was)."""
+    res = getattr(args, 'halo_pk', None)
+    if res is None:
+        if getattr(args, 'halo_weight', None) is not None:
+            _die('--halo_weight needs --halo_pk')
+        return None
+    if not getattr(args, 'fof', False):
+        _die('--halo_pk needs --fof')
+    from .halos import HALO_WEIGHT_NAMES
+    return dict(res=int(res), worder=int(getattr(args, 'mas_worder', 2)),
+                weight=HALO_WEIGHT_NAMES[getattr(args, 'halo_weight', 'number')])
+
+
+def xcorr_option(args):
+    """The (N, N, N) float32 field of --xcorr, or None without it.  It needs --density_res and that mesh size."""
+    path = getattr(args, 'xcorr', None)
+    if path is None:
+        return None
+    res = getattr(args, 'density_res', None)
+    if res is None:
+        _die('--xcorr needs --density_res')
+    _check_file(path)
+    field = np.load(path)
+    if field.shape != (res,) * 3:
+        _die(f'--xcorr: {path} has shape {field.shape}, expected {(res,) * 3}')
+    return np.ascontiguousarray(field, dtype=np.float32)
+
+
+def fof_catalog(disp, fof, Om, halo=None):
+    """The arrays of fof_catalog.npz for the device displacement of one box, as {'fof': arrays}; with the settings of
+    --halo_pk also 'halo': halos.halo_spectra's result (None for a box without a halo)."""
+    from .halos import catalog_arrays, fof_halos, halo_spectra
     cat = fof_halos(disp, boxsize=fof['boxsize'], linking_length=fof['linking_length'], nmin=fof['nmin'])
-    return catalog_arrays(cat, int(disp.shape[1]), fof['boxsize'], Om, fof['linking_length'], False, fof['nmin'])
+    out = {'fof': catalog_arrays(cat, int(disp.shape[1]), fof['boxsize'], Om, fof['linking_length'], False, fof['nmin'])}
+    if halo is not None:
+        out['halo'] = halo_spectra(cat, disp, fof['boxsize'], halo['res'], halo['worder'], halo['weight'])
+    return out
 
 
 def density_summaries(delta, dens, bispec, onepoint):
@@ -388,6 +435,8 @@ def run(args):
     paint_vel, rsd = velocity_options(args)
     multipoles, wedges = anisotropy_options(args)
     fof = fof_options(args)
+    halo = halo_options(args)
+    target = xcorr_option(args)
     if bispec:
         for k1, k2 in BISPECTRUM_CONFIGS:                    # density.bispectrum's closure condition, before any work
             if 2.0 * (k1 + k2) * dens['boxsize'] / (2.0 * np.pi) + 1.5 >= dens['res']:
@@ -400,7 +449,8 @@ def run(args):
               + (", velocity mesh" if paint_vel else "") + (f", redshift space along axis {rsd}" if rsd is not None else "")
               + (", multipoles" if multipoles else "") + (f", {wedges} wedges" if wedges is not None else ""))
     if fof is not None:
-        print(f"  Halos: FoF b = {fof['linking_length']}, nmin {fof['nmin']}, boxsize {fof['boxsize']}")
+        print(f"  Halos: FoF b = {fof['linking_length']}, nmin {fof['nmin']}, boxsize {fof['boxsize']}"
+              + (f", halo spectra on a {halo['res']}^3 mesh" if halo is not None else ""))
     print()
 
     shape = None
@@ -436,6 +486,9 @@ def run(args):
             np.save(out_dir / 'emu_dis.npy', result)
         if extra is not None and 'fof' in extra:
             np.savez_compressed(out_dir / 'fof_catalog.npz', **extra['fof'])
+        if extra is not None and 'halo' in extra:
+            from .halos import save_halo_spectra
+            save_halo_spectra(out_dir, extra['halo'])
         if extra is not None and 'delta' in extra:
             np.save(out_dir / 'emu_delta.npy', extra['delta'])
             if 'pk' in extra:
@@ -460,6 +513,8 @@ def run(args):
                 np.savez(out_dir / 'emu_pk_rsd_multipoles.npz', **extra['pk_rsd_multipoles'])
             if 'pk_rsd_wedges' in extra:
                 np.savez(out_dir / 'emu_pk_rsd_wedges.npz', **extra['pk_rsd_wedges'])
+            if 'xcorr' in extra:
+                np.savez(out_dir / 'emu_xcorr.npz', **extra['xcorr'])
 
     def with_density(dis_in, z, Om):
         """process_box on the device, the density field of its float32 displacement, host copies of the fields."""
@@ -468,7 +523,7 @@ def run(args):
         box_t = torch.from_numpy(np.ascontiguousarray(dis_in)).to('cuda')
         result = emu.process_box(box_t, z=z, Om=Om, show_progress=not args.quiet)
         disp = result[0] if args.vel else result
-        extra = {} if fof is None else {'fof': fof_catalog(disp, fof, Om)}
+        extra = {} if fof is None else fof_catalog(disp, fof, Om, halo)
         out_dt = np.dtype(args.output_precision)
         if dens is None:
             host = tuple(t.cpu().numpy().astype(out_dt, copy=False) for t in (result if args.vel else (result,)))
@@ -478,6 +533,9 @@ def run(args):
         extra['delta'] = delta.cpu().numpy()
         if dens['pk']:
             extra['pk'] = power_spectrum(delta, boxsize=dens['boxsize'])
+        if target is not None:
+            from .density import cross_correlation
+            extra['xcorr'] = cross_correlation(delta, torch.from_numpy(target).to(delta.device), boxsize=dens['boxsize'])
         if mink:
             extra['mf'] = minkowski_functionals(delta, boxsize=dens['boxsize'])
         if bispec or onepoint:
