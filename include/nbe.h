@@ -465,6 +465,49 @@ int nbe_fof_catalog(const void* coords, const void* parent, const void* slot, co
                     const int exponents[3], int64_t count, int wave_reduce, int max_blocks, void* sums, void* labels,
                     void* stream);
 
+/* ---- Pairs (no context) ------------------------------------------------------------------------------
+ * Pair counts of periodic catalogues and the histogram behind xi(r), xi(s, mu) and its multipoles (DESIGN.md section
+ * 12.7).  Pointers, `stream` and asynchrony as for "Density"; coordinates, the minimum-image difference d_c, cells and keys
+ * as for "Halos", in a cubic periodic box of side L with U = 2^30 units.  A catalogue is (count, 3) positions, any number of
+ * boxes away, with X_c = rint((x_c / L) 2^30) mod 2^30 formed in float64 (nbe_pair_coords), or a displaced lattice with the
+ * coordinates of nbe_fof_cells.  q = d_0^2 + d_1^2 + d_2^2 in 64-bit integers, always below 2^60.  Radial bins: thresholds
+ * T_0 < T_1 < ... < T_nbins, T_b = floor((r_b / L)^2 2^60) (T_0 = -1 for r_0 = 0), and a pair is in bin b iff
+ * T_b < q <= T_{b+1}: (r_b, r_{b+1}] on the rounded coordinates, "<= T" being the FoF link rule, so that the auto count
+ * for the edges [0, l] is the number of FoF links at linking length l.  mu bins: nmu uniform bins of mu = |d_los| / |d| over
+ * [0, 1] about axis los; for q > 0, m = #{ j in 1 .. nmu - 1 : d_los^2 nmu^2 >= j^2 q }, compared as 128-bit products, and
+ * m = 0 for q = 0.  An auto count takes each unordered pair {i, j}, i != j, once; a cross count takes every (i in A, j in
+ * B), rows that coincide included (q = 0: in the first bin only if T_0 = -1).  Cells: 3 <= ncell <= NBE_FOF_MAX_CELLS with
+ * ncell (isqrt(T_nbins) + 1) <= 2^30, so that a counted pair shares a cell or sits in adjacent ones; the cells are found by
+ * binary search in the sorted keys, and memory stays O(particles).  Counts are integer sums: the same bits for every launch
+ * geometry, sort order of ties and stream.  The calls, per catalogue: nbe_pair_coords or nbe_fof_cells, the caller's sort
+ * of `keys`, nbe_fof_gather; then nbe_pair_count. */
+#define NBE_PAIR_MAX_BINS 128
+#define NBE_PAIR_MAX_MU 32
+#define NBE_PAIR_MAX_IMAGE 4096      /* nbins nmu 64-bit counters: a 32 KiB image in LDS */
+#define NBE_PAIR_FORM 2               /* nbe_pair_count's form of nbe_pair_count_form: measured fastest (section 12.7) */
+/* replaces the positions-to-cells step of Corrfunc's theory.DD / theory.DDsmu (the gridlink of its periodic box) and of
+ * nbodykit's SimulationBox2PCF: pos = (count, 3) row-major, float32 or float64 (pos_dtype NBE_F32 / NBE_F64); coords =
+ * (3, count) int32 receives X; keys = count int64 the cell keys; stats = 1 int32, zeroed by the caller, counts the rows with
+ * a non-finite position or |x_c / L| >= 2^20 (their X and key are 0: the caller must not go on). */
+int nbe_pair_coords(const void* pos, int pos_dtype, int64_t count, double boxsize, int ncell, int max_blocks, void* coords,
+                    void* keys, void* stats, void* stream);
+/* replaces the pair loop of Corrfunc's theory.DD (nmu = 1) and theory.DDsmu (nmu > 1), and the counting step of nbodykit's
+ * SimulationBox2PCF: sortedA / keysA = nbe_fof_gather's records and the sorted keys of catalogue A, countA rows; sortedB /
+ * keysB / countB those of B, or sortedB = keysB = NULL for the auto count of A.  thresholds = nbins + 1 int64 on the HOST,
+ * strictly increasing from -1 or more; 1 <= nbins <= NBE_PAIR_MAX_BINS, 1 <= nmu <= NBE_PAIR_MAX_MU, nbins nmu <=
+ * NBE_PAIR_MAX_IMAGE, los in 0 .. 2.  counts = (nbins, nmu) uint64, zeroed by the caller, receives the pairs.  A pair is
+ * rejected on |d_c| > isqrt(T_nbins) in 32 bits, binned by a search of the thresholds, added into a per-workgroup LDS image
+ * and flushed once with 64-bit atomics.  One thread per row of A walks its cells of B (FoF's decomposition). */
+int nbe_pair_count(const void* sortedA, const void* keysA, int64_t countA, const void* sortedB, const void* keysB,
+                   int64_t countB, int ncell, const int64_t* thresholds, int nbins, int nmu, int los, int max_blocks,
+                   void* counts, void* stream);
+/* nbe_pair_count with its two choices made by the caller (tools/time_pairs.py and the tests; the counts are the same bits):
+ * form bit 0 adds the equal bins of a wave once instead of one LDS atomic per lane, bit 1 takes one thread per row of A
+ * (FoF's decomposition) instead of a workgroup per run of one cell with B in LDS tiles; 0 .. 3. */
+int nbe_pair_count_form(const void* sortedA, const void* keysA, int64_t countA, const void* sortedB, const void* keysB,
+                        int64_t countB, int ncell, const int64_t* thresholds, int nbins, int nmu, int los, int max_blocks,
+                        int form, void* counts, void* stream);
+
 /* ---- Input fields (no context)---------------------------------------------------------------------
  * The reference's pipeline brings a linear density field to the particle grid (resize_density_grid) and turns it into
  * the first-order LPT displacement before process_box (scripts/core.py:302-409).  These are the passes between the

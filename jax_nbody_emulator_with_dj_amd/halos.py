@@ -12,8 +12,10 @@ Here the displacement stays where `process_box` left it:
     slab, ncells = density_slab(delta, 1000.0, axis=0, center=500.0, width=20.0)
     delta_h, info = paint_halos(cat, 1000.0, res=512, min_length=100)               # the halo density contrast
     hb = halo_bias(cat, delta_m, 1000.0, min_length=100)                            # P_hh, P_mm, P_hm, r(k), bias, shot noise
+    xi = halo_correlation(cat, 1000.0, np.linspace(1.0, 50.0, 21), min_length=100)  # xi_hh(r) by pair counts; matter=: xi_hm
 
     python -m jax_nbody_emulator_with_dj_amd.halos --displacement_file emu_dis.npy --output_dir out/ [--halo_pk 256]
+        [--halo_xi [--xi_rmin 1 --xi_rmax 50 --xi_nbins 20 --xi_log] [--xi_nmu N]]
 
 Definition (DESIGN.md section 12.5 has the proofs; tests/fof_ref.py restates it in NumPy).  With U = 2^30, particle
 p = (i0 n + i1) n + i2 of the (n, n, n) lattice has the integer coordinates X_c = rint((i_c / n + psi_c / L) U) mod U,
@@ -44,7 +46,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import NBEError
-from .density import (_back, _check_array, _device_of, _dtype_name, _is_torch, _ptr, _real, _same_kind, _stream,
+from .density import (_back, _check_array, _check_los, _device_of, _dtype_name, _is_torch, _ptr, _real, _same_kind, _stream,
                       _to_device, _triple)
 
 try:
@@ -52,7 +54,8 @@ try:
 except Exception:  # pragma: no cover
     torch = None
 
-__all__ = ["fof_halos", "particle_mass", "halo_mass_function", "density_slab", "paint_halos", "halo_bias"]
+__all__ = ["fof_halos", "particle_mass", "halo_mass_function", "density_slab", "paint_halos", "halo_bias",
+           "halo_correlation"]
 
 _U = 1 << 30                    # include/nbe.h, "Halos": coordinate units per box side
 _MIN_N, _MAX_N = 2, 1024        # NBE_FOF_MIN_N, NBE_FOF_MAX_N
@@ -355,7 +358,33 @@ def halo_bias(cat, delta_m, boxsize, **kwargs):
     return out
 
 
-HALO_DELTA_FILE, HALO_PK_FILE = "halo_delta.npy", "halo_pk.npz"
+def halo_correlation(cat, boxsize, r_edges, matter=None, min_length=None, max_length=None, redshift_space=None, los=2,
+                     velocity_to_length=None, nmu=None):
+    """The two-point function of a halo catalogue by pair counts (correlation.correlation_function of fof_halos's
+    CMPosition; Corrfunc's theory.DD / DDsmu, nbodykit's SimulationBox2PCF on the reference's fof_catalog): the auto
+    function xi_hh, or with `matter` -- (count, 3) positions or a (3, n, n, n) displacement of the catalogue's kind -- the
+    cross function xi_hm.
+
+    cat, min_length, max_length, redshift_space, los, velocity_to_length: the halos and their selection as paint_halos (a
+    true redshift_space moves every halo by velocity_to_length * CMVelocity[:, los] along array axis los first).  r_edges,
+    nmu: as correlation.pair_counts; los is also the axis of the mu bins.  Returns correlation_function's dict (npairs, rr,
+    xi, r_mid, ..., with nmu xi0, xi2, xi4) with count, the halos selected, added."""
+    from .correlation import correlation_function
+    keep, count = _select_halos(cat, None, min_length, max_length, redshift_space)
+    pos = cat["CMPosition"] if keep is None else cat["CMPosition"][keep]
+    if redshift_space:
+        if velocity_to_length is None:
+            raise ValueError("velocity_to_length is required with redshift_space (rsd_factor(z, Om))")
+        los = _check_los(los)
+        vel = cat["CMVelocity"] if keep is None else cat["CMVelocity"][keep]
+        pos = pos.clone() if _is_torch(pos) else np.array(pos, dtype=np.float64)
+        pos[:, los] += _real(velocity_to_length, "velocity_to_length") * vel[:, los]
+    out = correlation_function(pos, boxsize, r_edges, b=matter, nmu=nmu, los=los)
+    out["count"] = count
+    return out
+
+
+HALO_DELTA_FILE, HALO_PK_FILE, HALO_XI_FILE = "halo_delta.npy", "halo_pk.npz", "halo_xi.npz"
 HALO_WEIGHT_NAMES = {"number": None, "length": "Length"}
 
 
@@ -373,6 +402,38 @@ def halo_spectra(cat, disp, boxsize, res, worder=2, weight=None):
     host = delta_h.cpu().numpy() if _is_torch(delta_h) else delta_h
     return host, dict(k=cc["k"], p_hh=cc["p_aa"], p_mm=cc["p_bb"], p_hm=cc["p_ab"], r=cc["r"], bias=cc["bias"],
                       nmodes=cc["nmodes"], shot_noise=np.float64(info["shot_noise"]), count=np.int64(info["count"]))
+
+
+def xi_edges(rmin=1.0, rmax=50.0, nbins=20, log=False):
+    """The nbins + 1 edges of --halo_xi: linear from rmin to rmax, or logarithmic with --xi_log (rmin > 0)."""
+    if not (np.isfinite(rmin) and np.isfinite(rmax)) or rmin < 0.0 or not rmax > rmin or nbins < 1:
+        raise ValueError("--halo_xi needs 0 <= xi_rmin < xi_rmax and xi_nbins >= 1, got %r, %r, %r" % (rmin, rmax, nbins))
+    if log:
+        if not rmin > 0.0:
+            raise ValueError("--xi_log needs xi_rmin > 0, got %r" % (rmin,))
+        return np.geomspace(rmin, rmax, nbins + 1)
+    return np.linspace(rmin, rmax, nbins + 1)
+
+
+def halo_xi_arrays(cat, boxsize, r_edges, nmu=None, los=2):
+    """The arrays of halo_xi.npz: r_edges, r_mid, npairs, rr, xi, count, and with nmu mu_edges, xi0, xi2, xi4 -- or None
+    for a catalogue without a halo."""
+    if int(cat["Length"].shape[0]) == 0:
+        return None
+    out = halo_correlation(cat, boxsize, r_edges, nmu=nmu, los=los)
+    to_np = lambda a: a.cpu().numpy() if _is_torch(a) else np.asarray(a)
+    names = ("r_edges", "r_mid", "npairs", "rr", "xi") + (("mu_edges", "xi0", "xi2", "xi4") if nmu is not None else ())
+    arrs = {k: to_np(out[k]) for k in names}
+    arrs["count"] = np.int64(out["count"])
+    return arrs
+
+
+def save_halo_xi(out_dir, arrs):
+    """Write halo_xi.npz, or print the one line that says why not (halo_xi_arrays's None)."""
+    if arrs is None:
+        print("no halo in the catalogue: %s is not written" % HALO_XI_FILE)
+        return
+    np.savez(os.path.join(str(out_dir), HALO_XI_FILE), **arrs)
 
 
 # ---- drivers -----------------------------------------------------------------------------------------------------------
@@ -416,7 +477,47 @@ def build_parser():
                     help="with --halo_pk: 1 NGP, 2 CIC, 3 TSC, 4 PCS (default: 2)")
     ap.add_argument("--halo_weight", choices=sorted(HALO_WEIGHT_NAMES), default="number",
                     help="with --halo_pk: count halos, or weight each by its particle count (default: number)")
+    add_xi_arguments(ap)
     return ap
+
+
+def add_xi_arguments(ap, suppress=False):
+    """The options of --halo_xi, shared with run_emulator (whose parser leaves an option that was not given out of the
+    namespace: suppress)."""
+    flag, value = (argparse.SUPPRESS, argparse.SUPPRESS) if suppress else (False, None)
+    ap.add_argument("--halo_xi", action="store_true", default=flag,
+                    help="also count the halo pairs: %s (r_edges, r_mid, npairs, rr, xi, count; with --xi_nmu also mu_edges, "
+                         "xi0, xi2, xi4) inside the output directory" % HALO_XI_FILE)
+    ap.add_argument("--xi_rmin", type=float, default=value, help="with --halo_xi: smallest edge in Mpc/h (default: 1)")
+    ap.add_argument("--xi_rmax", type=float, default=value,
+                    help="with --halo_xi: largest edge in Mpc/h, below boxsize / 3 (default: 50)")
+    ap.add_argument("--xi_nbins", type=int, default=value, help="with --halo_xi: number of bins, 1 .. 128 (default: 20)")
+    ap.add_argument("--xi_log", action="store_true", default=flag, help="with --halo_xi: logarithmic bins")
+    ap.add_argument("--xi_nmu", type=int, default=value, metavar="N",
+                    help="with --halo_xi: N uniform mu bins about axis 2 and the multipoles xi0, xi2, xi4")
+
+
+def xi_options(args, boxsize, die):
+    """The settings of --halo_xi of a parsed command line as a dict (r_edges, nmu), or None without it; `die(message)` for
+    an option without --halo_xi and for edges or mu bins that pair_counts would refuse."""
+    from .correlation import MAX_IMAGE, MAX_MU, pair_geometry
+    given = [n for n in ("xi_rmin", "xi_rmax", "xi_nbins", "xi_nmu") if getattr(args, n, None) is not None]
+    if getattr(args, "xi_log", False):
+        given.append("xi_log")
+    if not getattr(args, "halo_xi", False):
+        if given:
+            die("--%s needs --halo_xi" % given[0])
+        return None
+    get = lambda n, d: d if getattr(args, n, None) is None else getattr(args, n)
+    nmu = getattr(args, "xi_nmu", None)
+    try:
+        edges = xi_edges(get("xi_rmin", 1.0), get("xi_rmax", 50.0), get("xi_nbins", 20), bool(getattr(args, "xi_log", False)))
+        pair_geometry(boxsize, edges)
+        if nmu is not None and (not 1 <= nmu <= MAX_MU or nmu * (len(edges) - 1) > MAX_IMAGE):
+            raise ValueError("--xi_nmu must be in 1 .. %d with xi_nbins xi_nmu <= %d, got %d" % (MAX_MU, MAX_IMAGE, nmu))
+    except ValueError as e:
+        die(str(e))
+    return dict(r_edges=edges, nmu=nmu)
 
 
 def save_halo_spectra(out_dir, spectra):
@@ -446,6 +547,7 @@ def main(argv=None):
     a = build_parser().parse_args(argv)
     if a.halo_pk is not None and a.halo_pk < 1:
         sys.exit("--halo_pk must be >= 1, got %d" % a.halo_pk)
+    xi = xi_options(a, a.boxsize, sys.exit)
     disp = load_displacement(a.displacement_file)
     try:
         cat = fof_halos(disp, boxsize=a.boxsize, linking_length=a.linking_length, nmin=a.nmin, absolute=a.absolute_linking)
@@ -460,6 +562,8 @@ def main(argv=None):
     if a.halo_pk is not None:
         save_halo_spectra(a.output_dir, halo_spectra(cat, disp, a.boxsize, a.halo_pk, a.mas_worder,
                                                      HALO_WEIGHT_NAMES[a.halo_weight]))
+    if xi is not None:
+        save_halo_xi(a.output_dir, halo_xi_arrays(cat, a.boxsize, xi["r_edges"], xi["nmu"]))
 
 
 if __name__ == "__main__":
