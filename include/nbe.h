@@ -194,9 +194,12 @@ int nbe_process_region(nbe_ctx* ctx, const void* box, const int64_t box_size[3],
  * The four calls must follow each other on one context (any other call in between invalidates the brick and the next
  * brick call fails); all are asynchronous on the context's stream -- the caller orders the exchanges against it (events).
  * EVERY RANK MUST USE THE SAME RANGE SHIFT: call nbe_set_input_range with the box-wide max |x| first (the shim all-reduces
- * it).  Fields equal the single-device nbe_process_box of the whole box: bit for bit on the direct kernels (NBE_WINO=0) and
- * whenever slab starts pair the planes alike, else to float32 rounding (conv_h3w_kernel pairs planes from the first plane of
- * a launch).  b0 must be a multiple of 8, at least 48.  nbe_brick_plan returns the planes per z-slab the brick would run
+ * it).  Fields equal the single-device nbe_process_box of the whole box bit for bit, in every arithmetic and for any cut
+ * (tests/test_gpu_bricks.py).  conv_h3w_kernel takes a launch only when its plane count is even and pairs the planes from the
+ * first one: with b0 % 8 == 0 and origins % 8 == 0, levels 0 - 2 always launch even plane counts from even global planes --
+ * the z-slabs inside a brick (nbe_set_slab) included -- and conv_c at level 3, whose b0 / 8 + 6 and b0 / 8 + 4 planes from
+ * level-3 plane origin / 8 - 4 are even or odd with the cut, runs on the direct kernels in every call of the engine.
+ * b0 must be a multiple of 8, at least 48.  nbe_brick_plan returns the planes per z-slab the brick would run
  * with on the memory that is free now, or 0 when it does not fit (the caller then takes nbe_process_region). */
 int64_t nbe_brick_halo_bytes(nbe_ctx* ctx, const int64_t brick_size[3], int which);
 int nbe_brick_plan(nbe_ctx* ctx, const int64_t brick_size[3]);
@@ -224,7 +227,8 @@ int nbe_set_max_tile(nbe_ctx* ctx, int max_tile);
 int nbe_plan_tiles_ctx(nbe_ctx* ctx, const int64_t region[3], const int ndiv[3], int periodic_box, int out_ndiv[3]);
 /* Schedule of the two full-resolution levels of the U-Net inside a tile: whole tensors, or slabs of `slab` output
  * planes along z (even; the slab-sized tensors let a tile be as deep as the box: 512^3 runs as ONE tile).  Results are
- * identical.  -1 (default, or env NBE_SLAB): chosen with the tiling by the memory that is free; 0: never; S: always. */
+ * identical.  -1 (default, or env NBE_SLAB): chosen with the tiling by the memory that is free; 0: never; S: always
+ * (a brick plan that nbe_brick_plan / nbe_brick_encode cached under the previous setting is dropped). */
 int nbe_set_slab(nbe_ctx* ctx, int slab);
 /* Periodic-yx mode (default on, env NBE_PERIODIC=0 off): a tile of nbe_process_box that spans the periodic box in y
  * and x supplies the 48 voxels of y/x context of the two full-resolution levels layer by layer (1-voxel wrap-around

@@ -319,6 +319,7 @@ int nbe_set_precision(nbe_ctx* c, int prec) {
     if (prec != PREC_F32 && prec != PREC_F16X3 && prec != PREC_F16) return fail("precision must be NBE_PREC_F32 (0), NBE_PREC_F16X3 (1) or NBE_PREC_F16 (2)");
     if (c->have_weights && prec != c->prec)
         return fail("nbe_set_precision must be called before the weights are loaded (they are packed per precision)");
+    if (prec != c->prec) c->bp_slab = 0;                        // planes_for(mid, prec): another workspace layout, another brick plan
     c->prec = prec;
     return 0;
 }
@@ -333,6 +334,7 @@ int nbe_set_slab(nbe_ctx* c, int slab) {
     if (!c) return fail("null context");
     if (slab > 0 && (slab & 1)) return fail("slab must be even");
     c->slab_forced = slab < 0 ? -1 : slab;
+    c->bp_slab = 0;                                             // a cached brick plan was made under the previous setting
     return 0;
 }
 

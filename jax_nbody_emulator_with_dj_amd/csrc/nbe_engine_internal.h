@@ -192,6 +192,7 @@ struct nbe_ctx {
     // Winograd-z form of the gauged 3x3x3 layers (conv_h3w_kernel): packed beside pw.w for every gauged wide layer;
     // wino_ok is cleared when a weight of the current modulation leaves the f16 range at the kernel's 2^14 scale
     int* wino_flag = nullptr; bool wino_ok = false;
+    bool direct_z = false;                        // the block being scheduled takes the direct kernels (conv_c: lower_levels)
     // Range shift of the f16-based arithmetic (include/nbe.h, "Range"): activations and biases of a call are multiplied
     // by act_scale = 2^k (exact), the head divides it out.  flags[0]: bit pattern of max |input| (launch_absmax),
     // flags[1]: a non-finite value was written by the head.

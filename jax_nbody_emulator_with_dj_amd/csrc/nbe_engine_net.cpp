@@ -110,7 +110,7 @@ int run_conv(nbe_ctx* c, const Layer& L, const ConvLaunch& cl_in, bool has_dx) {
     // of output planes (the conditions of launch_h3w).  NBE_WINO=0 is the A/B switch (read per launch: tests flip it).
     // (the float16 model's form adds the residual in its epilogue: its blocks run their skips as launches of their own)
     cl.wino = (g6 || nov) && c->wino_ok && &pw == &L.pw && pw.ww && (!cl.skw || cl.skw->ww) && (c->prec == PREC_F16 || !(cl.flags & F_RES)) &&
-              (cl.Dv & 1) == 0 && cl.in_off == 0 && cl.osz == 1 && !wino_env_off();
+              (cl.Dv & 1) == 0 && cl.in_off == 0 && cl.osz == 1 && !c->direct_z && !wino_env_off();
     if (c->paths)
         *c->paths |= (cl.skw ? NBE_PATH_SKIP_FUSED : 0) | (cl.skw && (cl.flags & F_SKIP_NODX) ? NBE_PATH_SKIP_NODX : 0) |
                      (cl.csplit_ch ? NBE_PATH_TWO_SOURCE : 0) | (cl.skw && cl.sk_split_ch ? NBE_PATH_TWO_SOURCE_SKIP : 0) |
@@ -162,10 +162,10 @@ const Layer* find_layer(nbe_ctx* c, const char* block, const char* layer) {
 // (the float16 model: as displacement only -- the Winograd-z kernel is the one kernel with a fused skip)
 static bool wino_only_fuse(const nbe_ctx* c) { return !c->vel || c->prec == PREC_F16; }
 // Does the block of conv_1 layer L1 run its skip fused, on `nres` result planes?  (displacement only and float16: the fused
-// skip exists in conv_h3w_kernel alone, which pairs planes -- an odd number of result planes, the 5 planes of conv_c behind
-// a 104-voxel input, takes the unfused path; slabs always have an even number)
+// skip exists in conv_h3w_kernel alone, which pairs planes -- an odd number of result planes, and conv_c (direct_z), take
+// the unfused path; slabs always have an even number)
 bool block_fused(const nbe_ctx* c, const Layer* L1, int nres) {
-    return c->fuse && L1->fskip != nullptr && (!wino_only_fuse(c) || (!wino_env_off() && (nres & 1) == 0));
+    return c->fuse && L1->fskip != nullptr && (!wino_only_fuse(c) || (!c->direct_z && !wino_env_off() && (nres & 1) == 0));
 }
 
 // Can a fused decoder block read concat([skip, up]) from two tensors?  The kernels switch sources between whole K chunks: 16
@@ -491,7 +491,13 @@ static int lower_levels(nbe_ctx* c, Tensor t, Tensor cat1, Tensor* r_out) {
     if (downblock(c, "down_l2", y2, &t)) return 1;
     tfree(c, y2);
 
-    if (resblock(c, "conv_c", t, true, true, m, m, &r)) return 1;
+    // Level 3 runs on the direct kernels: its plane count (D / 8 - 2, - 4 for a tile of D planes) is even or odd with the cut
+    // of the box, and the Winograd-z kernel pairs planes -- a voxel's bits would depend on the tile or brick it falls in.
+    // (Levels 0 - 2 launch even plane counts from even planes for every tile and brick.)  0.1 % of the 512^3 box's kernel time.
+    c->direct_z = true;
+    const int rc = resblock(c, "conv_c", t, true, true, m, m, &r);
+    c->direct_z = false;
+    if (rc) return 1;
     tfree(c, t);
 
     if (upblock(c, "up_r2", r, cat2)) return 1;

@@ -71,6 +71,7 @@ void release_layer(Layer& L) {
 // ------------------------------------------------------------------------------------------------
 void free_layers(nbe_ctx* c) {
     drop_graphs(c); ++c->epoch;
+    c->bp_slab = 0;                                             // the workspace layout follows the layers (width, fused skips): plan the brick again
     for (auto& kv : c->layers) release_layer(kv.second);
     c->layers.clear();
     c->bias_scale = 1.f; c->bias_max = 0.f; c->bias_dirty = true;

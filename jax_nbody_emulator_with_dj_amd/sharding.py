@@ -230,7 +230,7 @@ class ShardedBox:
         self.nd_local = tuple(max(1, n // g) for n, g in zip(ndiv, self.grid))
         self.group = group
         self.comm_stream = comm_stream
-        self._halo = None                       # (send_lo, send_hi, recv_lo, recv_hi), allocated once
+        self._halo = {}                         # (device, the engine's three face sizes) -> its twelve exchange buffers, allocated once
         self.fallback = None                    # optional strict-float32 Engine with the same parameters (see process)
         self._agreed = False                    # the ranks have agreed on brick mode vs padded bricks (first call)
         self.trace = False                      # bracket the compute stream's waits for exchanges with timing events (wait_ms)
@@ -258,21 +258,41 @@ class ShardedBox:
         interior of conv_l1."""
         cur = torch.cuda.current_stream(brick.device) if brick.is_cuda else None
         H = exchange_halo(brick, self.grid, self.coords, RAW_HALO, self.group, pad_unsplit=False)     # raw input, 4 planes in z
-        if self._halo is None or self._halo[0].device != brick.device:
-            n = [self.eng.brick_halo_bytes(self.bshape, w) for w in (1, 2, 3)]
-            self._halo = tuple(torch.empty(k, dtype=torch.uint8, device=brick.device) for k in (n[0],) * 4 + (n[1],) * 4 + (n[2],) * 4)
-        s_lo, s_hi, r_lo, r_hi, s2_lo, s2_hi, r2_lo, r2_hi, k_lo, k_hi, q_lo, q_hi = self._halo
-        self.eng.brick_encode(H, self.bshape, Dz, vel_fac, s_lo, s_hi, k_lo, k_hi)
+        # a face is planes_for(mid, precision) * pstride * 16 bytes: the strict-float32 fallback of a float16 primary exchanges
+        # faces twice the size of the primary's, so every engine that runs here gets buffers of its own sizes
+        n = tuple(self.eng.brick_halo_bytes(self.bshape, w) for w in (1, 2, 3))
+        key = (brick.device,) + n
+        if key not in self._halo:
+            self._halo[key] = tuple(torch.empty(k, dtype=torch.uint8, device=brick.device) for k in (n[0],) * 4 + (n[1],) * 4 + (n[2],) * 4)
+        s_lo, s_hi, r_lo, r_hi, s2_lo, s2_hi, r2_lo, r2_hi, k_lo, k_hi, q_lo, q_hi = self._halo[key]
+        # An engine call that fails on THIS rank must not take the exchanges with it: the neighbours are waiting for this
+        # rank's faces, and the all-reduce of process() comes only after them.  The rank goes on exchanging (whatever its
+        # buffers hold: the sizes are fixed), skips its remaining engine calls, and raises after the last exchange.
+        from .engine import NBEError
+        failed = []
+
+        def step(call, *args, **kw):
+            if not failed:
+                try:
+                    call(*args, **kw)
+                except NBEError as e:
+                    failed.append(e)
+
+        step(self.eng.brick_encode, H, self.bshape, Dz, vel_fac, s_lo, s_hi, k_lo, k_hi)
         ev = self._exchange_async(cur, s_lo, s_hi, r_lo, r_hi)
-        self.eng.brick_interior()                                   # runs while the faces travel
+        step(self.eng.brick_interior)                               # runs while the faces travel
         self._wait(cur, ev, "down_l0 faces")
-        self.eng.brick_exchange(r_lo, r_hi, s2_lo, s2_hi)
+        step(self.eng.brick_exchange, r_lo, r_hi, s2_lo, s2_hi)
         ev = self._exchange_async(cur, s2_lo, s2_hi, r2_lo, r2_hi)
         # the skip connection's planes go last on the communication stream (behind the faces the compute stream is waiting
         # for) and are needed last: the engine waits for them after levels 1-3, inside brick_finish
         ev_skip = self._exchange_async(cur, k_lo, k_hi, q_lo, q_hi)
         self._wait(cur, ev, "down_l1 faces")
-        self.eng.brick_finish(r2_lo, r2_hi, q_lo, q_hi, Dz, vel_fac, disp, vel, skip_ready=ev_skip)
+        step(self.eng.brick_finish, r2_lo, r2_hi, q_lo, q_hi, Dz, vel_fac, disp, vel, skip_ready=ev_skip)
+        if failed:
+            if cur is not None and ev_skip is not None:
+                cur.wait_event(ev_skip)                             # (brick_finish would have waited for the last exchange)
+            raise failed[0]
 
     def _wait(self, cur, ev, what):
         """The compute stream waits for an exchange.  With self.trace the wait is bracketed by timing events: how long the
@@ -299,11 +319,14 @@ class ShardedBox:
 
     def _agree_on_bricks(self, device):
         """A brick whose workspace does not fit the memory that is free now runs as padded bricks instead; every rank must
-        take the same path (the exchanges differ), so they agree once, with a 4-byte all-reduce."""
+        take the same path (the exchanges differ), so they agree once, with a 4-byte all-reduce.  The strict-float32 fallback
+        (set it before the first step) is planned with the primary: its brick is larger, and a recompute must not part the
+        ranks either."""
         if self._agreed or not self.zbricks:
             self._agreed = True
             return
-        ok = 1 if self.eng.brick_plan(self.bshape) > 0 else 0
+        engines = [self.eng] + ([self.fallback] if self.fallback is not None and self.fallback is not self.eng else [])
+        ok = 1 if all(e.brick_plan(self.bshape) > 0 for e in engines) else 0
         if self.world > 1:
             flag = torch.tensor([ok], dtype=torch.int32, device="cpu" if dist.get_backend(self.group) == "gloo" else device)
             dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.group)
@@ -327,16 +350,20 @@ class ShardedBox:
         on the outcome as well: when an activation leaves the f16 range on ANY rank, every rank learns it through a second
         4-byte all-reduce and all of them either recompute the step on `fallback` (strict float32 engines, same
         parameters; set ShardedBox.fallback) or raise NBERangeError together -- no rank walks into the next collective
-        alone.  The preset range is cleared again before this returns, whatever happens."""
-        from .engine import NBERangeError
+        alone.  The all-reduced flag carries a code: 1 = range, 2 = any other NBEError of an engine call of the brick step
+        (a brick that no longer fits, buffers refused, ...); with a 2 anywhere every rank raises NBEError, there is nothing a
+        recompute would mend.  The preset range is cleared again before this returns, whatever happens."""
+        from .engine import NBEError, NBERangeError
+        bad, msg, err = 0, "", None
         try:
-            self._process(self.eng, brick, Dz, vel_fac, disp, vel)
-            bad, msg = 0, ""
-            if check_finite:
-                try:
+            try:
+                self._process(self.eng, brick, Dz, vel_fac, disp, vel)
+                if check_finite:
                     self.eng.check_finite()
-                except NBERangeError as e:
-                    bad, msg = 1, str(e)
+            except NBEError as e:
+                if not check_finite:                            # (the caller defers the check, and the agreement with it)
+                    raise
+                bad, msg, err = (1, str(e), None) if isinstance(e, NBERangeError) else (2, str(e), e)
         finally:
             self.eng.set_input_range(None)
         if not check_finite:
@@ -347,6 +374,11 @@ class ShardedBox:
             anybad = int(flag.item())
         else:
             anybad = bad
+        if anybad >= 2:
+            if err is not None:
+                raise err
+            raise NBEError("an engine call failed on another rank of the sharded box%s: every rank gives up this step"
+                           % (" (this rank: %s)" % msg if msg else ""))
         if anybad:
             if self.fallback is None:
                 raise NBERangeError(msg or "non-finite values on another rank of the sharded box: an activation left the range "

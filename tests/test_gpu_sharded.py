@@ -172,3 +172,86 @@ def test_brick_protocol_over_rccl_with_one_rank_as_its_own_neighbour():
                        capture_output=True, text=True, timeout=300)
     print(r.stdout[-1500:], r.stderr[-1500:])
     assert r.returncode == 0 and "rccl self check: ok" in r.stdout and "bit-identical: True" in r.stdout
+
+
+SIZE_FB, NDIV_FB, SEED_FB = (96, 48, 48), (2, 1, 1), 63
+
+
+def _fallback_rank_main(rank, world, port, prec, mid, q):
+    import warnings
+    import torch
+    os.environ["NBE_ZBRICKS"] = "1"
+    import torch.distributed as dist
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    os.environ["NBE_MEM_FRACTION"] = "%.3f" % (0.8 / world)     # the ranks share one card: plan tiles with a share of it
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from jax_nbody_emulator_with_dj_amd import sharding
+        from jax_nbody_emulator_with_dj_amd.engine import Engine
+        import test_gpu_range as R
+        torch.cuda.set_device(0)
+        p = R._overflowing_premod_tree(mid)
+        eng = Engine(device=0, mid_chan=mid, compute_vel=True, precision=prec)
+        fb = Engine(device=0, mid_chan=mid, compute_vel=True, precision="f32")
+        for e in (eng, fb):
+            e.load_params(p, premodulated=True)
+        full = np.random.default_rng(SEED_FB).standard_normal((3,) + SIZE_FB).astype(np.float32)
+        sb = sharding.ShardedBox(eng, SIZE_FB, NDIV_FB, rank, world)
+        sb.fallback = fb
+        o, b = sb.origin, sb.bshape
+        assert sb.zbricks and sb.grid == (2, 1, 1) and b == (48, 48, 48)
+        brick = torch.from_numpy(np.ascontiguousarray(full[:, o[0]:o[0] + b[0]])).cuda()
+        disp, vel = torch.zeros_like(brick), torch.zeros_like(brick)
+        with warnings.catch_warnings(record=True) as seen:
+            warnings.simplefilter("always")
+            sb.process(brick, R.DZ, R.VF, disp, vel)
+        torch.cuda.synchronize()
+        warned = any(issubclass(w.category, RuntimeWarning) and "strict float32" in str(w.message) for w in seen)
+        q.put((rank, o, disp.cpu().numpy(), vel.cpu().numpy(), warned, sb.zbricks))
+        eng.close(); fb.close()
+    except Exception as e:                                      # (both ranks fail alike here: tell the test at once)
+        q.put((rank, "error", repr(e)))
+        raise
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("prec,mid", [("f16x3", 64), ("f16", 32)])
+def test_sharded_fallback_recomputes_on_real_engines(engine_factory, prec, mid):
+    """ShardedBox.process with REAL fallback engines: a premodulated tree whose conv_l1 leaves the f16 range overflows on both
+    ranks alike, so both warn and recompute their 48-plane brick on a strict-float32 engine -- in brick mode, with faces of
+    the fallback's own size (a float16 primary's are half as large) -- and the assembled fields are the bits of a
+    single-process strict-float32 process_box."""
+    import torch.multiprocessing as mp
+    import jax_nbody_emulator_with_dj_amd as J
+    import test_gpu_range as R
+    J.models.release_engines()                                  # give the card back before the rank processes start
+    world = 2
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_fallback_rank_main, args=(r, world, port, prec, mid, q)) for r in range(world)]
+    for pr in procs:
+        pr.start()
+    try:
+        parts = [q.get(timeout=120) for _ in range(world)]
+        for pr in procs:
+            pr.join(timeout=120)
+    finally:
+        for pr in procs:                                        # a rank left in a collective must not outlive the test
+            if pr.is_alive():
+                pr.kill()
+    assert not any(part[1] == "error" for part in parts), [part for part in parts if part[1] == "error"]
+    assert all(pr.exitcode == 0 for pr in procs)
+    full = np.random.default_rng(SEED_FB).standard_normal((3,) + SIZE_FB).astype(np.float32)
+    e = engine_factory(mid_chan=mid, compute_vel=True, precision="f32")
+    e.load_params(R._overflowing_premod_tree(mid), premodulated=True)
+    d_ref, v_ref = e.process_box(full, SIZE_FB, NDIV_FB, ((48, 48),) * 3, R.DZ, R.VF)
+    d_all, v_all = np.full_like(d_ref, np.nan), np.full_like(v_ref, np.nan)
+    for rank, o, d, v, warned, zbricks in parts:
+        assert warned, "rank %d did not warn about the strict float32 recompute" % rank
+        assert zbricks, "rank %d left brick mode" % rank
+        d_all[:, o[0]:o[0] + d.shape[1]], v_all[:, o[0]:o[0] + v.shape[1]] = d, v
+    assert np.all(np.isfinite(d_all)) and np.all(np.isfinite(v_all))
+    assert np.array_equal(d_all, d_ref) and np.array_equal(v_all, v_ref)

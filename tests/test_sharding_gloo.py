@@ -254,3 +254,83 @@ def test_sharded_brick_protocol_and_collective_error_handling(world):
         assert p.exitcode == 0
     for rank, out in res:
         assert out == {"clean": True, "raise": True, "fallback": True}, (rank, out)
+
+
+class _LenientEngine(_FakeEngine):
+    """A rank whose neighbour failed: the faces it receives hold whatever the neighbour's buffers held, as on a real card;
+    it computes on them without looking."""
+
+    def brick_exchange(self, r_lo, r_hi, s2_lo, s2_hi):
+        self.calls.append("exchange")
+
+    def brick_finish(self, r2_lo, r2_hi, q_lo, q_hi, Dz, vf, disp, vel, skip_ready=None):
+        self.calls.append("finish")
+
+
+class _FailingEngine(_LenientEngine):
+    """An engine whose nbe_brick_encode fails with a plain NBEError (a brick that no longer fits, buffers refused)."""
+
+    def brick_encode(self, H, b, Dz, vf, s_lo, s_hi, k_lo, k_hi):
+        from jax_nbody_emulator_with_dj_amd.engine import NBEError
+        self.calls.append("encode")
+        raise NBEError("brick of 48 x 48 x 48 does not fit the device memory that is free (fake)")
+
+
+def _engine_error_worker(rank, world, port, q):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import warnings
+        from jax_nbody_emulator_with_dj_amd.engine import NBEError, NBERangeError
+        size, ndiv = (48 * world, 48, 48), (world, 1, 1)
+        brick = torch.full((3, 48, 48, 48), float(rank + 1))
+        disp, vel = torch.zeros_like(brick), torch.zeros_like(brick)
+        out = {}
+        for name, with_fallback in (("raise", False), ("raise_with_fallback", True)):
+            e = (_FailingEngine if rank == 1 else _LenientEngine)(rank, world)
+            fb = _LenientEngine(rank, world)
+            sb = S.ShardedBox(e, size, ndiv, rank, world)
+            if with_fallback:
+                sb.fallback = fb
+            try:
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    sb.process(brick, 0.77, 50.0, disp, vel)
+                out[name] = "returned"
+            except NBERangeError:
+                out[name] = "range error"
+            except NBEError as err:
+                # the failing rank keeps its own message and makes no further engine call; the others ran their step to
+                # the end (the exchanges stayed in step) and learnt of it in the all-reduce; nobody recomputed
+                mine = "does not fit" in str(err)
+                calls = ["encode"] if rank == 1 else ["encode", "interior", "exchange", "finish"]
+                out[name] = (mine == (rank == 1)) and e.calls == calls and e.range is None and fb.calls == []
+        dist.barrier()                                             # nobody is stuck
+        q.put((rank, out))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_sharded_brick_step_agrees_on_an_engine_error(world):
+    """One rank's nbe_brick_encode fails with a plain NBEError (not a range error).  That rank still takes part in the four
+    exchanges, so its neighbours are not left waiting for its faces, and the all-reduced flag carries code 2: EVERY rank
+    raises NBEError -- with or without fallback engines, which cannot mend it -- and none walks into a collective alone."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_engine_error_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    try:
+        res = [q.get(timeout=120) for _ in range(world)]
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0
+    finally:
+        for p in procs:                                            # a rank left in a collective must not outlive the test
+            if p.is_alive():
+                p.kill()
+    for rank, out in res:
+        assert out == {"raise": True, "raise_with_fallback": True}, (rank, out)
