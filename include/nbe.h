@@ -590,6 +590,37 @@ int nbe_block_average(const void* src, int64_t n_in, void* dst, int64_t n_out, v
  * periodic trilinear interpolation of src (n_in^3 float32) at the nodes i n_in / n_out; n_in divides n_out */
 int nbe_trilinear_upsample(const void* src, int64_t n_in, void* dst, int64_t n_out, void* stream);
 
+/* ---- Profiles (no context) ---------------------------------------------------------------------------
+ * Radial count profiles around centres: one histogram of separations per centre, from which the
+ * host forms density profiles and spherical-overdensity radii and masses.  The reference has no such step: its
+ * scripts/halos.py stops at the FoF Length, although the Tinker, Tinker10 and Watson fits it overlays (--hmf,
+ * scripts/halos.py:203) are defined for spherical-overdensity masses.  Pointers, `stream` and asynchrony as for "Density";
+ * records, sorted keys, thresholds, the rule T_b < q <= T_{b+1}, ncell and its adjacency condition exactly as for "Pairs",
+ * whose code decides every bin.  The calls, per catalogue (centres A, matter B): nbe_pair_coords or nbe_fof_cells, the
+ * caller's sort of `keys`, nbe_fof_gather; then nbe_halo_profiles. */
+#define NBE_PROFILE_WAVE_CENTRES 4096 /* nbe_halo_profiles takes form 1 of nbe_halo_profiles_form where countA is at least this */
+#define NBE_PROFILE_WAVE_BELOW 3000   /* and 27 countB / ncell^3 is below this, else form 0 (measured, section 12.8) */
+/* replaces the profile and spherical-overdensity step of a halo finder such as Rockstar or AHF (the particles about a
+ * halo's centre binned in radius), which the reference does not have.  sortedA / keysA = nbe_fof_gather's records and the
+ * sorted keys of the centres, countA rows (keysA is part of a catalogue as for nbe_pair_count; this call reads only the
+ * records); sortedB / keysB / countB those of the matter.  thresholds = nbins + 1 int64 on the HOST, strictly increasing
+ * from -1 or more, 1 <= nbins <= NBE_PAIR_MAX_BINS; counts in 1 .. 2^30; 3 <= ncell <= NBE_FOF_MAX_CELLS with
+ * ncell (isqrt(T_nbins) + 1) <= 2^30.  counts = (countA, nbins) uint64 row-major, NOT zeroed by the caller: row p, the
+ * centre's index before the sort (the record's p), receives the rows of B in each bin, a row of B that coincides with the
+ * centre included (q = 0: in the first bin only if T_0 = -1).  One workgroup of 256 threads per centre, grid-strided
+ * (max_blocks > 0 caps the grid), streams the centre's at most 18 ranges of B end to end, adds into an LDS image of 32-bit
+ * counters and writes the row with plain stores: no global atomics, and the same bits for every launch geometry.  From
+ * NBE_PROFILE_WAVE_CENTRES centres on, where 27 countB / ncell^3 < NBE_PROFILE_WAVE_BELOW, a wave takes a centre instead
+ * (form 1 below), which measured faster there. */
+int nbe_halo_profiles(const void* sortedA, const void* keysA, int64_t countA, const void* sortedB, const void* keysB,
+                      int64_t countB, int ncell, const int64_t* thresholds, int nbins, int max_blocks, void* counts,
+                      void* stream);
+/* nbe_halo_profiles with its form chosen by the caller (tools/time_profiles.py and the tests; the counts are the same
+ * bits): 0 a workgroup per centre, 1 a wave per centre with four centres a workgroup and no workgroup barrier in the loop. */
+int nbe_halo_profiles_form(const void* sortedA, const void* keysA, int64_t countA, const void* sortedB, const void* keysB,
+                           int64_t countB, int ncell, const int64_t* thresholds, int nbins, int max_blocks, int form,
+                           void* counts, void* stream);
+
 /* ---- test / measurement hooks (not part of the reference surface) ------------------------------ */
 
 /* One layer through the production kernels, host NCDHW in / out.  kind: 0 conv3 (VALID 3x3x3),

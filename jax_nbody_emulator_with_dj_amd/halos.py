@@ -13,9 +13,11 @@ Here the displacement stays where `process_box` left it:
     delta_h, info = paint_halos(cat, 1000.0, res=512, min_length=100)               # the halo density contrast
     hb = halo_bias(cat, delta_m, 1000.0, min_length=100)                            # P_hh, P_mm, P_hm, r(k), bias, shot noise
     xi = halo_correlation(cat, 1000.0, np.linspace(1.0, 50.0, 21), min_length=100)  # xi_hh(r) by pair counts; matter=: xi_hm
+    hp = halo_profiles(cat, displacement, 1000.0, profile_edges(0.05, 5.0, 20), overdensity=200.0)   # counts (H, 20), R, N
 
     python -m jax_nbody_emulator_with_dj_amd.halos --displacement_file emu_dis.npy --output_dir out/ [--halo_pk 256]
         [--halo_xi [--xi_rmin 1 --xi_rmax 50 --xi_nbins 20 --xi_log] [--xi_nmu N]]
+        [--halo_profiles [--profile_rmin 0.05 --profile_rmax 5 --profile_nbins 20] [--so_overdensity 200 --so_reference mean]]
 
 Definition (DESIGN.md section 12.5 has the proofs; tests/fof_ref.py restates it in NumPy).  With U = 2^30, particle
 p = (i0 n + i1) n + i2 of the (n, n, n) lattice has the integer coordinates X_c = rint((i_c / n + psi_c / L) U) mod U,
@@ -55,7 +57,7 @@ except Exception:  # pragma: no cover
     torch = None
 
 __all__ = ["fof_halos", "particle_mass", "halo_mass_function", "density_slab", "paint_halos", "halo_bias",
-           "halo_correlation"]
+           "halo_correlation", "halo_profiles"]
 
 _U = 1 << 30                    # include/nbe.h, "Halos": coordinate units per box side
 _MIN_N, _MAX_N = 2, 1024        # NBE_FOF_MIN_N, NBE_FOF_MAX_N
@@ -384,7 +386,38 @@ def halo_correlation(cat, boxsize, r_edges, matter=None, min_length=None, max_le
     return out
 
 
+def halo_profiles(cat, matter, boxsize, r_edges, min_length=None, max_length=None, overdensity=None, reference="mean",
+                  Om=None, z=0.0, particle_mass=None):
+    """The matter profile around every halo of a catalogue and, with `overdensity`, its spherical-overdensity radius and
+    mass (profiles.radial_counts on fof_halos's CMPosition; the profile and SO step of a halo finder such as Rockstar or
+    AHF, which the reference does not have).
+
+    cat, min_length, max_length: the halos and their selection as paint_halos.  matter: (count, 3) positions or the
+    (3, n, n, n) displacement, of the catalogue's kind.  boxsize, r_edges: as profiles.radial_counts.  overdensity: None, or
+    the Delta of profiles.spherical_overdensity with reference, Om, z and particle_mass (r_edges[0] must then be 0).
+    Returns radial_counts's dict (counts (H, nb), r_edges, thresholds, ncell, count_a, count_b) with Length, the selected
+    halos' lengths in the kind of the catalogue, and count, their number, added, and with overdensity R, N, M, flag and
+    delta_eff (host float64 / int8, as spherical_overdensity returns them)."""
+    from .profiles import radial_counts, spherical_overdensity
+    keep, count = _select_halos(cat, None, min_length, max_length, False)
+    if overdensity is not None and not float(np.asarray(r_edges, dtype=np.float64).ravel()[0]) == 0.0:
+        raise ValueError("spherical_overdensity needs r_edges[0] == 0 (enclosed counts), got %g"
+                         % float(np.asarray(r_edges, dtype=np.float64).ravel()[0]))
+    if overdensity is not None and reference == "critical" and Om is None:
+        raise ValueError("spherical_overdensity: reference='critical' needs Om")
+    pos = cat["CMPosition"] if keep is None else cat["CMPosition"][keep]
+    out = radial_counts(pos, matter, boxsize, r_edges)
+    out["Length"] = cat["Length"] if keep is None else cat["Length"][keep]
+    out["count"] = count
+    if overdensity is not None:
+        L = float(np.asarray(boxsize, dtype=np.float64).ravel()[0])
+        out.update(spherical_overdensity(out["counts"], out["r_edges"], L, out["count_b"], overdensity=overdensity,
+                                         reference=reference, Om=Om, z=z, particle_mass=particle_mass))
+    return out
+
+
 HALO_DELTA_FILE, HALO_PK_FILE, HALO_XI_FILE = "halo_delta.npy", "halo_pk.npz", "halo_xi.npz"
+HALO_PROFILES_FILE = "halo_profiles.npz"
 HALO_WEIGHT_NAMES = {"number": None, "length": "Length"}
 
 
@@ -478,6 +511,7 @@ def build_parser():
     ap.add_argument("--halo_weight", choices=sorted(HALO_WEIGHT_NAMES), default="number",
                     help="with --halo_pk: count halos, or weight each by its particle count (default: number)")
     add_xi_arguments(ap)
+    add_profile_arguments(ap)
     return ap
 
 
@@ -520,6 +554,77 @@ def xi_options(args, boxsize, die):
     return dict(r_edges=edges, nmu=nmu)
 
 
+SO_REFERENCES = ("mean", "critical")
+
+
+def add_profile_arguments(ap, suppress=False):
+    """The options of --halo_profiles, shared with run_emulator as add_xi_arguments's are."""
+    flag, value = (argparse.SUPPRESS, argparse.SUPPRESS) if suppress else (False, None)
+    ap.add_argument("--halo_profiles", action="store_true", default=flag,
+                    help="also count the matter in shells about every halo: %s (r_edges, r_mid, counts, rho, Length, R_delta, "
+                         "N_delta, M_delta, flag, overdensity, reference, count) inside the output directory"
+                         % HALO_PROFILES_FILE)
+    ap.add_argument("--profile_rmin", type=float, default=value,
+                    help="with --halo_profiles: first edge after 0 in Mpc/h (default: 0.05)")
+    ap.add_argument("--profile_rmax", type=float, default=value,
+                    help="with --halo_profiles: largest edge in Mpc/h, below boxsize / 3 (default: 5)")
+    ap.add_argument("--profile_nbins", type=int, default=value,
+                    help="with --halo_profiles: edges from rmin to rmax, logarithmic, after the one at 0; 2 .. 128 (default: 20)")
+    ap.add_argument("--so_overdensity", type=float, default=value,
+                    help="with --halo_profiles: the spherical overdensity Delta of R_delta, N_delta, M_delta (default: 200)")
+    ap.add_argument("--so_reference", choices=SO_REFERENCES, default=value,
+                    help="with --halo_profiles: Delta times the mean matter density, or the critical density (default: mean)")
+
+
+def profile_options(args, boxsize, die):
+    """The settings of --halo_profiles of a parsed command line as a dict (r_edges, overdensity, reference), or None without
+    it; `die(message)` for an option without --halo_profiles and for edges that radial_counts would refuse."""
+    from .correlation import pair_geometry
+    from .profiles import profile_edges
+    names = ("profile_rmin", "profile_rmax", "profile_nbins", "so_overdensity", "so_reference")
+    given = [n for n in names if getattr(args, n, None) is not None]
+    if not getattr(args, "halo_profiles", False):
+        if given:
+            die("--%s needs --halo_profiles" % given[0])
+        return None
+    get = lambda n, d: d if getattr(args, n, None) is None else getattr(args, n)
+    delta = get("so_overdensity", 200.0)
+    try:
+        edges = profile_edges(get("profile_rmin", 0.05), get("profile_rmax", 5.0), get("profile_nbins", 20))
+        pair_geometry(boxsize, edges)
+        if not (np.isfinite(delta) and delta > 0.0):
+            raise ValueError("--so_overdensity must be positive, got %r" % (delta,))
+    except ValueError as e:
+        die(str(e))
+    return dict(r_edges=edges, overdensity=float(delta), reference=get("so_reference", "mean"))
+
+
+def halo_profile_arrays(cat, matter, boxsize, n, Om, r_edges, overdensity=200.0, reference="mean", z=0.0):
+    """The arrays of halo_profiles.npz for a catalogue and the displacement it was found in (an n^3 load at redshift z,
+    Omega_m Om): r_edges, r_mid, counts, rho, Length, R_delta, N_delta, M_delta, flag, overdensity, reference, count -- or None for
+    a catalogue without a halo."""
+    from .profiles import density_profile
+    if int(cat["Length"].shape[0]) == 0:
+        return None
+    out = halo_profiles(cat, matter, boxsize, r_edges, overdensity=overdensity, reference=reference, Om=Om, z=z,
+                        particle_mass=particle_mass(Om, boxsize, n))
+    to_np = lambda a: a.cpu().numpy() if _is_torch(a) else np.asarray(a)
+    counts, edges = to_np(out["counts"]), to_np(out["r_edges"])
+    prof = density_profile(counts, edges, boxsize, out["count_b"])
+    return dict(r_edges=edges, r_mid=prof["r_mid"], counts=counts, rho=prof["rho"],
+                Length=to_np(out["Length"]).astype(np.int64), R_delta=out["R"], N_delta=out["N"], M_delta=out["M"],
+                flag=out["flag"], overdensity=np.float64(overdensity), reference=np.str_(reference),
+                count=np.int64(out["count"]))
+
+
+def save_halo_profiles(out_dir, arrs):
+    """Write halo_profiles.npz, or print the one line that says why not (halo_profile_arrays's None)."""
+    if arrs is None:
+        print("no halo in the catalogue: %s is not written" % HALO_PROFILES_FILE)
+        return
+    np.savez(os.path.join(str(out_dir), HALO_PROFILES_FILE), **arrs)
+
+
 def save_halo_spectra(out_dir, spectra):
     """Write halo_delta.npy and halo_pk.npz, or print the one line that says why not (halo_spectra's None)."""
     if spectra is None:
@@ -548,6 +653,7 @@ def main(argv=None):
     if a.halo_pk is not None and a.halo_pk < 1:
         sys.exit("--halo_pk must be >= 1, got %d" % a.halo_pk)
     xi = xi_options(a, a.boxsize, sys.exit)
+    prof = profile_options(a, a.boxsize, sys.exit)
     disp = load_displacement(a.displacement_file)
     try:
         cat = fof_halos(disp, boxsize=a.boxsize, linking_length=a.linking_length, nmin=a.nmin, absolute=a.absolute_linking)
@@ -564,6 +670,9 @@ def main(argv=None):
                                                      HALO_WEIGHT_NAMES[a.halo_weight]))
     if xi is not None:
         save_halo_xi(a.output_dir, halo_xi_arrays(cat, a.boxsize, xi["r_edges"], xi["nmu"]))
+    if prof is not None:
+        save_halo_profiles(a.output_dir, halo_profile_arrays(cat, disp, a.boxsize, disp.shape[1], a.omega_m, prof["r_edges"],
+                                                             prof["overdensity"], prof["reference"]))
 
 
 if __name__ == "__main__":

@@ -45,7 +45,11 @@ halos (halos.paint_halos; `--halo_weight number|length`) and the matter (density
 p_hm, r, bias, nmodes, shot_noise, count: density.cross_correlation of the two fields), and `--halo_xi` counts the halo
 pairs (halos.halo_correlation; `--xi_rmin 1 --xi_rmax 50 --xi_nbins 20 [--xi_log] [--xi_nmu N]`) and writes
 <output_dir>/halo_xi.npz (r_edges, r_mid, npairs, rr, xi, count, with --xi_nmu mu_edges, xi0, xi2,
-xi4); a box without a halo writes none of these and says so.  `--xcorr FILE` (with --density_res) writes <output_dir>/emu_xcorr.npz, density.cross_correlation of
+xi4), and `--halo_profiles` counts the matter in shells about every halo (halos.halo_profiles; `--profile_rmin 0.05
+--profile_rmax 5 --profile_nbins 20 [--so_overdensity 200 --so_reference mean|critical]`) and writes
+<output_dir>/halo_profiles.npz (r_edges, r_mid, counts, rho, Length, R_delta, N_delta, M_delta, flag, overdensity,
+reference, count; the spherical-overdensity radii and masses at the box's redshift); a box without a halo writes none of
+these and says so.  `--xcorr FILE` (with --density_res) writes <output_dir>/emu_xcorr.npz, density.cross_correlation of
 emu_delta against the saved (N, N, N) field FILE (k, p_aa, p_bb, p_ab, nmodes, r, transfer, bias): the reference's
 emulator-against-target check (scripts/utils.py:1451-1470).
 
@@ -223,6 +227,8 @@ def build_parser():
                     help='With --halo_pk: count halos, or weight each by its particle count (default: number)')
     from .halos import add_xi_arguments
     add_xi_arguments(ap, suppress=True)                      # --halo_xi, --xi_rmin, --xi_rmax, --xi_nbins, --xi_log, --xi_nmu
+    from .halos import add_profile_arguments
+    add_profile_arguments(ap, suppress=True)                 # --halo_profiles, --profile_rmin / _rmax / _nbins, --so_overdensity / _reference
     ap.add_argument('--xcorr', type=Path, metavar='FILE', default=argparse.SUPPRESS,
                     help='With --density_res: also write r(k), transfer and bias of emu_delta against the saved (N, N, N) '
                          'float32 field FILE to <output_dir>/emu_xcorr.npz')
@@ -370,6 +376,16 @@ def halo_xi_options(args):
     return xi
 
 
+def halo_profile_options(args):
+    """The settings of --halo_profiles (halos.profile_options: r_edges, overdensity, reference), or None without it.  It
+    needs --fof."""
+    from .halos import profile_options
+    prof = profile_options(args, float(getattr(args, 'boxsize', 1000.0)), _die)
+    if prof is not None and not getattr(args, 'fof', False):
+        _die('--halo_profiles needs --fof')
+    return prof
+
+
 def xcorr_option(args):
     """The (N, N, N) float32 field of --xcorr, or None without it.  It needs --density_res and that mesh size."""
     path = getattr(args, 'xcorr', None)
@@ -385,17 +401,21 @@ def xcorr_option(args):
     return np.ascontiguousarray(field, dtype=np.float32)
 
 
-def fof_catalog(disp, fof, Om, halo=None, xi=None):
+def fof_catalog(disp, fof, Om, halo=None, xi=None, profiles=None, z=0.0):
     """The arrays of fof_catalog.npz for the device displacement of one box, as {'fof': arrays}; with the settings of
     --halo_pk also 'halo': halos.halo_spectra's result (None for a box without a halo); with those of --halo_xi also
-    'halo_xi': halos.halo_xi_arrays's."""
-    from .halos import catalog_arrays, fof_halos, halo_spectra, halo_xi_arrays
+    'halo_xi': halos.halo_xi_arrays's; with those of --halo_profiles also 'halo_profiles': halos.halo_profile_arrays's at
+    redshift z."""
+    from .halos import catalog_arrays, fof_halos, halo_profile_arrays, halo_spectra, halo_xi_arrays
     cat = fof_halos(disp, boxsize=fof['boxsize'], linking_length=fof['linking_length'], nmin=fof['nmin'])
     out = {'fof': catalog_arrays(cat, int(disp.shape[1]), fof['boxsize'], Om, fof['linking_length'], False, fof['nmin'])}
     if halo is not None:
         out['halo'] = halo_spectra(cat, disp, fof['boxsize'], halo['res'], halo['worder'], halo['weight'])
     if xi is not None:
         out['halo_xi'] = halo_xi_arrays(cat, fof['boxsize'], xi['r_edges'], xi['nmu'])
+    if profiles is not None:
+        out['halo_profiles'] = halo_profile_arrays(cat, disp, fof['boxsize'], int(disp.shape[1]), Om, profiles['r_edges'],
+                                                   profiles['overdensity'], profiles['reference'], z=z)
     return out
 
 
@@ -453,6 +473,7 @@ def run(args):
     fof = fof_options(args)
     halo = halo_options(args)
     halo_xi = halo_xi_options(args)
+    halo_prof = halo_profile_options(args)
     target = xcorr_option(args)
     if bispec:
         for k1, k2 in BISPECTRUM_CONFIGS:                    # density.bispectrum's closure condition, before any work
@@ -468,7 +489,8 @@ def run(args):
     if fof is not None:
         print(f"  Halos: FoF b = {fof['linking_length']}, nmin {fof['nmin']}, boxsize {fof['boxsize']}"
               + (f", halo spectra on a {halo['res']}^3 mesh" if halo is not None else "")
-              + (f", halo pairs in {len(halo_xi['r_edges']) - 1} bins" if halo_xi is not None else ""))
+              + (f", halo pairs in {len(halo_xi['r_edges']) - 1} bins" if halo_xi is not None else "")
+              + (f", halo profiles in {len(halo_prof['r_edges']) - 1} bins" if halo_prof is not None else ""))
     print()
 
     shape = None
@@ -510,6 +532,9 @@ def run(args):
         if extra is not None and 'halo_xi' in extra:
             from .halos import save_halo_xi
             save_halo_xi(out_dir, extra['halo_xi'])
+        if extra is not None and 'halo_profiles' in extra:
+            from .halos import save_halo_profiles
+            save_halo_profiles(out_dir, extra['halo_profiles'])
         if extra is not None and 'delta' in extra:
             np.save(out_dir / 'emu_delta.npy', extra['delta'])
             if 'pk' in extra:
@@ -544,7 +569,7 @@ def run(args):
         box_t = torch.from_numpy(np.ascontiguousarray(dis_in)).to('cuda')
         result = emu.process_box(box_t, z=z, Om=Om, show_progress=not args.quiet)
         disp = result[0] if args.vel else result
-        extra = {} if fof is None else fof_catalog(disp, fof, Om, halo, halo_xi)
+        extra = {} if fof is None else fof_catalog(disp, fof, Om, halo, halo_xi, halo_prof, float(z))
         out_dt = np.dtype(args.output_precision)
         if dens is None:
             host = tuple(t.cpu().numpy().astype(out_dt, copy=False) for t in (result if args.vel else (result,)))
