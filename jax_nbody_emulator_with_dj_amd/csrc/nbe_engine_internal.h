@@ -287,8 +287,8 @@ int check_range(nbe_ctx* c);
 
 // ---- nbe_engine_net.cpp: tensors in the arena, one layer, the blocks, the U-Net schedule ---------------------------
 int planes_for(int C, int prec);
-Tensor talloc(nbe_ctx* c, int C, int D, int H, int W);
-Tensor tallocp(nbe_ctx* c, int C, int D, int Hi, int Wi, int pad);
+Tensor talloc(nbe_ctx* c, int C, int D, int H, int W, bool zero_rest = true);
+Tensor tallocp(nbe_ctx* c, int C, int D, int Hi, int Wi, int pad, bool zero_rest = true);
 void fill_halo(nbe_ctx* c, const Tensor& t);
 void tfree(nbe_ctx* c, Tensor& t);
 Tensor zview(const Tensor& t, int z0, int nz);
@@ -302,10 +302,11 @@ bool block_fused(const nbe_ctx* c, const Layer* L1, int nres);
 bool two_source_width(const nbe_ctx* c);
 Tensor alloc_hidden(nbe_ctx* c, int cmid, int nz, const Tensor& x, bool fused);
 int resblock_part(nbe_ctx* c, const char* name, const Tensor& x, const Tensor& h, const Tensor& s,
-                  int js, int ns, int jh, int nh, bool has_dx, bool final_act, const int* zr, const Tensor* x2 = nullptr);
+                  int js, int ns, int jh, int nh, bool has_dx, bool final_act, const int* zr, const Tensor* x2 = nullptr,
+                  bool halo_s = true);
 int resblock(nbe_ctx* c, const char* name, const Tensor& x, bool has_dx, bool final_act, int cout, int cmid, Tensor* out,
-             Tensor* hidden_out = nullptr);
-int down_conv(nbe_ctx* c, const Layer& L, const Tensor& x, Tensor& o, bool probe);
+             Tensor* hidden_out = nullptr, const int* zr = nullptr, const Tensor* x2 = nullptr);
+int down_conv(nbe_ctx* c, const Layer& L, const Tensor& x, Tensor& o, bool probe, const int* zr = nullptr);
 int downblock(nbe_ctx* c, const char* name, const Tensor& x, Tensor* out);
 int upblock(nbe_ctx* c, const char* name, const Tensor& x, const Tensor& cat, int xcrop = 0, int g0 = -1);
 void crop_into(nbe_ctx* c, const Tensor& src, int crop, const Tensor& dst, int cz = -1);

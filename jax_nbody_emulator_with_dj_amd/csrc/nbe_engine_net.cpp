@@ -22,14 +22,15 @@ static Planes ws_planes(nbe_ctx* c, int G, int D, int H, int W, int64_t* off_out
     return p;
 }
 
-Tensor talloc(nbe_ctx* c, int C, int D, int H, int W) {
+// (zero_rest = false: a tensor none of whose consumers reads a channel plane beyond C -- conv_r01's result, which the head reads)
+Tensor talloc(nbe_ctx* c, int C, int D, int H, int W, bool zero_rest) {
     Tensor t;
     t.p = ws_planes(c, planes_for(C, c->prec), D, H, W, &t.off);
     // Channel planes beyond C (C not a multiple of 16: narrow test models) are read by the consumer against zero
     // weights but never written by the producer: they must hold finite values whatever an earlier call -- another
     // shape, a NaN in its input, an overflow -- left at this place of the arena.  No such planes at production width.
     const int gw = c->prec == PREC_F16 ? (C + 7) / 8 : c->prec == PREC_F16X3 ? 2 * ((C + 7) / 8) : (C + 3) / 4;
-    if (!c->dry && t.off >= 0 && gw < t.p.G) {
+    if (zero_rest && !c->dry && t.off >= 0 && gw < t.p.G) {
         const size_t off = (size_t)gw * t.p.pstride * 4, bytes = (size_t)(t.p.G - gw) * t.p.pstride * 16;
         launch_zero(t.p.x + off, (int64_t)bytes, c->stream);
         if (t.p.dx) launch_zero(t.p.dx + off, (int64_t)bytes, c->stream);
@@ -37,8 +38,8 @@ Tensor talloc(nbe_ctx* c, int C, int D, int H, int W) {
     return t;
 }
 // interior Hi x Wi plus a y/x halo of `pad`
-Tensor tallocp(nbe_ctx* c, int C, int D, int Hi, int Wi, int pad) {
-    Tensor t = talloc(c, C, D, Hi + 2 * pad, Wi + 2 * pad);
+Tensor tallocp(nbe_ctx* c, int C, int D, int Hi, int Wi, int pad, bool zero_rest) {
+    Tensor t = talloc(c, C, D, Hi + 2 * pad, Wi + 2 * pad, zero_rest);
     t.pad = pad;
     return t;
 }
@@ -154,6 +155,11 @@ const Layer* find_layer(nbe_ctx* c, const char* block, const char* layer) {
 // schedule
 // ------------------------------------------------------------------------------------------------
 
+// A tile that is the whole periodic box: planes of periodic z context on either side of a level input's own planes.  Level 1:
+// what conv_l1 reads beyond the box's own N / 2 planes for the N / 2 + 8 planes of the level-1 skip connection (4 + 2).
+// Level 2 (also its y/x halo, in every periodic-yx tile): what levels 2 and 3 consume.  The same counts as a brick's faces.
+static constexpr int L1_CTX = BRICK_H1, L2_CTX = BRICK_H2;
+
 // StyleResNetBlock3DVel (style_blocks_vel.py:96-166): skip 1x1x1 cropped by 2, conv-act-conv, add, [act].
 // Periodic-yx mode (x.pad = 1): y and x do not shrink -- every 3x3x3 convolution reads its input's wrap-around halo
 // and writes the interior of a tensor of the same padded size, whose halo is filled afterwards; z shrinks as always.
@@ -187,8 +193,9 @@ Tensor alloc_hidden(nbe_ctx* c, int cmid, int nz, const Tensor& x, bool fused) {
 // zr = {lo, hi, period} (branch probe): planes [lo, hi) of the block's result exist in a box periodic along z (nullptr: no wrap).
 // x2: the block input is concat([x, x2]) along the channels (mid channels each, same geometry) without a concat tensor:
 // the gauged f16x3 kernel reads its K chunks from two tensors (fused blocks only)
+// halo_s = false: nothing reads the y/x halo of the result (conv_r01: the head reads the interior), so it is not filled
 int resblock_part(nbe_ctx* c, const char* name, const Tensor& x, const Tensor& h, const Tensor& s,
-                         int js, int ns, int jh, int nh, bool has_dx, bool final_act, const int* zr, const Tensor* x2) {
+                         int js, int ns, int jh, int nh, bool has_dx, bool final_act, const int* zr, const Tensor* x2, bool halo_s) {
     const Layer *Ls = find_layer(c, name, "skip"), *L0 = find_layer(c, name, "conv_0"), *L1 = find_layer(c, name, "conv_1");
     if (!Ls || !L0 || !L1) return fail("missing layers of block %s", name);
     const int H = x.p.H, W = x.p.W, pad = x.pad;
@@ -225,14 +232,15 @@ int resblock_part(nbe_ctx* c, const char* name, const Tensor& x, const Tensor& h
         org_conv(x, 2, og); og[0] += js;
         if (final_act) probe_act(c, *L1, cl.out, 0, og, cl.Dv, cl.Hv, cl.Wv, pad != 0, zr);
     }
-    fill_halo(c, sv);
+    if (halo_s) fill_halo(c, sv);
     return 0;
 }
 
 // the block on whole tensors: its result is allocated (cout channels), the hidden tensor (cmid channels) lives meanwhile
 // (hidden_out: a view of the released hidden tensor, whose planes stay as they are until the next allocation -- nbe_test_block)
+// (zr, x2: as resblock_part)
 int resblock(nbe_ctx* c, const char* name, const Tensor& x, bool has_dx, bool final_act, int cout, int cmid, Tensor* out,
-                    Tensor* hidden_out) {
+                    Tensor* hidden_out, const int* zr, const Tensor* x2) {
     const Layer* L1 = find_layer(c, name, "conv_1");
     if (!L1) return fail("missing layers of block %s", name);
     const int D = x.p.D, pad = x.pad;
@@ -240,7 +248,7 @@ int resblock(nbe_ctx* c, const char* name, const Tensor& x, bool has_dx, bool fi
     Tensor s = tallocp(c, cout, D - 4, x.p.H - 2 * pad - 2 * sy, x.p.W - 2 * pad - 2 * sy, pad);
     Tensor h = alloc_hidden(c, cmid, D - 2, x, block_fused(c, L1, D - 4));
     if (s.off < 0 || h.off < 0) return fail("workspace exhausted in block %s", name);
-    if (resblock_part(c, name, x, h, s, 0, D - 4, 0, D - 2, has_dx, final_act, nullptr)) return 1;
+    if (resblock_part(c, name, x, h, s, 0, D - 4, 0, D - 2, has_dx, final_act, zr, x2)) return 1;
     tfree(c, h);
     if (hidden_out) *hidden_out = h;
     int og[3];
@@ -256,14 +264,28 @@ static void carry_planes(nbe_ctx* c, const Tensor& t, int src, int dst, int n) {
     launch_crop(zview(t, src, n).p, 0, zview(t, dst, n).p, 0, c->vel, c->stream, 0);
 }
 
-// down-sampling layer L (stride 2) of x's interior into o, which takes x's frame halved; probe: record its branches
-int down_conv(nbe_ctx* c, const Layer& L, const Tensor& x, Tensor& o, bool probe) {
-    ConvLaunch cl; cl.in = inner(x); cl.Dv = o.p.D; cl.Hv = o.p.H; cl.Wv = o.p.W; cl.out = o.p; cl.flags = F_ACT;
+// down-sampling layer L (stride 2) of x's interior into o's interior (o.pad > 0: the kernel writes where the next level reads,
+// the caller fills the halo), which takes x's frame halved; probe: record its branches (zr: as probe_act)
+int down_conv(nbe_ctx* c, const Layer& L, const Tensor& x, Tensor& o, bool probe, const int* zr) {
+    ConvLaunch cl; cl.in = inner(x); cl.Dv = o.p.D; cl.Hv = o.p.H - 2 * o.pad; cl.Wv = o.p.W - 2 * o.pad; cl.out = inner(o); cl.flags = F_ACT;
     if (run_conv(c, L, cl, true)) return 1;
     set_org(o, x.org[0] / 2, x.org[1] / 2, x.org[2] / 2);
     // (periodic-yx: the interior only; its periodic images are copies)
-    if (probe) probe_act(c, L, cl.out, 0, o.org, cl.Dv, cl.Hv, cl.Wv, x.pad != 0);
+    if (probe) probe_act(c, L, cl.out, 0, o.org, cl.Dv, cl.Hv, cl.Wv, x.pad != 0, zr);
     return 0;
+}
+
+// Periodic z context of a level input whose own planes [cz, D - cz) are complete, y/x halo included: the cz planes on either
+// side are copies of the planes one period (= the own planes) away: plain plane copies.  A shallow box has fewer own planes
+// than context planes (depth 8: 4 and 2 own planes against 6 and 10), so the context is built outward from the own planes
+// in chunks of at most one period -- each chunk's source is own or already copied, and never overlaps its destination.
+static void wrap_z(nbe_ctx* c, const Tensor& t, int cz) {
+    const int own = t.p.D - 2 * cz;
+    for (int done = 0; done < cz; done += own) {
+        const int n = std::min(own, cz - done);
+        carry_planes(c, t, cz - done - n + own, cz - done - n, n);   // below the planes [cz - done, ..)
+        carry_planes(c, t, cz + done, cz + own + done, n);            // above the planes [.., cz + own + done)
+    }
 }
 
 int downblock(nbe_ctx* c, const char* name, const Tensor& x, Tensor* out) {
@@ -344,9 +366,10 @@ void run_head(nbe_ctx* c, const Tensor& y, const Tensor& xin, const HeadOut& h, 
 // Periodic-yx mode (tin.pad = 1: the tile spans the whole periodic box in y and x).  The two full-resolution levels
 // do not pad-and-shrink in y and x: their tensors are N + 2 wide, every 3x3x3 convolution reads the wrap-around halo
 // of its input and the halo of its output is filled afterwards -- the same arithmetic per voxel as the reference's
-// 48-voxel periodic padding, without computing the halo voxels (about 10 % of the FLOPs of a 512^3 box).  The levels
-// below keep the padded scheme: down_l0 runs on the interior and its output is extended periodically by the 22
-// voxels of context those levels consume; up_r0 takes the centre of the level-1 result.
+// 48-voxel periodic padding, without computing the halo voxels (about 10 % of the FLOPs of a 512^3 box).  Level 1 runs
+// the same way on the interior that down_l0 writes straight into its input tensor; levels 2 and 3 keep the padded scheme
+// on the 10 voxels of periodic context that stream_level1 gives the level-2 input; up_r0 takes the centre of the level-1
+// result.
 static int stream_encode(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S, Tensor* skip0_out, Tensor* td_out) {
     const int m = c->mid, pad = tin.pad;
     const int D = tin.p.D, H = tin.p.H, W = tin.p.W;
@@ -362,8 +385,12 @@ static int stream_encode(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S
     const int zlo = pz ? (zx ? 44 : 40) : 0, zhi = pz ? (zx ? Y - 44 : Y - 40) : Y;
     // the level-0 skip connection: centre crop by 40 (z only in periodic-yx mode)
     Tensor skip0 = pad ? tallocp(c, m, Y - 80, Hi, Wi, pad) : talloc(c, m, Y - 80, H - 88, W - 88);
-    // down_l0 output; periodic-yx: on the interior first (td), then extended by 22 voxels of periodic context (t)
-    Tensor td = pad ? talloc(c, m, pz ? (D - 96) / 2 : Y / 2, Hi / 2, Wi / 2) : talloc(c, m, Y / 2, (H - 8) / 2, (W - 8) / 2);
+    // down_l0 output.  Periodic-yx: down_l0 writes the interior of the level-1 input itself (1-voxel y/x halo; periodic in z,
+    // L1_CTX planes of context on either side of the box's own N / 2), which stream_level1 completes.  Brick mode keeps a
+    // tensor of the interior alone (td): its faces travel to the neighbours as they are.
+    const int cz1 = (pz && !zx) ? L1_CTX : 0, dpad = (pad && !zx) ? 1 : 0;
+    const int D1 = pz ? (D - 96) / 2 : Y / 2;
+    Tensor td = pad ? tallocp(c, m, D1 + 2 * cz1, Hi / 2, Wi / 2, dpad) : talloc(c, m, Y / 2, (H - 8) / 2, (W - 8) / 2);
     if (skip0.off < 0 || td.off < 0) return fail("workspace exhausted (level 0)");
     const Layer* Ld = find_layer(c, "down_l0", "conv_0");
     if (!Ld) return fail("missing layer down_l0/conv_0");
@@ -413,9 +440,9 @@ static int stream_encode(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S
             // planes [d0, d1) of this slab go through down_l0 (periodic in z: only the box's own planes, 44 .. Y - 44)
             const int d0 = pz ? std::max(z, 44) : z, d1 = pz ? std::min(z + n, Y - 44) : z + n;
             if (d1 > d0) {
-                const Tensor tv = zview(td, (d0 - (pz ? 44 : 0)) / 2, (d1 - d0) / 2);
+                const Tensor tv = zview(td, cz1 + (d0 - (pz ? 44 : 0)) / 2, (d1 - d0) / 2);
                 Tensor yv = zview(y0, d0 - z, d1 - d0);
-                ConvLaunch cl; cl.in = inner(yv); cl.Dv = tv.p.D; cl.Hv = tv.p.H; cl.Wv = tv.p.W; cl.out = tv.p; cl.flags = F_ACT;
+                ConvLaunch cl; cl.in = inner(yv); cl.Dv = tv.p.D; cl.Hv = tv.p.H - 2 * dpad; cl.Wv = tv.p.W - 2 * dpad; cl.out = inner(tv); cl.flags = F_ACT;
                 if (run_conv(c, *Ld, cl, true)) return 1;
                 const int og[3] = {yv.org[0] / 2, yv.org[1] / 2, yv.org[2] / 2};
                 const int zd[3] = {22, 22 + (D - 96) / 2, pz ? (D - 96) / 2 : 0};   // periodic in z: the box's own N / 2 planes
@@ -427,60 +454,76 @@ static int stream_encode(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S
     if (!pz) tfree(c, y0r);
     // frames: the skip connection is conv_l01's result cropped by 40 (its frame starts 40 voxels in; periodic-yx keeps all
     // of y and x, whose interior sits 44 voxels into the padded frame); down_l0's output starts at plane 44 / 2 when the
-    // encoder only produced the box's own planes (pz)
+    // encoder only produced the box's own planes (pz), cz1 planes of context before them
     set_org(skip0, 0, pad ? 4 : 0, pad ? 4 : 0);
-    set_org(td, pz ? 22 : 0, pad ? 22 : 0, pad ? 22 : 0);
+    set_org(td, pz ? 22 - cz1 : 0, pad ? 22 : 0, pad ? 22 : 0);
     *skip0_out = skip0; *td_out = td;
     return 0;
 }
 
-// Level 1 of the encoder (whole tensors, and the z-slab schedule outside brick mode): the down_l0 output td -> the level-1
-// skip connection cat1 (first half of the decoder's concat) and the level-2 input t.
-// Periodic-yx: level 1 runs periodic in y and x as well -- its input is the interior result of down_l0 with a 1-voxel
-// wrap-around halo (and, periodic in z, 22 planes of periodic context); level 2 and below keep the padded scheme: down_l1
-// runs on the interior and is extended periodically by the 10 voxels those levels consume.
-static int stream_level1(nbe_ctx* c, int pad, bool pz, Tensor td, Tensor* cat1_out, Tensor* t_out) {
+// Level 1 of the encoder (whole tensors, and the z-slab schedule outside brick mode): the down_l0 output td -> conv_l1's
+// result, from which come the level-1 skip connection and the level-2 input t.
+// Periodic-yx: level 1 runs periodic in y and x as well.  td is its input already -- down_l0 wrote the interior of the box's
+// own planes (stream_encode); here their 1-voxel wrap-around halo is filled and, periodic in z, the L1_CTX planes of context on
+// either side are copied from the own planes one period away.  conv_l1 then computes N / 2 + 8 planes: exactly the skip
+// connection.  Level 2 and below keep the padded scheme, and get their context the same way: down_l1 runs on the box's own
+// planes and writes the interior of the level-2 input, whose L2_CTX voxels of y/x halo are filled and whose L2_CTX planes of z
+// context are copied.  (A tile that is not the whole box in z has no periodic images along z: conv_l1 and down_l1 run on
+// all planes, and the skip connection is the result cropped by 16 planes.)
+// The skip connection: a fused conv_r1 at a two-source width reads it where it is -- conv_l1's result stays alive (*y1_out)
+// and no concat tensor is formed (lower_levels); otherwise it is copied into the first half of the concat tensor *cat1_out.
+static int stream_level1(nbe_ctx* c, int pad, bool pz, Tensor td, Tensor* cat1_out, Tensor* y1_out, Tensor* t_out) {
     const int m = c->mid;
-    Tensor t = td;
-    if (pad) {
-        t = tallocp(c, m, td.p.D + (pz ? 44 : 0), td.p.H, td.p.W, 1);
-        if (t.off < 0) return fail("workspace exhausted (level 1 input)");
-        if (!c->dry) launch_wrap_pad(td.p, t.p, 1, c->vel, c->stream, pz ? 22 : 0);
-        set_org(t, pz ? td.org[0] - 22 : td.org[0], td.org[1], td.org[2]);
-        tfree(c, td);
-    }
-
-    Tensor y1, cat1;
-    if (resblock(c, "conv_l1", t, true, true, m, m, &y1)) return 1;
-    tfree(c, t);
-    if (pad) {
-        cat1 = tallocp(c, 2 * m, y1.p.D - 32, y1.p.H - 2, y1.p.W - 2, 1);
-        if (cat1.off < 0) return fail("workspace exhausted (cat1)");
-        crop_into(c, y1, 0, cat1, 16);
-        set_org(cat1, y1.org[0], y1.org[1] - 16, y1.org[2] - 16);    // cropped by 16 in z only; the frame moves by 16 on every axis
-        Tensor t2 = talloc(c, m, y1.p.D / 2, (y1.p.H - 2) / 2, (y1.p.W - 2) / 2);
-        const Layer* Ld1 = find_layer(c, "down_l1", "conv_0");
-        if (t2.off < 0 || !Ld1) return fail("workspace exhausted or missing layer (down_l1)");
-        if (down_conv(c, *Ld1, y1, t2, true)) return 1;
-        t = talloc(c, m, t2.p.D, t2.p.H + 20, t2.p.W + 20);
-        if (t.off < 0) return fail("workspace exhausted (level 2 input)");
-        if (!c->dry) launch_wrap_pad(t2.p, t.p, 10, c->vel, c->stream, 0);
-        set_org(t, t2.org[0], t2.org[1] - 10, t2.org[2] - 10);
-        tfree(c, t2);
-    } else {
+    Tensor t = td, y1, cat1;
+    *y1_out = Tensor();
+    if (!pad) {
+        if (resblock(c, "conv_l1", t, true, true, m, m, &y1)) return 1;
+        tfree(c, t);
         cat1 = talloc(c, 2 * m, y1.p.D - 32, y1.p.H - 32, y1.p.W - 32);
         if (cat1.off < 0) return fail("workspace exhausted (cat1)");
         crop_into(c, y1, 16, cat1);
         if (downblock(c, "down_l1", y1, &t)) return 1;
+        tfree(c, y1);
+        *cat1_out = cat1; *t_out = t;
+        return 0;
     }
-    tfree(c, y1);
+    const int cz1 = pz ? L1_CTX : 0, cz2 = pz ? L2_CTX : 0;
+    fill_halo(c, zview(t, cz1, t.p.D - 2 * cz1));
+    wrap_z(c, t, cz1);
+    // (branch probe: periodic in z, planes [16, 16 + N / 2 + 8) of conv_l1's result exist, and the box's own N / 4 of down_l1's)
+    const int zr1[3] = {t.org[0], t.org[0] + t.p.D - 4, t.p.D - 2 * cz1};
+    if (resblock(c, "conv_l1", t, true, true, m, m, &y1, nullptr, pz ? zr1 : nullptr)) return 1;
+    tfree(c, t);
+
+    const int zc = pz ? 0 : 16;                                   // planes of y1 on either side of the skip connection
+    const Layer *Lr1 = find_layer(c, "conv_r1", "conv_1"), *Ld1 = find_layer(c, "down_l1", "conv_0");
+    if (!Lr1 || !Ld1) return fail("missing layer conv_r1/conv_1 or down_l1/conv_0");
+    const bool two = block_fused(c, Lr1, y1.p.D - 2 * zc - 4) && two_source_width(c);
+    if (!two) {
+        cat1 = tallocp(c, 2 * m, y1.p.D - 2 * zc, y1.p.H - 2, y1.p.W - 2, 1);
+        if (cat1.off < 0) return fail("workspace exhausted (cat1)");
+        crop_into(c, y1, 0, cat1, zc);
+        set_org(cat1, y1.org[0] + zc - 16, y1.org[1] - 16, y1.org[2] - 16);   // the skip connection's frame starts 16 voxels into y1's on every axis
+    }
+    Tensor y1d = pz ? zview(y1, 4, y1.p.D - 8) : y1;              // what down_l1 runs on
+    t = talloc(c, m, y1d.p.D / 2 + 2 * cz2, (y1.p.H - 2) / 2 + 2 * L2_CTX, (y1.p.W - 2) / 2 + 2 * L2_CTX);
+    if (t.off < 0) return fail("workspace exhausted (level 2 input)");
+    Tensor tp = zview(t, cz2, y1d.p.D / 2);                       // its own planes as a tensor with a y/x halo
+    tp.pad = L2_CTX;
+    const int zd[3] = {y1d.org[0] / 2, y1d.org[0] / 2 + tp.p.D, tp.p.D};
+    if (down_conv(c, *Ld1, y1d, tp, true, pz ? zd : nullptr)) return 1;
+    fill_halo(c, tp);
+    wrap_z(c, t, cz2);
+    set_org(t, tp.org[0] - cz2, tp.org[1] - L2_CTX, tp.org[2] - L2_CTX);
+    if (two) *y1_out = y1; else tfree(c, y1);
     *cat1_out = cat1; *t_out = t;
     return 0;
 }
 
-// Levels 2 and 3 and the level-1 decoder: the level-2 input t and the level-1 skip connection cat1 -> the level-1 decoder
-// output (conv_r1) in *r_out
-static int lower_levels(nbe_ctx* c, Tensor t, Tensor cat1, Tensor* r_out) {
+// Levels 2 and 3 and the level-1 decoder: the level-2 input t and the level-1 skip connection -> the level-1 decoder output
+// (conv_r1) in *r_out.  The skip connection is the first half of the concat tensor cat1, or (y1.off >= 0, stream_level1) the
+// centre planes of conv_l1's result y1: conv_r1 then reads concat([skip, up]) from two tensors, as the level-0 decoder does.
+static int lower_levels(nbe_ctx* c, Tensor t, Tensor cat1, Tensor y1, Tensor* r_out) {
     const int m = c->mid;
     Tensor y2, cat2, r;
     if (resblock(c, "conv_l2", t, true, true, m, m, &y2)) return 1;
@@ -505,12 +548,22 @@ static int lower_levels(nbe_ctx* c, Tensor t, Tensor cat1, Tensor* r_out) {
     if (resblock(c, "conv_r2", cat2, true, true, m, 2 * m, &r)) return 1;
     tfree(c, cat2);
 
+    const bool two = y1.off >= 0;
+    Tensor sk;
+    if (two) {                                                   // the up-sampled half in a mid-channel tensor of its own
+        cat1 = tallocp(c, m, 2 * r.p.D, y1.p.H - 2, y1.p.W - 2, 1);
+        if (cat1.off < 0) return fail("workspace exhausted (up_r1)");
+        sk = zview(y1, (y1.p.D - 2 * r.p.D) / 2, 2 * r.p.D);
+        set_org(sk, sk.org[0] - 16, y1.org[1] - 16, y1.org[2] - 16);   // the skip connection's frame starts 16 voxels into y1's on every axis
+        set_org(cat1, sk.org[0], sk.org[1], sk.org[2]);
+    }
     // periodic-yx (cat1.pad = 1): the level-2 result carries 2 voxels of y/x context that the periodic level 1 does not need
-    if (upblock(c, "up_r1", r, cat1, cat1.pad ? 2 : 0)) return 1;
+    if (upblock(c, "up_r1", r, cat1, cat1.pad ? 2 : 0, two ? 0 : -1)) return 1;
     fill_halo(c, cat1);
     tfree(c, r);
-    if (resblock(c, "conv_r1", cat1, true, true, m, 2 * m, r_out)) return 1;
+    if (resblock(c, "conv_r1", two ? sk : cat1, true, true, m, 2 * m, r_out, nullptr, nullptr, two ? &cat1 : nullptr)) return 1;
     tfree(c, cat1);
+    if (two) tfree(c, y1);
     return 0;
 }
 
@@ -518,7 +571,7 @@ static int lower_levels(nbe_ctx* c, Tensor t, Tensor cat1, Tensor* r_out) {
 // the level-0 encoder and decoder differ from the z-slab schedule (network_stream).
 int network(nbe_ctx* c, const Tensor& tin, Tensor* yout) {
     const int m = c->mid;
-    Tensor a, y0, t, cat0, cat1, r;
+    Tensor a, y0, t, cat0, cat1, y1, r;
     if (resblock(c, "conv_l00", tin, false, true, m, m, &a)) return 1;
     if (resblock(c, "conv_l01", a, true, true, m, m, &y0)) return 1;
     tfree(c, a);
@@ -528,8 +581,8 @@ int network(nbe_ctx* c, const Tensor& tin, Tensor* yout) {
     if (downblock(c, "down_l0", y0, &t)) return 1;
     tfree(c, y0);
 
-    if (stream_level1(c, 0, false, t, &cat1, &t)) return 1;
-    if (lower_levels(c, t, cat1, &r)) return 1;
+    if (stream_level1(c, 0, false, t, &cat1, &y1, &t)) return 1;
+    if (lower_levels(c, t, cat1, y1, &r)) return 1;
 
     if (upblock(c, "up_r0", r, cat0)) return 1;
     tfree(c, r);
@@ -542,13 +595,14 @@ int network(nbe_ctx* c, const Tensor& tin, Tensor* yout) {
 }
 
 // Everything from the level-2 input on: levels 2-3, the level-1 decoder, then the level-0 decoder slab by slab with the head.
-static int stream_tail(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S, Tensor skip0, Tensor cat1, Tensor t) {
+// (cat1, y1: the level-1 skip connection in either of its forms, lower_levels)
+static int stream_tail(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S, Tensor skip0, Tensor cat1, Tensor y1, Tensor t) {
     const int m = c->mid, pad = tin.pad;
     const int sy = pad ? 0 : 2;
     const Layer *Lr00 = find_layer(c, "conv_r00", "conv_1"), *Lr01 = find_layer(c, "conv_r01", "conv_1");
     if (!Lr00 || !Lr01) return fail("missing conv_1 layers of the level-0 blocks");
     Tensor r;                                                    // the level-1 decoder output
-    if (lower_levels(c, t, cat1, &r)) return 1;
+    if (lower_levels(c, t, cat1, y1, &r)) return 1;
     if (2 * r.p.D != skip0.p.D || 2 * (r.p.H - 2 * r.pad) != skip0.p.H - 2 * pad || 2 * (r.p.W - 2 * r.pad) != skip0.p.W - 2 * pad)
         return fail("internal: level-0 concat geometry mismatch");
 
@@ -567,7 +621,9 @@ static int stream_tail(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S, 
     const bool two = block_fused(c, Lr00, S + 4) && two_source_width(c);
     Tensor cat = tallocp(c, two ? m : 2 * m, S + 8, Hs, Ws, pad), hq = alloc_hidden(c, 2 * m, S + 6, cat, block_fused(c, Lr00, S + 4));
     Tensor q = tallocp(c, m, S + 4, Hs - 2 * sy, Ws - 2 * sy, pad), hy = alloc_hidden(c, m, S + 2, q, block_fused(c, Lr01, S));
-    Tensor y = tallocp(c, c->out_chan, S, Hs - 4 * sy, Ws - 4 * sy, pad);
+    // conv_r01's result: the head reads out_chan channels of its interior and nothing else does -- its padding channel planes are
+    // not zeroed and its y/x halo is not filled
+    Tensor y = tallocp(c, c->out_chan, S, Hs - 4 * sy, Ws - 4 * sy, pad, false);
     if (cat.off < 0 || hq.off < 0 || q.off < 0 || hy.off < 0 || y.off < 0) return fail("workspace exhausted (level-0 decoder slabs)");
     for (int z = 0, n = 0; z < Yo; z += n) {
         n = std::min(S, Yo - z);
@@ -585,10 +641,10 @@ static int stream_tail(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S, 
         const Tensor* up2 = two ? &cat : nullptr;
         if (first) {
             if (resblock_part(c, "conv_r00", sk, hq, q, 0, n + 4, 0, n + 6, true, true, nullptr, up2)) return 1;
-            if (resblock_part(c, "conv_r01", q, hy, y, 0, n, 0, n + 2, true, false, nullptr)) return 1;
+            if (resblock_part(c, "conv_r01", q, hy, y, 0, n, 0, n + 2, true, false, nullptr, nullptr, false)) return 1;
         } else {
             if (resblock_part(c, "conv_r00", sk, hq, q, 4, n, 6, n, true, true, nullptr, up2)) return 1;
-            if (resblock_part(c, "conv_r01", q, hy, y, 0, n, 2, n, true, false, nullptr)) return 1;
+            if (resblock_part(c, "conv_r01", q, hy, y, 0, n, 2, n, true, false, nullptr, nullptr, false)) return 1;
         }
         if (z + n < Yo) {
             carry_planes(c, cat, n, 0, 8);
@@ -633,9 +689,9 @@ int network_stream(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S) {
         }
     }
     if (!zx) {
-        Tensor cat1, t;
-        if (stream_level1(c, pad, pad && c->pz, st.td, &cat1, &t)) return 1;
-        return stream_tail(c, tin, ho, S, st.skip0, cat1, t);
+        Tensor cat1, y1, t;
+        if (stream_level1(c, pad, pad && c->pz, st.td, &cat1, &y1, &t)) return 1;
+        return stream_tail(c, tin, ho, S, st.skip0, cat1, y1, t);
     }
     if (c->phase == 0 || c->phase == 2) {
         if (brick_interior(c, st)) return 1;
@@ -648,11 +704,13 @@ int network_stream(nbe_ctx* c, const Tensor& tin, const HeadOut& ho, int S) {
     Tensor t;
     if (brick_level2(c, st, &t)) return 1;
     st.valid = false;
-    return stream_tail(c, st.tin, ho, st.S, st.skip0, st.cat1, t);
+    return stream_tail(c, st.tin, ho, st.S, st.skip0, st.cat1, Tensor(), t);
 }
 
-// periodic-yx tiles: z as usual; y and x are the box itself (+ 2 halo voxels), a multiple of 8 with room for the
-// 22 voxels of periodic context of the level-1 input
+// periodic-yx tiles: z as usual; y and x are the box itself (+ 2 halo voxels), a multiple of 8 and at least 48, so that the
+// 10 voxels of y/x halo of the level-2 input fit its extent of at least 12.  z has no such bound:
+// a tile that is the whole box in z may be 8 planes deep, and the periodic z context of the level-1 and level-2 inputs
+// (6 and 10 planes) then spans several periods (wrap_z)
 int check_dims_pyx(int D, int H, int W) {
     if (D < 104 || D % 8 != 0) return fail("input depth %d unsupported: must be >= 104 and a multiple of 8", D);
     const int v[2] = {H - 2, W - 2};

@@ -171,6 +171,12 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvKArgs a) {
         long o;
         if (MODE == MODE_DOWN) {
             o = q;
+            if (a.Ho != a.Hv || a.Wo != a.Wv) {                      // the output is the interior of a tensor with a y/x halo
+                const int hw = a.Hv * a.Wv;
+                const int z = (int)(q / hw), rem = (int)(q - (long)z * hw);
+                const int yy = rem / a.Wv, xx = rem - yy * a.Wv;
+                o = ((long)z * a.Ho + yy) * a.Wo + xx;
+            }
         } else {
             const int z = (int)(q / HW), rem = (int)(q - (long)z * HW);
             const int yy = rem / a.W, xx = rem - yy * a.W;
