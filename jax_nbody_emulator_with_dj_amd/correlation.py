@@ -36,8 +36,8 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import NBEError
-from .density import _check_array, _check_los, _device_of, _dtype_name, _is_torch, _ptr, _same_kind, _stream, _triple
+from .density import (_check_array, _check_free_memory, _check_los, _check_max_blocks, _device_of, _dtype_name, _is_torch,
+                      _ptr, _same_kind, _stream, _triple)
 
 try:
     import torch
@@ -121,22 +121,7 @@ def _validate(a, boxsize, r_edges, b, nmu, los, max_blocks):
         if (len(T) - 1) * nmu > MAX_IMAGE:
             raise ValueError("pair_counts: %d x %d bins exceed %d" % (len(T) - 1, nmu, MAX_IMAGE))
     los = _check_los(los)
-    if max_blocks is None:
-        blocks = 0
-    elif isinstance(max_blocks, (bool, np.bool_)) or not isinstance(max_blocks, numbers.Integral) or int(max_blocks) < 1:
-        raise ValueError("pair_counts: _max_blocks must be an int >= 1, got %r" % (max_blocks,))
-    else:
-        blocks = int(max_blocks)
-    return A, B, L[0], edges, T, ncell, nmu, los, blocks
-
-
-def _check_memory(dev, rows):
-    free, _ = torch.cuda.mem_get_info(dev)
-    free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)      # cached blocks are reusable
-    need = BYTES_PER_PARTICLE * rows
-    if need > free:
-        raise NBEError("pair_counts: %d rows need about %.1f GB of device memory (%d bytes each), %.1f GB are free"
-                       % (rows, need / 1e9, BYTES_PER_PARTICLE, free / 1e9))
+    return A, B, L[0], edges, T, ncell, nmu, los, _check_max_blocks(max_blocks, "pair_counts")
 
 
 def _on_device(x, dev):
@@ -219,7 +204,8 @@ def pair_counts(a, boxsize, r_edges, b=None, nmu=None, los=2, _max_blocks=None):
     |x_c / L| >= 2^20 (no partial result is returned); NBEError when the device's free memory cannot take 96 bytes per row."""
     A, B, L, edges, T, ncell, nmu, los, blocks = _validate(a, boxsize, r_edges, b, nmu, los, _max_blocks)
     dev = _device_of(A[0])
-    _check_memory(dev, A[2] + (B[2] if B is not None else 0))
+    rows = A[2] + (B[2] if B is not None else 0)
+    _check_free_memory(dev, BYTES_PER_PARTICLE * rows, "pair_counts: %d rows" % rows, "%d bytes each" % BYTES_PER_PARTICLE)
     counts = _count(A, B, L, T, ncell, 1 if nmu is None else nmu, los, blocks)
     if nmu is None:
         counts = counts.reshape(-1)

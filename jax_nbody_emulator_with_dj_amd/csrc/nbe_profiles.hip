@@ -3,10 +3,10 @@
 // a halo finder such as Rockstar or AHF, which the reference does not have.  No context: these entry points need no
 // weights.
 //
-// Everything that decides a bin is nbe_pairs.hip's, whose inline bodies this file includes: the records, pair_range with
-// half = false (the 27 cells around a centre as at most 18 ranges of the sorted matter) and pair_bin with nmu = 1 (the
-// 32-bit rejection, q in 64 bits, T_b < q <= T_{b+1}).  Nothing about coordinates, the minimum image, the threshold rule or
-// the adjacency of cells is restated here.
+// Everything that decides a bin is the pair count's, from nbe_catalog.h: the records, pair_range with half = false (the 27
+// cells around a centre as at most 18 ranges of the sorted matter), the ranges laid end to end and pair_bin with nmu = 1
+// (the 32-bit rejection, q in 64 bits, T_b < q <= T_{b+1}).  Nothing about coordinates, the minimum image, the threshold
+// rule or the adjacency of cells is restated here; tools/catalog_host_walk.hip walks the per-centre bodies on the host.
 //
 // What differs is the decomposition.  nbe_pair_count adds every row of A into one histogram with one thread per row;
 // a halo catalogue has 10^3 .. 10^4 rows, a few dozen workgroups, and wants one histogram per row.  Here a centre is the
@@ -19,14 +19,16 @@
 // sum of ones: both forms and every launch geometry give the same bits.  nbe_halo_profiles takes the wave form from
 // NBE_PROFILE_WAVE_CENTRES centres on where 27 countB / ncell^3 < NBE_PROFILE_WAVE_BELOW, as measured (section 12.8); a
 // 64-bit image measured the same as the 32-bit one, which is half the LDS.
-//
-// The per-centre bodies are __host__ __device__ so that a stand-alone program can walk them serially on the host
-// (tools/profiles_host_walk.hip); only the LDS image and the launches are device code.
 
-#ifndef NBE_PAIRS_BODIES_ONLY
-#define NBE_PAIRS_BODIES_ONLY 1                            // the pair bodies without their entry points
-#endif
-#include "nbe_pairs.hip"
+#include "../../include/nbe.h"
+#include "nbe_catalog.h"
+#include "nbe_spectral.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+using namespace nbe;
 
 namespace {
 
@@ -39,37 +41,6 @@ using ProfileCounter = unsigned long long;
 #else
 using ProfileCounter = unsigned int;
 #endif
-
-// range t of the centre `me` in the sorted matter: rlo[t], rlen[t]
-__host__ __device__ inline void profile_range(const FofParticle& me, const long long* skB, long long countB, int ncell, int t,
-                                              long long* rlo, long long* rlen) {
-    long long lo, hi;
-    pair_range(skB, countB, fof_cell(me.x0, ncell), fof_cell(me.x1, ncell), fof_cell(me.x2, ncell), ncell, false, t, &lo, &hi);
-    rlo[t] = lo; rlen[t] = hi - lo;
-}
-
-__host__ __device__ inline long long profile_total(const long long* rlen) {
-    long long total = 0;
-    for (int t = 0; t < kPairRanges; ++t) total += rlen[t];
-    return total;
-}
-
-// the sorted position of record q of the ranges laid end to end, 0 <= q < profile_total
-__host__ __device__ inline long long profile_locate(const long long* rlo, const long long* rlen, long long q) {
-    int t = 0;
-    for (long long len = rlen[0]; q >= len; len = rlen[++t]) q -= len;
-    return rlo[t] + q;
-}
-
-// records first, first + step, ... of the centre's ranges: add(bin or -1) for each
-template <typename Add>
-__host__ __device__ inline void profile_stream(const FofParticle& me, const FofParticle* B, const long long* rlo,
-                                               const long long* rlen, long long total, long long first, long long step,
-                                               const long long* T, int nb, int s, Add add) {
-    for (long long q = first; q < total; q += step) add(pair_bin(me, B[profile_locate(rlo, rlen, q)], T, nb, s, 1, 0));
-}
-
-#if defined(__HIPCC__)
 
 // what one wave wrote to LDS becomes visible to its other lanes (no workgroup barrier: the waves run apart)
 __device__ inline void profile_wave_sync() {
@@ -94,7 +65,7 @@ __global__ __launch_bounds__(kProfileThreads) void profile_group_kernel(const Fo
         if (tid < kPairRanges) profile_range(me, skB, countB, ncell, tid, rlo, rlen);
         for (int b = tid; b < nb; b += kProfileThreads) image[b] = 0;
         __syncthreads();
-        profile_stream(me, B, rlo, rlen, profile_total(rlen), tid, kProfileThreads, T, nb, s,
+        profile_stream(me, B, rlo, rlen, pair_ranges_total(rlen), tid, kProfileThreads, T, nb, s,
                        [&](int b) { if (b >= 0) atomicAdd(&image[b], (ProfileCounter)1); });
         __syncthreads();
         unsigned long long* row = counts + (long long)me.p * nb;
@@ -122,7 +93,7 @@ __global__ __launch_bounds__(kProfileThreads) void profile_wave_kernel(const Fof
         if (lane < kPairRanges) profile_range(me, skB, countB, ncell, lane, rlo, rlen);
         for (int b = lane; b < nb; b += kProfileWave) image[b] = 0;
         profile_wave_sync();
-        profile_stream(me, B, rlo, rlen, profile_total(rlen), lane, kProfileWave, T, nb, s,
+        profile_stream(me, B, rlo, rlen, pair_ranges_total(rlen), lane, kProfileWave, T, nb, s,
                        [&](int b) { if (b >= 0) atomicAdd(&image[b], (ProfileCounter)1); });
         profile_wave_sync();
         unsigned long long* row = counts + (long long)me.p * nb;
@@ -131,21 +102,13 @@ __global__ __launch_bounds__(kProfileThreads) void profile_wave_kernel(const Fof
     }
 }
 
-#endif  // __HIPCC__
-
-}  // namespace
-
-#if defined(__HIPCC__) && !defined(NBE_PROFILES_BODIES_ONLY)
-
-namespace {
-
 int halo_profiles_launch(const void* sortedA, const void* keysA, int64_t countA, const void* sortedB, const void* keysB,
                          int64_t countB, int ncell, const int64_t* thresholds, int nbins, int max_blocks, int form,
                          void* counts, void* stream) {
     if (!sortedA || !keysA || !sortedB || !keysB || !thresholds || !counts) return fail("nbe_halo_profiles: NULL argument");
-    if (countA < 1 || countA > (1LL << 30) || countB < 1 || countB > (1LL << 30))
+    if (!count_ok(countA) || !count_ok(countB))
         return fail("nbe_halo_profiles: bad row counts %lld, %lld", (long long)countA, (long long)countB);
-    if (ncell < 3 || ncell > NBE_FOF_MAX_CELLS) return fail("nbe_halo_profiles: ncell %d not in 3 .. %d", ncell, NBE_FOF_MAX_CELLS);
+    if (int rc = check_ncell("nbe_halo_profiles", ncell)) return rc;
     if (nbins < 1 || nbins > NBE_PAIR_MAX_BINS) return fail("nbe_halo_profiles: nbins %d not in 1 .. %d", nbins, NBE_PAIR_MAX_BINS);
     if (form < -1 || form > 1) return fail("nbe_halo_profiles_form: form %d not in 0 .. 1", form);
     // the library's choice: a wave per centre where there are centres enough to fill the card with waves and the 27 cells
@@ -154,16 +117,8 @@ int halo_profiles_launch(const void* sortedA, const void* keysA, int64_t countA,
         form = countA >= NBE_PROFILE_WAVE_CENTRES &&
                27.0 * (double)countB < (double)NBE_PROFILE_WAVE_BELOW * ncell * ncell * ncell ? 1 : 0;
     PairBins bins;
-    for (int b = 0; b <= nbins; ++b) {
-        bins.T[b] = thresholds[b];
-        if (b ? thresholds[b] <= thresholds[b - 1] : thresholds[0] < -1)
-            return fail("nbe_halo_profiles: the thresholds must increase strictly from -1 or more");
-    }
-    // the cells must be at least isqrt(T_nb) + 1 units wide (the adjacency argument): ncell (s + 1) <= 2^30
-    const long long room = (1LL << kCoordBits) / ncell - 1, top = bins.T[nbins];
-    if (top < 0 || top >= (room + 1) * (room + 1))
-        return fail("nbe_halo_profiles: threshold %lld needs cells wider than 2^30 / %d", top, ncell);
-    const int s = (int)pair_isqrt(top);
+    int s;
+    if (int rc = check_thresholds("nbe_halo_profiles", thresholds, nbins, ncell, &bins, &s)) return rc;
     long long g = form ? (countA + kProfileWaves - 1) / kProfileWaves : countA;
     if (g > kProfileMaxGrid) g = kProfileMaxGrid;
     if (max_blocks > 0 && max_blocks < g) g = max_blocks;
@@ -200,5 +155,3 @@ int nbe_halo_profiles_form(const void* sortedA, const void* keysA, int64_t count
 }
 
 }  // extern "C"
-
-#endif

@@ -1,6 +1,9 @@
-// Pieces shared by the context-free entry points (nbe_density.hip, nbe_lpt.hip): how a mode of torch's row-major half
-// spectrum is decoded, and how such an entry point reports an error and sizes a launch.  Each is written once, here.
+// Pieces shared by the context-free entry points (nbe_density.hip, nbe_lpt.hip, nbe_fof.hip, nbe_pairs.hip,
+// nbe_profiles.hip): how a mode of torch's row-major half spectrum is decoded, and how such an entry point reports an
+// error, checks an argument of a catalogue and sizes a launch.  Each is written once, here.
 #pragma once
+
+#include "nbe_catalog.h"
 
 #include <hip/hip_runtime.h>
 
@@ -45,6 +48,43 @@ __device__ inline HalfMode half_mode(long long i, long long r0, long long r1, lo
 [[maybe_unused]] int grid_for(long long n, int threads) {
     long long g = (n + threads - 1) / threads;
     return (int)(g < 1 ? 1 : g > 65536 ? 65536 : g);
+}
+
+// the grid of a catalogue kernel of 256 threads with one row a thread, capped by the caller's max_blocks
+[[maybe_unused]] int fof_grid(long long count, int max_blocks) {
+    const int g = grid_for(count, 256);
+    return max_blocks > 0 && max_blocks < g ? max_blocks : g;
+}
+
+// The arguments of the catalogue entry points, one check per kind; `what` is the entry point's name.
+[[maybe_unused]] bool count_ok(long long count) { return count >= 1 && count <= (1LL << 30); }
+
+[[maybe_unused]] int check_count(const char* what, long long count) {
+    return count_ok(count) ? 0 : fail("%s: bad particle count %lld", what, count);
+}
+
+[[maybe_unused]] int check_ncell(const char* what, int ncell) {
+    return ncell >= 3 && ncell <= NBE_FOF_MAX_CELLS ? 0 : fail("%s: ncell %d not in 3 .. %d", what, ncell, NBE_FOF_MAX_CELLS);
+}
+
+[[maybe_unused]] int check_boxsize(const char* what, double boxsize) {
+    return boxsize > 0.0 && std::isfinite(boxsize) ? 0 : fail("%s: bad boxsize %g", what, boxsize);
+}
+
+// thresholds[0 .. nbins] into *bins, and *s = isqrt of the last: they increase strictly from -1 or more, and the cells are
+// at least s + 1 units wide (the adjacency argument of nbe_catalog.h): ncell (s + 1) <= 2^30
+[[maybe_unused]] int check_thresholds(const char* what, const int64_t* thresholds, int nbins, int ncell, nbe::PairBins* bins,
+                                      int* s) {
+    for (int b = 0; b <= nbins; ++b) {
+        bins->T[b] = thresholds[b];
+        if (b ? thresholds[b] <= thresholds[b - 1] : thresholds[0] < -1)
+            return fail("%s: the thresholds must increase strictly from -1 or more", what);
+    }
+    const long long room = (1LL << nbe::kCoordBits) / ncell - 1, top = bins->T[nbins];
+    if (top < 0 || top >= (room + 1) * (room + 1))
+        return fail("%s: threshold %lld needs cells wider than 2^30 / %d", what, top, ncell);
+    *s = (int)nbe::pair_isqrt(top);
+    return 0;
 }
 
 }  // namespace

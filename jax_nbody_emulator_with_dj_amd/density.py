@@ -267,6 +267,27 @@ def _same_kind(a, b, name_a, name_b):
         raise ValueError("%s and %s must both be NumPy arrays or both tensors on one device" % (name_a, name_b))
 
 
+def _check_max_blocks(max_blocks, who):
+    """The cap on the grid of every launch as the C side takes it: 0 for None, else the int >= 1."""
+    if max_blocks is None:
+        return 0
+    if isinstance(max_blocks, (bool, np.bool_)) or not isinstance(max_blocks, numbers.Integral) or int(max_blocks) < 1:
+        raise ValueError("%s: _max_blocks must be an int >= 1, got %r" % (who, max_blocks))
+    return int(max_blocks)
+
+
+def _free_memory(dev):
+    free, _ = torch.cuda.mem_get_info(dev)
+    return free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)     # cached blocks are reusable
+
+
+def _check_free_memory(dev, need, what, detail):
+    """NBEError "<what> need about .. GB of device memory (<detail>), .. GB are free" where `need` bytes are not free."""
+    free = _free_memory(dev)
+    if need > free:
+        raise NBEError("%s need about %.1f GB of device memory (%s), %.1f GB are free" % (what, need / 1e9, detail, free / 1e9))
+
+
 def _validate_field(displacement, quantity, boxsize, res, worder, normalize, fill, velocity, los, velocity_to_length):
     q = _check_array(quantity, "quantity")
     if q.ndim not in (3, 4) or min(q.shape) < 1 or (q.ndim == 4 and q.shape[0] > _MAX_CHANNELS):
@@ -1026,8 +1047,7 @@ def _bk_batch(dev, n, want, max_batch):
     workspace: four fields of 4 n^3 bytes are reserved for each."""
     if max_batch is not None:
         return max(1, min(int(max_batch), want))
-    free, _ = torch.cuda.mem_get_info(dev)
-    free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)      # cached blocks are reusable
+    free = _free_memory(dev)
     per_shell = 16 * (n ** 3 + 2 * n * n)
     return max(1, min(want, int(0.7 * free) // per_shell))
 

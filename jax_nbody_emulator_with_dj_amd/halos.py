@@ -47,9 +47,8 @@ import sys
 import numpy as np
 
 from . import _lib
-from ._lib import NBEError
-from .density import (_back, _check_array, _check_los, _device_of, _dtype_name, _is_torch, _ptr, _real, _same_kind, _stream,
-                      _to_device, _triple)
+from .density import (_back, _check_array, _check_free_memory, _check_los, _check_max_blocks, _device_of, _dtype_name,
+                      _is_torch, _ptr, _real, _same_kind, _stream, _to_device, _triple)
 
 try:
     import torch
@@ -111,17 +110,7 @@ def _validate(displacement, boxsize, linking_length, nmin, absolute, velocity, m
         if _dtype_name(v) not in ("float32", "float16"):
             raise ValueError("fof_halos: velocity must be float32 or float16, got %s" % _dtype_name(v))
         _same_kind(x, v, "fof_halos: displacement", "velocity")
-    blocks = 0 if max_blocks is None else _int(max_blocks, "_max_blocks", 1)
-    return x, n, L[0], nmin, ell, R2, ncell, v, blocks
-
-
-def _check_memory(dev, count):
-    free, _ = torch.cuda.mem_get_info(dev)
-    free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)      # cached blocks are reusable
-    need = BYTES_PER_PARTICLE * count
-    if need > free:
-        raise NBEError("fof_halos: %d particles need about %.1f GB of device memory (%d bytes each), %.1f GB are free"
-                       % (count, need / 1e9, BYTES_PER_PARTICLE, free / 1e9))
+    return x, n, L[0], nmin, ell, R2, ncell, v, _check_max_blocks(max_blocks, "fof_halos")
 
 
 def _velocity_exponents(l, vd, count, s, dev):
@@ -220,7 +209,7 @@ def fof_halos(displacement, boxsize=1000.0, linking_length=0.2, nmin=20, absolut
     x, n, L, nmin, ell, R2, ncell, v, blocks = _validate(displacement, boxsize, linking_length, nmin, absolute, velocity,
                                                          _max_blocks)
     dev = _device_of(x)
-    _check_memory(dev, n ** 3)
+    _check_free_memory(dev, BYTES_PER_PARTICLE * n ** 3, "fof_halos: %d particles" % n ** 3, "%d bytes each" % BYTES_PER_PARTICLE)
     dtypes = (torch.float32, torch.float16)
     xd = _to_device(x, dev, dtypes)
     vd = None if v is None else _to_device(v, dev, dtypes)

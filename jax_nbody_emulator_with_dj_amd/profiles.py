@@ -34,9 +34,8 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import NBEError
 from . import correlation as CF
-from .density import _device_of, _is_torch, _ptr, _same_kind, _stream, _triple
+from .density import _check_free_memory, _check_max_blocks, _device_of, _is_torch, _ptr, _same_kind, _stream, _triple
 
 try:
     import torch
@@ -68,24 +67,10 @@ def _validate(centres, matter, boxsize, r_edges, max_blocks, form):
     if len(set(L)) != 1:
         raise ValueError("radial_counts needs a cubic box, got boxsize %s" % (L,))
     edges, T, ncell = CF.pair_geometry(L[0], r_edges)
-    if max_blocks is None:
-        blocks = 0
-    elif isinstance(max_blocks, (bool, np.bool_)) or not isinstance(max_blocks, numbers.Integral) or int(max_blocks) < 1:
-        raise ValueError("radial_counts: _max_blocks must be an int >= 1, got %r" % (max_blocks,))
-    else:
-        blocks = int(max_blocks)
+    blocks = _check_max_blocks(max_blocks, "radial_counts")
     if form is not None and (isinstance(form, (bool, np.bool_)) or form not in FORMS):
         raise ValueError("radial_counts: _form must be None, 0 or 1, got %r" % (form,))
     return A, B, L[0], edges, T, ncell, blocks, form
-
-
-def _check_memory(dev, rows, H, nb):
-    free, _ = torch.cuda.mem_get_info(dev)
-    free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)      # cached blocks are reusable
-    need = CF.BYTES_PER_PARTICLE * rows + 8 * H * nb
-    if need > free:
-        raise NBEError("radial_counts: %d rows and %d x %d counts need about %.1f GB of device memory (%d bytes a row, 8 a "
-                       "count), %.1f GB are free" % (rows, H, nb, need / 1e9, CF.BYTES_PER_PARTICLE, free / 1e9))
 
 
 def _count(A, B, L, T, ncell, blocks, form=None, timer=None, records=None):
@@ -131,7 +116,9 @@ def radial_counts(centres, matter, boxsize, r_edges, _max_blocks=None, _form=Non
     of both catalogues plus 8 H nb for the counts."""
     A, B, L, edges, T, ncell, blocks, form = _validate(centres, matter, boxsize, r_edges, _max_blocks, _form)
     dev = _device_of(A[0])
-    _check_memory(dev, A[2] + B[2], A[2], len(T) - 1)
+    rows, H, nb = A[2] + B[2], A[2], len(T) - 1
+    _check_free_memory(dev, CF.BYTES_PER_PARTICLE * rows + 8 * H * nb, "radial_counts: %d rows and %d x %d counts" % (rows, H, nb),
+                       "%d bytes a row, 8 a count" % CF.BYTES_PER_PARTICLE)
     counts = _count(A, B, L, T, ncell, blocks, form)
     tens = _is_torch(A[0])
     kind = (lambda v: torch.from_numpy(v).to(dev)) if tens else (lambda v: v)
