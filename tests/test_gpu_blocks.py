@@ -34,6 +34,7 @@ TOL = {"f32": (RTOL_L2, RTOL_MAX), "f16": (RTOL_L2_F16, RTOL_MAX_F16), "f16w": (
 
 _PARAMS = {}
 WORST = {}                                    # (stage, arithmetic, tolerance class) -> [rel-L2, max/RMS]
+_TABLE = [WORST]                              # the table run_case is filling: WORST, or another kind of tree's (Tree.worst)
 T0 = [None]
 
 
@@ -62,26 +63,42 @@ def _gauge_deviation():
 GAUGE_DEV = _gauge_deviation()
 
 
+class Tree:
+    """A kind of parameter tree the block cases run on: source(mid, vel) -> what block_ref evaluates (its .tree is loaded
+    where premodulated), the expected fusion, the deviation the returned gauge vectors are held to (4 x), and the table of
+    worst figures its cases fill."""
+    def __init__(self, source, expect_fused, gauge_dev, premodulated=False, gauge_active=True):
+        self.source, self.expect_fused, self.gauge_dev = source, expect_fused, gauge_dev
+        self.premodulated, self.gauge_active, self.worst = premodulated, gauge_active, {}
+
+
+TREES = {}                                    # "style" below; tests/test_gpu_blocks_premod.py adds the premodulated kinds
+
+
 @pytest.fixture(scope="module")
 def engines(engine_factory):
     made = {}
 
-    def get(mid, prec, vel, gauge=True):
-        key = (mid, prec, vel, gauge)
+    def get(mid, prec, vel, gauge=True, tree="style"):
+        key = (mid, prec, vel, gauge, tree)
+        tr = TREES[tree]
         if key not in made:
             keep = os.environ.get("NBE_GAUGE")
             if not gauge:
                 os.environ["NBE_GAUGE"] = "0"                    # read when the weights are loaded
             try:
                 e = engine_factory(mid_chan=mid, precision=prec, compute_vel=vel)
-                e.load_params(params_of(mid), False)
-                e.set_cosmology(OM, DZ)
+                if tr.premodulated:
+                    e.load_params(tr.source(mid, vel).tree, True)
+                else:
+                    e.load_params(params_of(mid), False)
+                    e.set_cosmology(OM, DZ)
             finally:
                 if not gauge:
                     os.environ.pop("NBE_GAUGE")
                     if keep is not None:
                         os.environ["NBE_GAUGE"] = keep
-            assert bool(e.query("gauge_active")) == (vel and gauge)
+            assert bool(e.query("gauge_active")) == (vel and gauge and tr.gauge_active)
             made[key] = e
         return made[key]
     if T0[0] is None:
@@ -136,10 +153,14 @@ def expect_fused(block, mid, prec, vel, gauge, nres, wino_on):
     return False
 
 
+TREES["style"] = Tree(lambda mid, vel: params_of(mid), expect_fused, GAUGE_DEV)
+TREES["style"].worst = WORST
+
+
 # ---- checks -------------------------------------------------------------------------------------------------------------
 
 def _note(stage, arith, cls, e2, em):
-    w = WORST.setdefault((stage, arith, cls), [0.0, 0.0])
+    w = _TABLE[0].setdefault((stage, arith, cls), [0.0, 0.0])
     w[0], w[1] = max(w[0], e2), max(w[1], em)
 
 
@@ -180,13 +201,14 @@ def check_branches(branch, pre, what, cls):
         assert worst <= TOL[cls][1], "%s: a branch differs where the pre-activation is %.2e RMS from zero" % (what, worst)
 
 
-def check_gauges(r, g, what):
+def check_gauges(r, g, what, gauge_dev=None):
+    gauge_dev = GAUGE_DEV if gauge_dev is None else gauge_dev
     for name, got, want in zip(("input", "hidden", "output"), (r["gauge_in"], r["gauge_hidden"], r["gauge_out"]), g):
         if want is None:
             continue
         dev = float(np.abs(got.astype(np.float64) - want).max())
-        assert got.shape == want.shape and dev <= 4 * GAUGE_DEV, \
-            "%s: %s gauge deviates from the float64 table by %.2e (float32 evaluation: %.2e)" % (what, name, dev, GAUGE_DEV)
+        assert got.shape == want.shape and dev <= 4 * gauge_dev, \
+            "%s: %s gauge deviates from the float64 table by %.2e (float32 evaluation: %.2e)" % (what, name, dev, gauge_dev)
     return max(float(np.abs(got.astype(np.float64) - want).max()) for got, want in
                zip((r["gauge_in"], r["gauge_hidden"], r["gauge_out"]), g) if want is not None)
 
@@ -205,10 +227,12 @@ def make_input(block, mid, prec, vel, shape, g_in):
     return x, dxs
 
 
-def run_case(e, block, mid, prec, vel, shape, gauge=True, wino_on=True, forms=("cat", "two")):
+def run_case(e, block, mid, prec, vel, shape, gauge=True, wino_on=True, forms=("cat", "two"), tree="style"):
     """one block on one shape: stages, branches, gauges, paths; returns {form: engine result}"""
     D, H, W, pad = shape
-    p, s = params_of(mid), s64()
+    tr = TREES[tree]
+    _TABLE[0] = tr.worst
+    p, s = tr.source(mid, vel), s64()
     half = prec == "f16"
     table = B.gauges(p, s, block, mid)
     g = table if (gauge and vel) else tuple(None if t is None else np.zeros_like(t) for t in table)
@@ -242,14 +266,14 @@ def run_case(e, block, mid, prec, vel, shape, gauge=True, wino_on=True, forms=("
             if vel:
                 check(dy, dys_o, "%s (%s) tangent" % (block, form), cls, "resample", arith)
                 check_branches(br, S.p, "%s (%s)" % (block, form), cls)
-                print("    gauges: worst deviation from the float64 table %.2e (float32 evaluation %.2e)" % (check_gauges(r, g, block), GAUGE_DEV))
+                print("    gauges: worst deviation from the float64 table %.2e (float32 evaluation %.2e)" % (check_gauges(r, g, block, tr.gauge_dev), tr.gauge_dev))
             assert ("up8" in r["paths"]) == (up and prec != "f32"), r["paths"]
             assert not r["paths"] & {"skip_fused", "two_source", "narrow"}, r["paths"]
             out[form] = r
         return out
 
     nres = D - 4
-    fused = expect_fused(block, mid, prec, vel, gauge, nres, wino_on)
+    fused = tr.expect_fused(block, mid, prec, vel, gauge, nres, wino_on)
     dec = block in B.DECODERS
     todo = [("cat", False)]
     if dec and "two" in forms and mid % (32 if half else 16) == 0 and fused:
@@ -295,7 +319,7 @@ def run_case(e, block, mid, prec, vel, shape, gauge=True, wino_on=True, forms=("
             check(r["dy"], dys_o, "%s (%s) result tangent" % (block, form), c2, st2, arith)
             if act:
                 check_branches(br, S2.p, "%s (%s) result" % (block, form), c2)
-            print("    gauges: worst deviation from the float64 table %.2e (float32 evaluation %.2e)" % (check_gauges(r, g, block), GAUGE_DEV))
+            print("    gauges: worst deviation from the float64 table %.2e (float32 evaluation %.2e)" % (check_gauges(r, g, block, tr.gauge_dev), tr.gauge_dev))
     if "two" in out:
         # the two forms read the same numbers: they agree to the stage tolerance, and bit for bit on the direct f16x3 kernel
         a, b = out["two"], out["cat"]

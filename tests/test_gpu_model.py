@@ -242,6 +242,51 @@ def test_float16_mode(engine_factory, small, monkeypatch):
     assert rel_l2(d0_, gold["net64_disp"]) <= 2e-3 and rel_l2(v0_, gold["net64_vel"]) <= 4e-2
 
 
+def test_float16_mode_on_a_premodulated_tree(engine_factory, small):
+    """The float16 engine on the tree of modulate_emulator_parameters_vel: the gauge is recovered from the (W, dW) pairs
+    (wire_gauge_premod) and the gauged kernels run, but no skip is fused -- the float16 model gets a skip's Winograd-z pack
+    with a style tree only -- so all nine skips are launches of their own whose results conv_1 reads back as float16
+    residuals.  Same fixture and bounds as test_float16_mode (rel-L2 <= 2e-3 / 4e-2 against the float64 oracle), then
+    production width against the golden fixture, where the Winograd-z form (conv_h1w) does run."""
+    import os
+    from oracle import params as P
+    p, x, d_o, v_o = small
+    e = engine_factory(mid_chan=8, compute_vel=True, precision="f16")
+    e.load_params(P.premodulate_vel(p, 0.5, OM), premodulated=True)
+    assert int(e.query("gauge_active")) == 1
+    e.profile_reset(); e.profile_enable(True)
+    d, v = e.forward(x, DZ, VF)
+    e.profile_enable(False)
+    prof = e.profile_read()
+    assert np.all(np.isfinite(d)) and np.all(np.isfinite(v))
+    print("f16 premodulated mid8: disp rel_l2 %.3e vel rel_l2 %.3e" % (rel_l2(d, d_o), rel_l2(v, v_o)))
+    assert rel_l2(d, d_o) <= 2e-3 and rel_l2(v, v_o) <= 4e-2
+    assert any(k["kernel"].startswith("conv_h1g") for k in prof), [k["kernel"] for k in prof]
+    assert sum(k["launches"] for k in prof if k["kernel"].startswith("conv_h1<FLAT1,vel,dx>")) == 9 - 1
+    d2, v2 = e.forward(x, DZ, VF)
+    assert np.array_equal(d, d2) and np.array_equal(v, v2)
+
+    gold = np.load(os.path.join(os.path.dirname(__file__), "golden", "golden_v1.npz"))
+    seed_p, seed_x, mid, d0, d1, d2_ = (int(t) for t in gold["net64_meta"])
+    p = P.synthetic_params(seed=seed_p, mid_chan=mid)
+    x = np.random.default_rng(seed_x).standard_normal((1, 3, d0, d1, d2_)).astype(np.float32)[0]
+    e = engine_factory(mid_chan=mid, compute_vel=True, precision="f16")
+    e.load_params(P.premodulate_vel(p, 0.5, OM), premodulated=True)
+    assert int(e.query("gauge_active")) == 1
+    e.profile_reset(); e.profile_enable(True)
+    d, v = e.forward(x, DZ, VF)
+    e.profile_enable(False)
+    prof = e.profile_read()
+    names = [k["kernel"] for k in prof]
+    print("f16 premodulated mid64: disp rel_l2 %.3e vel rel_l2 %.3e" % (rel_l2(d, gold["net64_disp"]), rel_l2(v, gold["net64_vel"])))
+    assert rel_l2(d, gold["net64_disp"]) <= 2e-3 and rel_l2(v, gold["net64_vel"]) <= 4e-2
+    # the Winograd-z form runs, and none of its launches carries a skip: every skip with an input tangent is a launch of the
+    # general 1x1x1 kernel (conv_l00's, without one, has another kernel name), as under NBE_WINO=0 on a style tree
+    assert any(n.startswith("conv_h1w<FLAT3") for n in names), names
+    assert sum(k["launches"] for k in prof if k["kernel"].startswith("conv_h1<FLAT1,vel,dx>")) == 9 - 1
+    assert sum(k["launches"] for k in prof if k["kernel"].startswith("conv_h1<FLAT1,vel,nodx>")) == 1
+
+
 def test_full_width_c1_slice(engine_factory):
     """mid_chan=64 (production width) on the smallest legal input, against the committed golden
     fixture (float64 oracle output, tests/golden/make_golden.py), both arithmetic modes."""
