@@ -100,8 +100,12 @@ def _conv_valid_s1(x, w, zblock=8):
     assert Cin == Cin2, (x.shape, w.shape)
     Do, Ho, Wo = D - k + 1, H - k + 1, W - k + 1
     xl = np.ascontiguousarray(np.moveaxis(x, 0, -1))      # (D,H,W,Cin)
-    sz, sy, sx, sc = xl.strides
-    v = as_strided(xl, shape=(D, H, Wo, k * Cin), strides=(sz, sy, sx, sc), writeable=False)
+    # (the strides written out: NumPy leaves an axis of length 1 -- Cin = 1 -- whatever stride the view had)
+    sc = xl.itemsize
+    sx = Cin * sc
+    sy = W * sx
+    sz = H * sy
+    v =as_strided(xl, shape=(D, H, Wo, k * Cin), strides=(sz, sy, sx, sc), writeable=False)
     wt = np.ascontiguousarray(np.transpose(w, (2, 3, 4, 1, 0))).reshape(k, k, k * Cin, Cout)
     out = np.empty((Do, Ho, Wo, Cout), dtype=x.dtype)
     for z0 in range(0, Do, zblock):
