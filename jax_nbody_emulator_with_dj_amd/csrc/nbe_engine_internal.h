@@ -3,7 +3,7 @@
 #pragma once
 
 #include "../../include/nbe.h"
-#include "nbe_kernels.h"
+#include "nbe_conv_select.h"
 
 #include <cmath>
 #include <cstdarg>

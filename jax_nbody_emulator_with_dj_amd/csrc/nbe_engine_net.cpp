@@ -74,26 +74,14 @@ static void org_conv(const Tensor& x, int nconv, int out[3]) {
 }
 void set_org(Tensor& t, int z, int y, int x) { t.org[0] = z; t.org[1] = y; t.org[2] = x; }
 
-static std::string conv_name(const PackedW& pw, bool vel, bool has_dx, bool g6 = false, bool up8 = false) {
-    if (up8) return vel ? "up_h3<8 parities,vel,dx>" : "up_h3<8 parities,novel>";
-    const char* m = pw.mode == MODE_FLAT3 ? "FLAT3" : pw.mode == MODE_FLAT1 ? "FLAT1" : "DOWN";
-    if (pw.stem && !(vel && has_dx) && pw.mode == MODE_FLAT3) return vel ? "stem_h3<FLAT3,vel,nodx>" : "stem_h3<FLAT3,novel>";
-    char b[96];
-    if (g6 && prec_is_half(pw.prec)) snprintf(b, sizeof b, "%s<%s,vel,dx>", pw.prec == PREC_F16 ? "conv_h1g" : (pw.cout_t == 16 ? "conv_h3n" : "conv_h3g"), m);
-    else if (g6) snprintf(b, sizeof b, "conv_mfma_g<%s,vel,dx,ni%d>", m, pw.ni);
-    else if (prec_is_half(pw.prec))
-        snprintf(b, sizeof b, "%s<%s,%s,%s>", pw.prec == PREC_F16 ? "conv_h1" : "conv_h3", m, vel ? "vel" : "novel", (vel && has_dx) ? "dx" : "nodx");
-    else
-        snprintf(b, sizeof b, "conv_mfma<%s,%s,%s,ni%d>", m, vel ? "vel" : "novel", (vel && has_dx) ? "dx" : "nodx", pw.ni);
-    return b;
+// the float16 model's Winograd-z form (conv_h3w_kernel<., ., F16>): whole 32-channel stages
+bool wino_f16_layer(int prec, bool vel, int cin_pad) {
+    return prec == PREC_F16 && vel && cin_pad % (H3_CHUNK * H3W_F16_CHUNKS) == 0 && h3w_stages_fit(cin_pad, H3W_F16_CHUNKS);
 }
-
-// the float16 model's Winograd-z form (conv_h3w_kernel<., ., F16>): 32-channel stages
-bool wino_f16_layer(int prec, bool vel, int cin_pad) { return prec == PREC_F16 && vel && cin_pad % 32 == 0 && cin_pad / 32 <= 8; }
 bool wino_env_off() { return getenv("NBE_WINO") && atoi(getenv("NBE_WINO")) == 0; }   // A/B switch, read per launch
 // f16-based arithmetic, Cin <= 64 and an input tangent wherever there is velocity: all eight parities of an up-sampling
 // in one launch (up_h3_kernel: the input is read once)
-bool up8_launch(const nbe_ctx* c, const Layer& L, bool has_dx) { return prec_is_half(c->prec) && (!c->vel || has_dx) && L.pw.cin_pad <= 64; }
+bool up8_launch(const nbe_ctx* c, const Layer& L, bool has_dx) { return prec_is_half(c->prec) && (!c->vel || has_dx) && up8_fits(L.pw.cin_pad); }
 
 // launch one convolution layer (or record it in a dry run)
 int run_conv(nbe_ctx* c, const Layer& L, const ConvLaunch& cl_in, bool has_dx) {
@@ -107,31 +95,29 @@ int run_conv(nbe_ctx* c, const Layer& L, const ConvLaunch& cl_in, bool has_dx) {
         cl.bias = L.bias_f;
     }
     const PackedW& pw = (g6 && L.kind == 0 && L.pwn.w) ? L.pwn : L.pw;
-    // Winograd along z (conv_h3w_kernel): gauged wide 3x3x3 launches without a fused skip or residual, on an even number
-    // of output planes (the conditions of launch_h3w).  NBE_WINO=0 is the A/B switch (read per launch: tests flip it).
-    // (the float16 model's form adds the residual in its epilogue: its blocks run their skips as launches of their own)
-    cl.wino = (g6 || nov) && c->wino_ok && &pw == &L.pw && pw.ww && (!cl.skw || cl.skw->ww) && (c->prec == PREC_F16 || !(cl.flags & F_RES)) &&
-              (cl.Dv & 1) == 0 && cl.in_off == 0 && cl.osz == 1 && !c->direct_z && !wino_env_off();
-    if (c->paths)
-        *c->paths |= (cl.skw ? NBE_PATH_SKIP_FUSED : 0) | (cl.skw && (cl.flags & F_SKIP_NODX) ? NBE_PATH_SKIP_NODX : 0) |
-                     (cl.csplit_ch ? NBE_PATH_TWO_SOURCE : 0) | (cl.skw && cl.sk_split_ch ? NBE_PATH_TWO_SOURCE_SKIP : 0) |
-                     (cl.wino ? (L.layer == "conv_1" ? NBE_PATH_WINO_1 : NBE_PATH_WINO_0) : 0) |
-                     (&pw == &L.pwn ? NBE_PATH_NARROW : 0) | (cl.set < 0 ? NBE_PATH_UP8 : 0);
-    int pe = -1; hipEvent_t ea = nullptr, eb = nullptr;
+    // Winograd along z (conv_h3w_kernel) is allowed: policy only -- whether this launch has that form is conv_select's
+    // decision.  NBE_WINO=0 is the A/B switch (read per launch: tests flip it).
+    cl.wino = c->wino_ok && !c->direct_z && !wino_env_off();
+    hipEvent_t ea = nullptr, eb = nullptr;
     if (c->prof) {
-        std::string pn = cl.wino ? std::string(c->prec == PREC_F16 ? "conv_h1w<FLAT3,vel,dx>" : c->vel ? "conv_h3w<FLAT3,vel,dx>" : "conv_h3w<FLAT3,novel>")
-                                 : conv_name(pw, c->vel, has_dx, g6, cl.set < 0);
-        static const bool per_layer = getenv("NBE_PROF_LAYERS") && atoi(getenv("NBE_PROF_LAYERS")) == 1;   // tools: one entry per layer
-        if (per_layer) pn += " " + L.block + "/" + L.layer;
-        pe = prof_entry(c, pn);
         ea = get_event(c); eb = get_event(c);
         (void)hipEventRecord(ea, c->stream);
     }
-    if (launch_conv(pw, cl, c->vel, has_dx, c->stream))
-        return fail("internal error: no kernel for layer %s/%s (mode %d, gauged %d, input tangent %d, crop offset %ld, output stride %d)",
-                    L.block.c_str(), L.layer.c_str(), L.pw.mode, (int)g6, (int)has_dx, (long)cl.in_off, cl.osz);
+    ConvKernel k;
+    if (launch_conv(pw, cl, c->vel, has_dx, c->stream, &k))
+        return fail("internal error: no kernel for layer %s/%s (mode %d, gauged %d, input tangent %d, crop offset %ld, output stride %d, selected %s)",
+                    L.block.c_str(), L.layer.c_str(), L.pw.mode, (int)g6, (int)has_dx, (long)cl.in_off, cl.osz, conv_kernel_name(k));
+    if (c->paths)
+        *c->paths |= (cl.skw ? NBE_PATH_SKIP_FUSED : 0) | (cl.skw && (cl.flags & F_SKIP_NODX) ? NBE_PATH_SKIP_NODX : 0) |
+                     (cl.csplit_ch ? NBE_PATH_TWO_SOURCE : 0) | (cl.skw && cl.sk_split_ch ? NBE_PATH_TWO_SOURCE_SKIP : 0) |
+                     (conv_is_wino(k) ? (L.layer == "conv_1" ? NBE_PATH_WINO_1 : NBE_PATH_WINO_0) : 0) |
+                     (conv_is_narrow(k) ? NBE_PATH_NARROW : 0) | (k == CONV_UP8 ? NBE_PATH_UP8 : 0);
     if (c->prof) {
         (void)hipEventRecord(eb, c->stream);
+        std::string pn = conv_label(k, pw, c->vel, has_dx);     // the label of the kernel that ran
+        static const bool per_layer = getenv("NBE_PROF_LAYERS") && atoi(getenv("NBE_PROF_LAYERS")) == 1;   // tools: one entry per layer
+        if (per_layer) pn += " " + L.block + "/" + L.layer;
+        const int pe = prof_entry(c, pn);
         c->pending.push_back({pe, ea, eb});
         // algorithmic FLOPs: 2*MAC over valid outputs; x3 with tangent (x2 when the input has no tangent, and for
         // the gauged form W.x, W.dx~)
@@ -171,12 +157,12 @@ static bool wino_only_fuse(const nbe_ctx* c) { return !c->vel || c->prec == PREC
 // skip exists in conv_h3w_kernel alone, which pairs planes -- an odd number of result planes, and conv_c (direct_z), take
 // the unfused path; slabs always have an even number)
 bool block_fused(const nbe_ctx* c, const Layer* L1, int nres) {
-    return c->fuse && L1->fskip != nullptr && (!wino_only_fuse(c) || (!c->direct_z && !wino_env_off() && (nres & 1) == 0));
+    return c->fuse && L1->fskip != nullptr && (!wino_only_fuse(c) || (!c->direct_z && !wino_env_off() && h3w_pairs_planes(nres)));
 }
 
 // Can a fused decoder block read concat([skip, up]) from two tensors?  The kernels switch sources between whole K chunks: 16
 // channels in conv_h3g_kernel / conv_h3w_kernel, 32 in the float16 model's Winograd-z form (the one kernel that fuses there).
-bool two_source_width(const nbe_ctx* c) { return c->mid % (c->prec == PREC_F16 ? 32 : 16) == 0; }
+bool two_source_width(const nbe_ctx* c) { return c->mid % two_source_chunk(c->prec) == 0; }
 
 // hidden tensor of a block whose input x has `pad`: interior (Hi - sy) x (Wi - sy).  A fused block gives it the row
 // and plane pitch of x (conv_h3g_kernel fetches the skip's patches of x with the offsets of its own input's).

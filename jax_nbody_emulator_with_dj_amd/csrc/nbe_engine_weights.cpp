@@ -32,11 +32,11 @@ bool packs_narrow(int prec, bool vel, const Layer& L) {
 }
 // the Winograd-z packing of a 3x3x3 layer (conv_h3w_kernel): 4 transformed kernels per 3 dz slices, wide tile only, Cin <= 128
 bool packs_wino(int prec, bool vel, const Layer& L) {
-    return L.kind == 0 && !L.first && ((prec == PREC_F16X3 && !L.pwn.w && L.pw.cin_pad / 16 <= 8) || wino_f16_layer(prec, vel, L.pw.cin_pad));
+    return L.kind == 0 && !L.first && ((prec == PREC_F16X3 && !L.pwn.w && h3w_stages_fit(L.pw.cin_pad)) || wino_f16_layer(prec, vel, L.pw.cin_pad));
 }
 // [W_s | dW_s~] of a skip that may run fused into its block's conv_1 (the float16 model: style path only, with dwn_f beside it)
 bool packs_wino_skip(int prec, bool vel, bool style, const Layer& L) {
-    return L.kind == 1 && ((prec == PREC_F16X3 && !L.pwn.w && L.pw.cin_pad / 16 <= 8) ||
+    return L.kind == 1 && ((prec == PREC_F16X3 && !L.pwn.w && h3w_stages_fit(L.pw.cin_pad)) ||
                            (style && !L.first && wino_f16_layer(prec, vel, L.pw.cin_pad)));
 }
 // the first layer in its own packing (stem_h3_kernel): K = 27 taps x 3 channels = 81 <= 96
@@ -136,7 +136,7 @@ static int wire_novel(nbe_ctx* c) {
         auto i1 = c->layers.find(std::string(b) + "/conv_1"), is = c->layers.find(std::string(b) + "/skip");
         if (i1 == c->layers.end() || is == c->layers.end()) return fail("internal: block %s", b);
         Layer &L1 = i1->second, &Ls = is->second;
-        if (!L1.pw.ww || !Ls.pw.ww || 2 * (Ls.pw.cin_pad / 16) > 16 || L1.pw.ctiles != Ls.pw.ctiles) return 0;   // all blocks or none
+        if (!L1.pw.ww || !Ls.pw.ww || !h3w_skip_fits(Ls.pw.cin_pad) || L1.pw.ctiles != Ls.pw.ctiles) return 0;   // all blocks or none
     }
     for (const char* b : kBlocks) {
         if (!strncmp(b, "down_", 5) || !strncmp(b, "up_", 3)) continue;
@@ -194,7 +194,7 @@ static int wire_gauge(nbe_ctx* c) {
         }
         // float16 model (style path): the skip runs inside conv_h3w_kernel<SKIP, ., F16> wherever conv_1's launch has that form
         if (c->prec == PREC_F16 && L1->pw.ww && Ls->pw.ww && Ls->dwn_f && L1->pw.ctiles == Ls->pw.ctiles &&
-            2 * (Ls->pw.cin_pad / 32) <= 16) {                   // NBE_MAX_WSKIP (nbe_kernels_wino.h)
+            h3w_skip_fits(Ls->pw.cin_pad, H3W_F16_CHUNKS)) {
             L1->fskip = Ls; Ls->b_sub = L1->beta;
             const int nb = L1->pw.ctiles * 32 * L1->pw.ni;
             HIPCHK(hipMalloc((void**)&L1->bias_f, nb * 4));

@@ -89,11 +89,48 @@ struct ConvLaunch {
     int sk_split_ch = 0;
     int64_t sk_off = 0;            // flat offset in sk of the voxel aligned with output (0, 0, 0)
     const PackedW* skw = nullptr;  // the skip layer's packed weights (FLAT1): w = W_s, dw = dW_s~
-    bool wino = false;             // run the Winograd-z kernel when the layer and the launch have that form (run_conv)
+    bool wino = false;             // the engine allows the Winograd-z kernel (policy); conv_select decides whether the launch has that form
 };
 
-// 0 on success; 1 = the layer / flag combination has no kernel (an engine bug, reported through nbe_last_error)
-int launch_conv(const PackedW& pw, const ConvLaunch& L, bool vel, bool has_dx, hipStream_t s);
+// conv_h3g_kernel: what group g of a launch reads, prepared by the launcher (everything that does not depend on the tile)
+struct ConvGroupSrc { const char* x; const char* dx; const char* w; long psb; };
+
+// kernel arguments of every convolution variant (POD, passed by value)
+struct ConvKArgs {
+    const float* x; const float* dx; long in_pstride;
+    int D, H, W; long P; long in_off;
+    int Dv, Hv, Wv; long Q;
+    float* y; float* dy; long out_pstride; int out_g0;
+    int Ho, Wo; int osz, oz, oy, ox;
+    const float* r; const float* dr; long res_pstride;
+    const float* bias; const float* w; const float* dw;
+    int nchunk; int cout_groups; int flags; int ntiles;
+    int tny, tnx;            // patch kernel: number of 8-row / 32-column tiles per output plane
+    int zrun;                // conv_h3nz_kernel: output planes per workgroup (set by its launcher)
+    // tangent gauge (f16x3 style path, see conv_h3g_kernel): per-cout vectors, either may be NULL
+    const float* gout;       // the stored tangent is dy + gout[o] * y
+    const float* beta;       // the input tangent is in this layer's gauge: dy = W.dx~ + beta[o] * (W.x), no dW
+    // conv_h3g_kernel<false> only.  Second K-segment of the input: chunks >= csplit are read from x2 / dx2 (same D, H, W
+    // and offsets as x; its own plane stride) -- concat([skip, up]) without a concat tensor.  csplit >= nchunk: unused.
+    const float* x2; const float* dx2; long in2_pstride; int csplit;
+    // The block's 1x1x1 skip fused into its last 3x3x3 convolution: nskip 16-channel chunks of the block input xs / dxs
+    // (chunks >= s_csplit from xs2 / dxs2), row and plane pitch (H, W) of x, pointers already offset so that the centre
+    // tap of the patch of output tile (z, y0, x0) is the skip's voxel; ws / dws = the skip layer's FLAT1-packed W_s / dW_s~.
+    const float* xs; const float* dxs; long s_pstride; const float* xs2; const float* dxs2; long s2_pstride; int s_csplit;
+    const float* ws; const float* dws; int nskip;
+    long dws_delta;          // dws - ws in bytes
+    int up8; long set_stride; // up_h3_kernel: all eight parity sets of an up-sampling layer; bytes between weight sets
+    const float* wws; long wws_set_floats;   // conv_h3w_kernel<SKIP>: the fused skip's [W_s | dW_s~] in that kernel's scaling, floats per set
+    const float* ww;         // conv_h3w_kernel: the layer's Winograd-z packed weights when this launch may use them, or NULL
+    const float* stem_w;     // stem_h3_kernel: the first layer's weights in its own packing (PackedW::stem), or NULL
+    ConvGroupSrc gs[NBE_MAX_GROUPS];
+};
+
+// which kernel a launch gets: nbe_conv_select.h
+enum ConvKernel : int;
+// 0 on success; 1 = the layer / flag combination has no kernel (an engine bug, reported through nbe_last_error);
+// *ran (nullable) = the kernel conv_select() chose
+int launch_conv(const PackedW& pw, const ConvLaunch& L, bool vel, bool has_dx, hipStream_t s, ConvKernel* ran = nullptr);
 
 // weight preparation -------------------------------------------------------
 // (w_n, dw_tot) in OIDHW from raw style parameters (style_layers_vel.py:62-105)

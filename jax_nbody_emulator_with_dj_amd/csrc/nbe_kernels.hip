@@ -239,7 +239,8 @@ static void launch_conv_t(const ConvKArgs& ka, int ctiles, hipStream_t s) {
     hipLaunchKernelGGL(kern, grid, block, smem, s, ka);
 }
 
-int launch_conv(const PackedW& pw, const ConvLaunch& L, bool vel, bool has_dx, hipStream_t s) {
+int launch_conv(const PackedW& pw, const ConvLaunch& L, bool vel, bool has_dx, hipStream_t s, ConvKernel* ran) {
+    if (ran) *ran = CONV_NONE;
     ConvKArgs ka;
     ka.x = L.in.x; ka.dx = L.in.dx; ka.in_pstride = L.in.pstride;
     ka.D = L.in.D; ka.H = L.in.H; ka.W = L.in.W; ka.P = L.in.vox(); ka.in_off = L.in_off;
@@ -261,7 +262,7 @@ int launch_conv(const PackedW& pw, const ConvLaunch& L, bool vel, bool has_dx, h
     ka.cout_groups = prec_is_half(pw.prec) ? (pw.cout + 7) / 8 : (pw.cout + 3) / 4;
     ka.flags = L.flags;
     ka.gout = L.gout; ka.beta = L.beta;
-    // second input segment and fused skip (conv_h3g_kernel<false>; every other kernel ignores them, and the launcher
+    // second input segment and fused skip (conv_h3g_kernel<false>; every other kernel ignores them, and conv_select
     // refuses them where they would be ignored)
     ka.x2 = L.in2.x; ka.dx2 = L.in2.dx; ka.in2_pstride = L.in2.pstride;
     if (L.csplit_ch % 16 != 0 || L.sk_split_ch % 16 != 0) return 1;          // sources switch between 16-channel chunks
@@ -277,14 +278,10 @@ int launch_conv(const PackedW& pw, const ConvLaunch& L, bool vel, bool has_dx, h
         ka.ws = L.skw->w; ka.dws = L.skw->dw; ka.nskip = L.skw->cin_pad / 16;
     }
     ka.ntiles = (int)((ka.Q + TILE_VOX - 1) / TILE_VOX);
-    if (prec_is_half(pw.prec)) return launch_conv_h3(pw, ka, vel, has_dx, s);
+    const ConvKernel k = conv_select(pw, ka, vel, has_dx);
+    if (ran) *ran = k;
+    if (prec_is_half(pw.prec)) return launch_conv_h3(k, pw, ka, vel, has_dx, s);
     const int ct = pw.ctiles;
-    if (ka.beta) {                                               // gauged input tangent: 3x3x3 layers only
-        if (!(pw.mode == MODE_FLAT3 && vel && has_dx)) return 1;   // no gauged kernel for this layer: the caller reports it
-        if (pw.ni == 2) launch_conv_t<MODE_FLAT3, true, true, 2, true>(ka, ct, s);
-        else launch_conv_t<MODE_FLAT3, true, true, 1, true>(ka, ct, s);
-        return 0;
-    }
 #define NBE_DISPATCH(MODE)                                                                   \
     if (vel) {                                                                               \
         if (has_dx) { if (pw.ni == 2) launch_conv_t<MODE, true, true, 2>(ka, ct, s);        \
@@ -295,11 +292,19 @@ int launch_conv(const PackedW& pw, const ConvLaunch& L, bool vel, bool has_dx, h
         if (pw.ni == 2) launch_conv_t<MODE, false, false, 2>(ka, ct, s);                     \
         else launch_conv_t<MODE, false, false, 1>(ka, ct, s);                                \
     }
-    if (pw.mode == MODE_FLAT3) { NBE_DISPATCH(MODE_FLAT3) }
-    else if (pw.mode == MODE_FLAT1) { NBE_DISPATCH(MODE_FLAT1) }
-    else { NBE_DISPATCH(MODE_DOWN) }
+    switch (k) {
+    case CONV_MFMA_G:                                            // gauged input tangent: 3x3x3 layers only
+        if (pw.ni == 2) launch_conv_t<MODE_FLAT3, true, true, 2, true>(ka, ct, s);
+        else launch_conv_t<MODE_FLAT3, true, true, 1, true>(ka, ct, s);
+        return 0;
+    case CONV_MFMA:
+        if (pw.mode == MODE_FLAT3) { NBE_DISPATCH(MODE_FLAT3) }
+        else if (pw.mode == MODE_FLAT1) { NBE_DISPATCH(MODE_FLAT1) }
+        else { NBE_DISPATCH(MODE_DOWN) }
+        return 0;
+    default: return 1;                                           // no kernel for this layer: the caller reports it
+    }
 #undef NBE_DISPATCH
-    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

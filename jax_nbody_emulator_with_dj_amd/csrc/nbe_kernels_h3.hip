@@ -369,7 +369,6 @@ __global__ __launch_bounds__(512, 2) void conv_h3_kernel(ConvKArgs a) {
 // SPLIT = false: the float16 model (one plane per eight channels, one MFMA per product): half the LDS image, two workgroups per
 // CU, a third of the MFMAs -- instead of eight launches of the general 1x1x1 kernel that each read the whole input.
 constexpr int UP_XV = 256;                           // positions per workgroup
-constexpr int UP_MAXCH = 4;                          // Cin <= 64
 template <bool SPLIT> struct UpGeom {
     static constexpr int UN = SPLIT ? 4 : 2;             // 16-byte units per position and 16-channel chunk (2 h + part | h)
     static constexpr int XC = 2 * UN * UP_XV;            // units of one resident chunk: (X, dX) x UN units x 256
@@ -497,7 +496,7 @@ template <bool SPLIT, bool VEL = true>
 static int launch_up_h3(ConvKArgs ka, int ctiles, hipStream_t s) {
     constexpr size_t smem = (size_t)UpGeom<SPLIT>::LDS_UNITS * 16;
     static_assert(smem <= 160 * 1024, "LDS budget of one CU");
-    if (ka.nchunk > UP_MAXCH) return 1;
+    if (!up8_ok(ka)) return 2;
     ensure_lds_limit((const void*)up_h3_kernel<SPLIT, VEL>, smem);
     dim3 grid(ka.ntiles, ctiles, 1), block(512, 1, 1);
     hipLaunchKernelGGL((up_h3_kernel<SPLIT, VEL>), grid, block, smem, s, ka);
@@ -515,7 +514,6 @@ static int launch_up_h3(ConvKArgs ka, int ctiles, hipStream_t s) {
 // DMA per MFMA drops to ~34 B (activations) + 57 B (weights).  Tiles are ordered z-fastest so that the 32
 // workgroups of an XCD work on neighbouring planes of the same (y,x) patch and share two of their three input
 // planes through that XCD's L2.
-constexpr int HP_ROWS = 8, HP_COLS = 32;
 constexpr int HP_RS = HP_COLS + 2;                   // LDS row stride (units)
 constexpr int HP_PL = (HP_ROWS + 2) * HP_RS;         // units per plane of the patch image: 340
 
@@ -1076,11 +1074,9 @@ __global__ __launch_bounds__(512, 2) void conv_h3q_kernel(ConvKArgs a) {
 static int launch_h3q(ConvKArgs ka, int ctiles, hipStream_t s) {
     constexpr size_t smem = (size_t)HQ_LDS_UNITS * 16;
     static_assert(smem <= 160 * 1024, "LDS budget of one CU");
+    if (!h3q_ok(ka, ctiles)) return 2;
     ensure_lds_limit((const void*)conv_h3q_kernel, smem);
-    ka.tny = (ka.Hv + HP_ROWS - 1) / HP_ROWS;
-    ka.tnx = (ka.Wv + HP_COLS - 1) / HP_COLS;
-    ka.ntiles = ka.Dv * ka.tny * ka.tnx;
-    if (ctiles != (ka.cout_groups + 7) / 8) return 1;            // cout tiling mismatch: reported by the caller
+    ka.ntiles = (int)patch_tiles(ka, HP_ROWS, HP_COLS, ka.Dv);
     dim3 grid(ka.ntiles * ctiles, 1, 1), block(512, 1, 1);
     hipLaunchKernelGGL(conv_h3q_kernel, grid, block, smem, s, ka);
     return 0;
@@ -1464,27 +1460,18 @@ static int launch_h3g(ConvKArgs ka, int ctiles, hipStream_t s) {
     typedef HGGeom<NARROW> G;
     constexpr size_t smem = (size_t)G::LDS_UNITS * 16;
     static_assert(smem <= 160 * 1024, "LDS budget of one CU");
+    if (!h3g_ok(ka, ctiles, NARROW)) return 2;
     ensure_lds_limit((const void*)conv_h3g_kernel<NARROW>, smem);
-    ka.tny = (ka.Hv + HP_ROWS - 1) / HP_ROWS;
-    ka.tnx = (ka.Wv + HP_COLS - 1) / HP_COLS;
-    ka.ntiles = ka.Dv * ka.tny * ka.tnx;
-    if (ctiles != (ka.cout_groups + G::CT / 8 - 1) / (G::CT / 8)) return 1;
+    ka.ntiles = (int)patch_tiles(ka, HP_ROWS, HP_COLS, ka.Dv);
     const int ngroups = 3 * ka.nchunk, nskip = ka.nskip;
-    if (ngroups + nskip > NBE_MAX_GROUPS) return 1;              // the engine does not wire such a network for this kernel
     for (int g = 0; g < ngroups; ++g) {
-        const int chunk = g / 3, dz = g - chunk * 3;
-        const bool second = chunk >= ka.csplit;
-        const long ps = second ? ka.in2_pstride : ka.in_pstride;
-        const long off = ((long)(second ? chunk - ka.csplit : chunk) * 4 * ps + (long)dz * ka.H * ka.W) * 16;
-        ka.gs[g] = {(const char*)(second ? ka.x2 : ka.x) + off, (const char*)(second ? ka.dx2 : ka.dx) + off,
-                    (const char*)ka.w + (long)g * G::WG * 16, ps * 16};
+        const ChunkSrc c = input_chunk(ka, g / 3);
+        const long dz = (long)(g % 3) * ka.H * ka.W * 16;
+        ka.gs[g] = {c.x + dz, c.dx + dz, (const char*)ka.w + (long)g * G::WG * 16, c.psb};
     }
     for (int sc = 0; sc < nskip; ++sc) {
-        const bool second = sc >= ka.s_csplit;
-        const long ps = second ? ka.s2_pstride : ka.s_pstride;
-        const long off = (long)(second ? sc - ka.s_csplit : sc) * 4 * ps * 16;
-        ka.gs[ngroups + sc] = {(const char*)(second ? ka.xs2 : ka.xs) + off, (const char*)(second ? ka.dxs2 : ka.dxs) + off,
-                               (const char*)ka.ws + (long)sc * G::TAPU * 16, ps * 16};
+        const ChunkSrc c = skip_chunk(ka, sc);
+        ka.gs[ngroups + sc] = {c.x, c.dx, (const char*)ka.ws + (long)sc * G::TAPU * 16, c.psb};
     }
     ka.dws_delta = nskip ? (const char*)ka.dws - (const char*)ka.ws : 0;
     dim3 grid(ka.ntiles * ctiles, 1, 1), block(G::NW * 64, 1, 1);
@@ -1510,7 +1497,6 @@ static int launch_h3g(ConvKArgs ka, int ctiles, hipStream_t s) {
 // tile t = 8*mt + nt, nt = 2*row + column half; the rolling operand pipeline works on half tiles (2 rows).
 // LDS: weight buffer A (taps 0-4) / B (taps 5-8) with rows [tap][r][64 couts], r = 2*h + part (SPLIT) or 2*set + h;
 // patch planes p = 2*h + part (SPLIT) or 2*tensor + h, 18 x 34 units each.
-constexpr int H2_ROWS = 16;
 constexpr int H2_PL = (H2_ROWS + 2) * HP_RS;              // units per patch plane: 612
 // LDS pitch of a patch plane, padded so that the two planes a ds_read_b128 mixes in one LDS cycle start 0 mod 16 units
 // apart (no bank conflicts): planes 2*kh apart in the SPLIT variant (pitch multiple of 8), kh apart otherwise (of 16)
@@ -1794,11 +1780,9 @@ static int launch_h2q(ConvKArgs ka, int ctiles, hipStream_t s) {
     constexpr size_t smem = (size_t)H2_LDS_UNITS * 16;
     static_assert(smem <= 160 * 1024, "LDS budget of one CU");
     auto kern = conv_h2q_kernel<SPLIT, G6>;
+    if (!h2q_ok(ka, ctiles)) return 2;
     ensure_lds_limit((const void*)kern, smem);
-    ka.tny = (ka.Hv + H2_ROWS - 1) / H2_ROWS;
-    ka.tnx = (ka.Wv + HP_COLS - 1) / HP_COLS;
-    ka.ntiles = ka.Dv * ka.tny * ka.tnx;
-    if (ctiles != (ka.cout_groups + 7) / 8) return 1;
+    ka.ntiles = (int)patch_tiles(ka, H2_ROWS, HP_COLS, ka.Dv);
     dim3 grid(ka.ntiles * ctiles, 1, 1), block(512, 1, 1);
     hipLaunchKernelGGL(kern, grid, block, smem, s, ka);
     return 0;
@@ -1824,9 +1808,7 @@ static void launch_h3p_t(ConvKArgs ka, int ctiles, hipStream_t s) {
     static_assert(smem <= 160 * 1024, "LDS budget of one CU");
     auto kern = conv_h3p_kernel<VEL, HAS_DX, SPLIT>;
     ensure_lds_limit((const void*)kern, smem);
-    ka.tny = (ka.Hv + HP_ROWS - 1) / HP_ROWS;
-    ka.tnx = (ka.Wv + HP_COLS - 1) / HP_COLS;
-    ka.ntiles = ka.Dv * ka.tny * ka.tnx;
+    ka.ntiles = (int)patch_tiles(ka, HP_ROWS, HP_COLS, ka.Dv);
     dim3 grid(ka.ntiles, ctiles, 1), block(512, 1, 1);
     hipLaunchKernelGGL(kern, grid, block, smem, s, ka);
 }
@@ -1857,10 +1839,7 @@ static int launch_h3_vd(const ConvKArgs& ka, int ct, bool vel, bool has_dx, hipS
 // planes (64 couts x hi / lo x y / dy) per tile -- and a tile writes ST_COLS * 16 B contiguous bytes per row and plane: the
 // longer the runs, the faster (same-device A/B, -DNBE_STEM_ROWS=4 / 2 / 1: 26.9 / 22.9 / 20.6 ms per box, i.e. 3.0 / 3.5 /
 // 3.9 TB/s of output; profiles/r02_ab_stem_rows.txt).  One row of 128 columns: 2 KB runs.
-#ifndef NBE_STEM_ROWS
-#define NBE_STEM_ROWS 1
-#endif
-constexpr int ST_ROWS = NBE_STEM_ROWS, ST_COLS = 128 / ST_ROWS, ST_RS = ST_COLS + 2, ST_WPR = ST_COLS / 32;   // waves per row
+constexpr int ST_RS = ST_COLS + 2, ST_WPR = ST_COLS / 32;   // waves per row (ST_ROWS, ST_COLS: nbe_conv_select.h)
 constexpr int ST_PL = (ST_ROWS + 2) * ST_RS;                 // halves of one (part, channel, dz) patch plane: 3 x 130 = 390
 constexpr int ST_PV = 3 * ST_PL;                             // patch voxels of a tile: 1170
 constexpr int ST_NPV = (ST_PV + 255) / 256;                  // ... per thread
@@ -2062,10 +2041,8 @@ __global__ __launch_bounds__(256, 2) void stem_h3_kernel(ConvKArgs a) {
 
 template <bool VEL, bool SPLIT = true>
 static int launch_stem(ConvKArgs ka, hipStream_t s) {
-    ka.tny = (ka.Hv + ST_ROWS - 1) / ST_ROWS;
-    ka.tnx = (ka.Wv + ST_COLS - 1) / ST_COLS;
-    const long nt = (long)ka.Dv * ka.tny * ka.tnx;
-    if (nt <= 0 || nt >= (1L << 31) || ka.cout_groups > 8 || ka.nchunk != 1) return 1;
+    if (!stem_ok(ka)) return 2;
+    const long nt = patch_tiles(ka, ST_ROWS, ST_COLS, ka.Dv);
     ka.ntiles = (int)nt;
     const int grid = (int)std::min<long>(nt, 512);
     static_assert(2 * ST_LDS <= 160 * 1024, "two workgroups per CU");
@@ -2086,58 +2063,37 @@ __global__ __launch_bounds__(256) void pack_stem_kernel(const float* __restrict_
     dst[idx] = part == 0 ? hi : (_Float16)((v - (float)hi) * H3_SCALE);
 }
 
-// Which kernel runs a layer.  The generations that lost their A/B (DESIGN.md sections 4 and 4c) are gone from the sources.
-int launch_conv_h3(const PackedW& pw, const ConvKArgs& ka, bool vel, bool has_dx, hipStream_t s) {
+// Launch the kernel conv_select() chose (nbe_conv_select.h: which kernel runs a layer, and why).  0: launched; 1: no kernel
+// for this launch; 2: the launcher's own check disagrees with the selection (a bug here).
+int launch_conv_h3(ConvKernel k, const PackedW& pw, const ConvKArgs& ka, bool vel, bool has_dx, hipStream_t s) {
     const int ct = pw.ctiles;
     const bool split = pw.prec == PREC_F16X3;
-    if (ka.stem_w && !(vel && has_dx) && pw.mode == MODE_FLAT3 && ka.in_off == 0 && ka.osz == 1 &&
-        !(ka.flags & F_RES) && ka.nskip == 0 && !ka.beta) {
+    switch (k) {                                                 // in the order conv_select() considers them
+    case CONV_STEM:
         if (split) return vel ? launch_stem<true>(ka, s) : launch_stem<false>(ka, s);
         return vel ? launch_stem<true, false>(ka, s) : launch_stem<false, false>(ka, s);
-    }
-    // a second input segment / a fused skip exist only in the wide gauged f16x3 kernel and in conv_h3w_kernel's displacement-only form
-    if ((ka.nskip > 0 || ka.csplit < ka.nchunk) && !(ka.beta && split)) {
-        if (split && !vel && ka.ww && pw.mode == MODE_FLAT3 && ka.in_off == 0 && ka.osz == 1)
-            return launch_h3w(ka, ka.ww, ka.wws, ka.wws_set_floats, ct, s, true);     // 1: no such form for this launch (an engine bug)
-        if (!split && vel && has_dx && ka.beta && ka.ww && pw.mode == MODE_FLAT3 && ka.in_off == 0 && ka.osz == 1)
-            return launch_h3w(ka, ka.ww, ka.wws, ka.wws_set_floats, ct, s, false, true);   // the float16 model's Winograd-z form
-        return 1;
-    }
-    if (ka.beta) {                                               // gauged input tangent: only conv_h3g_kernel reads it
-        if (!(pw.mode == MODE_FLAT3 && vel && has_dx && ka.in_off == 0 && ka.osz == 1)) return 1;   // no gauged kernel
-        if (split) {
-            if (pw.cout_t == 16) {                              // the head convolution: one pass along z, dz in the MFMA rows, where the launch allows
-                if (launch_h3nz(ka, ct, pw.cout, s) == 0) return 0;
-                return launch_h3g<true>(ka, ct, s);
-            }
-            if (ka.ww && launch_h3w(ka, ka.ww, ka.wws, ka.wws_set_floats, ct, s) == 0) return 0;     // Winograd along z; 1: no such form for this launch
-            return launch_h3g<false>(ka, ct, s);
-        }
-        if (ka.ww && launch_h3w(ka, ka.ww, ka.wws, ka.wws_set_floats, ct, s, false, true) == 0) return 0;   // float16 model: Winograd along z
-        return launch_h2q<false, true>(ka, ct, s);
-    }
-    if (pw.mode == MODE_FLAT3) {
-        if (!(ka.in_off == 0 && ka.osz == 1)) return 1;          // 3x3x3 layers are never cropped or strided
-        if (split && vel && has_dx) return launch_h3q(ka, ct, s);
-        if (split && !vel && ka.ww && launch_h3w(ka, ka.ww, ka.wws, ka.wws_set_floats, ct, s, true) == 0) return 0;   // Winograd along z, displacement only
-        if (split && !vel) return launch_h2q<true>(ka, ct, s);
-        if (!split && vel && has_dx) return launch_h2q<false>(ka, ct, s);
-        // left for the 32x32x16 patch kernel: the first layer without the stem (velocity, no input tangent) and the float16
-        // model's displacement-only layers
+    case CONV_H3W_NOVEL: return launch_h3w(ka, ct, s, true, false);
+    case CONV_H3W_F16: return launch_h3w(ka, ct, s, false, true);
+    case CONV_H3NZ: return launch_h3nz(ka, ct, pw.cout, s);
+    case CONV_H3G_NARROW: return launch_h3g<true>(ka, ct, s);
+    case CONV_H3W_F16X3: return launch_h3w(ka, ct, s, false, false);
+    case CONV_H3G_WIDE: return launch_h3g<false>(ka, ct, s);
+    case CONV_H2Q_F16_G: return launch_h2q<false, true>(ka, ct, s);
+    case CONV_H3Q: return launch_h3q(ka, ct, s);
+    case CONV_H2Q_SPLIT: return launch_h2q<true>(ka, ct, s);
+    case CONV_H2Q_F16: return launch_h2q<false>(ka, ct, s);
+    case CONV_H3P:
         if (!vel) launch_h3p_t<false, false, false>(ka, ct, s);
         else if (split) launch_h3p_t<true, false, true>(ka, ct, s);
         else launch_h3p_t<true, false, false>(ka, ct, s);
         return 0;
+    case CONV_UP8:
+        if (vel) return split ? launch_up_h3<true>(ka, ct, s) : launch_up_h3<false>(ka, ct, s);
+        return split ? launch_up_h3<true, false>(ka, ct, s) : launch_up_h3<false, false>(ka, ct, s);
+    case CONV_H3_FLAT1: return split ? launch_h3_vd<MODE_FLAT1, true>(ka, ct, vel, has_dx, s) : launch_h3_vd<MODE_FLAT1, false>(ka, ct, vel, has_dx, s);
+    case CONV_H3_DOWN: return split ? launch_h3_vd<MODE_DOWN, true>(ka, ct, vel, has_dx, s) : launch_h3_vd<MODE_DOWN, false>(ka, ct, vel, has_dx, s);
+    default: return 1;
     }
-    if (pw.mode == MODE_FLAT1) {
-        if (ka.up8) {                                            // all eight parities in one launch
-            if (vel && has_dx) return split ? launch_up_h3<true>(ka, ct, s) : launch_up_h3<false>(ka, ct, s);
-            if (!vel) return split ? launch_up_h3<true, false>(ka, ct, s) : launch_up_h3<false, false>(ka, ct, s);
-            return 1;
-        }
-        return split ? launch_h3_vd<MODE_FLAT1, true>(ka, ct, vel, has_dx, s) : launch_h3_vd<MODE_FLAT1, false>(ka, ct, vel, has_dx, s);
-    }
-    return split ? launch_h3_vd<MODE_DOWN, true>(ka, ct, vel, has_dx, s) : launch_h3_vd<MODE_DOWN, false>(ka, ct, vel, has_dx, s);
 }
 
 // packed layout: [set][ct][stage = chunk*nseg + seg][tap][u = 2*h + part][co cout_t = 64 (16: narrow tiles)][j 8];

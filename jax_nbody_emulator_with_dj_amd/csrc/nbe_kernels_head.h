@@ -35,8 +35,7 @@
 // Resources (hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage): 172 VGPRs, 0 AGPRs, 102 SGPRs,
 // scratch 0, no spills; LDS 117,760 B, all dynamic (one workgroup of 8 waves per CU).
 constexpr int HNZ_ZRUN = 32;                                    // longest run of output planes of one workgroup
-constexpr int HNZ_MAXCH = 4;                                    // at most 64 input channels, and 64 of the block input
-constexpr int HNZ_R = 4;                                        // weight rows kept per 16-row unit
+// (HNZ_MAXCH, at most 64 input channels and 64 of the block input, and HNZ_R, the weight rows kept per 16-row unit: nbe_conv_select.h)
 constexpr int HNZ_TAPU = 4 * HNZ_R;                             // units per tap: 2 channel halves x hi/lo x 4 rows
 constexpr int HNZ_WG = 9 * HNZ_TAPU;                            // one (chunk, dz) group: 144 units
 constexpr int HNZ_WC = 3 * HNZ_WG;                              // a chunk: 432 units
@@ -267,33 +266,23 @@ __global__ __launch_bounds__(512, 1) void conv_h3nz_kernel(ConvKArgs a) {
     retire(zn + 1);
 }
 
-// 0: launched; 1: this launch has no such form (the caller takes conv_h3g_kernel<NARROW>): more than 4 couts or 64 channels,
-// the residual form, a skip whose input has no tangent
+// (launches that have no such form -- h3nz_ok, nbe_conv_select.h -- take conv_h3g_kernel<NARROW>)
 static int launch_h3nz(ConvKArgs ka, int ctiles, int cout, hipStream_t s) {
     constexpr size_t smem = (size_t)HNZ_LDS_UNITS * 16;
     static_assert(smem <= 160 * 1024, "LDS budget of one CU");
-    if (ctiles != 1 || cout > HNZ_R || ka.cout_groups != 1 || (ka.flags & (F_RES | F_SKIP_NODX)) || !ka.beta || ka.Dv < 1) return 1;
-    if (ka.nchunk > HNZ_MAXCH || ka.nskip > HNZ_MAXCH || ka.nchunk + ka.nskip > NBE_MAX_GROUPS) return 1;
+    if (!h3nz_ok(ka, ctiles, cout)) return 2;
     ensure_lds_limit((const void*)conv_h3nz_kernel, smem);
-    ka.tny = (ka.Hv + HP_ROWS - 1) / HP_ROWS;
-    ka.tnx = (ka.Wv + HP_COLS - 1) / HP_COLS;
     // runs of equal length, as long as HNZ_ZRUN allows: a run of Z planes stages Z + 2
     const int nrun = (ka.Dv + HNZ_ZRUN - 1) / HNZ_ZRUN;
     ka.zrun = (ka.Dv + nrun - 1) / nrun;
-    ka.ntiles = ((ka.Dv + ka.zrun - 1) / ka.zrun) * ka.tny * ka.tnx;
+    ka.ntiles = (int)patch_tiles(ka, HP_ROWS, HP_COLS, (ka.Dv + ka.zrun - 1) / ka.zrun);
     for (int chunk = 0; chunk < ka.nchunk; ++chunk) {
-        const bool second = chunk >= ka.csplit;
-        const long ps = second ? ka.in2_pstride : ka.in_pstride;
-        const long off = (long)(second ? chunk - ka.csplit : chunk) * 4 * ps * 16;
-        ka.gs[chunk] = {(const char*)(second ? ka.x2 : ka.x) + off, (const char*)(second ? ka.dx2 : ka.dx) + off,
-                        (const char*)ka.w, ps * 16};
+        const ChunkSrc c = input_chunk(ka, chunk);
+        ka.gs[chunk] = {c.x, c.dx, (const char*)ka.w, c.psb};
     }
     for (int sc = 0; sc < ka.nskip; ++sc) {
-        const bool second = sc >= ka.s_csplit;
-        const long ps = second ? ka.s2_pstride : ka.s_pstride;
-        const long off = (long)(second ? sc - ka.s_csplit : sc) * 4 * ps * 16;
-        ka.gs[ka.nchunk + sc] = {(const char*)(second ? ka.xs2 : ka.xs) + off, (const char*)(second ? ka.dxs2 : ka.dxs) + off,
-                                 (const char*)ka.ws, ps * 16};
+        const ChunkSrc c = skip_chunk(ka, sc);
+        ka.gs[ka.nchunk + sc] = {c.x, c.dx, (const char*)ka.ws, c.psb};
     }
     ka.dws_delta = ka.nskip ? (const char*)ka.dws - (const char*)ka.ws : 0;
     hipLaunchKernelGGL(conv_h3nz_kernel, dim3(ka.ntiles), dim3(512), smem, s, ka);

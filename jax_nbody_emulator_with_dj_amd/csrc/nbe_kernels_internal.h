@@ -1,6 +1,6 @@
 // Shared between nbe_kernels.hip (float32 path, data movement) and nbe_kernels_h3.hip (f16x3 path).
 #pragma once
-#include "nbe_kernels.h"
+#include "nbe_conv_select.h"
 #include <mutex>
 #include <set>
 #include <utility>
@@ -15,39 +15,22 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 #define NBE_LDS_AS __attribute__((address_space(3)))
 #define NBE_GLB_AS __attribute__((address_space(1)))
 
-// conv_h3g_kernel: what group g of a launch reads, prepared by the launcher (everything that does not depend on the tile)
-struct ConvGroupSrc { const char* x; const char* dx; const char* w; long psb; };
-
-// kernel arguments of every convolution variant (POD, passed by value)
-struct ConvKArgs {
-    const float* x; const float* dx; long in_pstride;
-    int D, H, W; long P; long in_off;
-    int Dv, Hv, Wv; long Q;
-    float* y; float* dy; long out_pstride; int out_g0;
-    int Ho, Wo; int osz, oz, oy, ox;
-    const float* r; const float* dr; long res_pstride;
-    const float* bias; const float* w; const float* dw;
-    int nchunk; int cout_groups; int flags; int ntiles;
-    int tny, tnx;            // patch kernel: number of 8-row / 32-column tiles per output plane
-    int zrun;                // conv_h3nz_kernel: output planes per workgroup (set by its launcher)
-    // tangent gauge (f16x3 style path, see conv_h3g_kernel): per-cout vectors, either may be NULL
-    const float* gout;       // the stored tangent is dy + gout[o] * y
-    const float* beta;       // the input tangent is in this layer's gauge: dy = W.dx~ + beta[o] * (W.x), no dW
-    // conv_h3g_kernel<false> only.  Second K-segment of the input: chunks >= csplit are read from x2 / dx2 (same D, H, W
-    // and offsets as x; its own plane stride) -- concat([skip, up]) without a concat tensor.  csplit >= nchunk: unused.
-    const float* x2; const float* dx2; long in2_pstride; int csplit;
-    // The block's 1x1x1 skip fused into its last 3x3x3 convolution: nskip 16-channel chunks of the block input xs / dxs
-    // (chunks >= s_csplit from xs2 / dxs2), row and plane pitch (H, W) of x, pointers already offset so that the centre
-    // tap of the patch of output tile (z, y0, x0) is the skip's voxel; ws / dws = the skip layer's FLAT1-packed W_s / dW_s~.
-    const float* xs; const float* dxs; long s_pstride; const float* xs2; const float* dxs2; long s2_pstride; int s_csplit;
-    const float* ws; const float* dws; int nskip;
-    long dws_delta;          // dws - ws in bytes
-    int up8; long set_stride; // up_h3_kernel: all eight parity sets of an up-sampling layer; bytes between weight sets
-    const float* wws; long wws_set_floats;   // conv_h3w_kernel<SKIP>: the fused skip's [W_s | dW_s~] in that kernel's scaling, floats per set
-    const float* ww;         // conv_h3w_kernel: the layer's Winograd-z packed weights when this launch may use them, or NULL
-    const float* stem_w;     // stem_h3_kernel: the first layer's weights in its own packing (PackedW::stem), or NULL
-    ConvGroupSrc gs[NBE_MAX_GROUPS];
-};
+// Where a launcher's source tables point.  Chunk c of the input (16 channels = 4 planes; chunks >= csplit come from the
+// second tensor) and chunk sc of a fused skip's input (likewise, from s_csplit on): first plane of the chunk, primal and
+// tangent, and the plane stride in bytes.
+struct ChunkSrc { const char* x; const char* dx; long psb; };
+inline ChunkSrc input_chunk(const ConvKArgs& ka, int c) {
+    const bool second = c >= ka.csplit;
+    const long ps = second ? ka.in2_pstride : ka.in_pstride;
+    const long off = (long)(second ? c - ka.csplit : c) * 4 * ps * 16;
+    return {(const char*)(second ? ka.x2 : ka.x) + off, (const char*)(second ? ka.dx2 : ka.dx) + off, ps * 16};
+}
+inline ChunkSrc skip_chunk(const ConvKArgs& ka, int sc) {
+    const bool second = sc >= ka.s_csplit;
+    const long ps = second ? ka.s2_pstride : ka.s_pstride;
+    const long off = (long)(second ? sc - ka.s_csplit : sc) * 4 * ps * 16;
+    return {(const char*)(second ? ka.xs2 : ka.xs) + off, (const char*)(second ? ka.dxs2 : ka.dxs) + off, ps * 16};
+}
 
 __device__ __forceinline__ void dma16(const float* src, f32x4* dst_wave_base) {
     // 64 lanes x 16 B: LDS destination = wave-uniform base + lane*16 (hardware rule), source per lane.
@@ -74,7 +57,7 @@ __device__ __forceinline__ int xcd_tile(int b, int nt) {
 }
 
 // f16x3 path (nbe_kernels_h3.hip)
-int launch_conv_h3(const PackedW& pw, const ConvKArgs& ka, bool vel, bool has_dx, hipStream_t s);
+int launch_conv_h3(ConvKernel k, const PackedW& pw, const ConvKArgs& ka, bool vel, bool has_dx, hipStream_t s);
 void launch_pack_h3(const float* w_oidhw, int cout, int cin, int kind, const PackedW& pw, float* dst, hipStream_t s);
 void launch_gather_h8(const float* box, int C, int Db, int Hb, int Wb, int a0, int a1, int a2,
                       float* dst, const Planes& geom, float scale, int parts, hipStream_t s);

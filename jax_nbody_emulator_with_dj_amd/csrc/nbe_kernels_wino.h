@@ -55,8 +55,7 @@
 #ifndef NBE_WINO_LOU
 #define NBE_WINO_LOU (NBE_XF_F32 ? 0 : 1)
 #endif
-constexpr int NBE_MAX_WSTAGES = 32;                // 4 * Cin / 16: Cin <= 128
-constexpr int NBE_MAX_WSKIP = 16;                  // fused skip: 2 planes x Cin_block / 16 source entries behind the transformed stages'
+// (NBE_MAX_WSTAGES and NBE_MAX_WSKIP, the lengths of the source table below: nbe_conv_select.h)
 constexpr float WINO_WSCALE = 16384.0f;            // 2^14
 constexpr float WINO_WSCALE_F16 = 256.0f;          // the float16 form: no lo part to keep out of the subnormals, 2^8 for the small weights
 
@@ -882,34 +881,27 @@ void launch_pack_h3w(const float* w_oidhw, int cout, int cin, int cin_pad, int c
                        (_Float16*)dst, flag, f16 ? 1 : 0);
 }
 
-// 0: launched; 1: this launch has no Winograd form (the caller falls back to conv_h3g_kernel)
-// wws: the fused skip's weights [W_s | dW_s~] in the kernel's scaling (PackedW::ww of the skip layer), needed when ka.nskip > 0
+// (launches that have no Winograd form -- h3w_ok, nbe_conv_select.h -- take the direct kernels)
+// ka.ww: the layer's Winograd-z packing; ka.wws: the fused skip's weights [W_s | dW_s~] in the kernel's scaling (PackedW::ww of
+// the skip layer), ka.wws_set_floats apart
 // novel: the displacement-only form (conv_h3w_kernel<SKIP, true>): no tangent tensors, two row blocks per workgroup
-// f16: the float16 model's form (32-channel stages, no fused skip, residual in the epilogue)
-static int launch_h3w(const ConvKArgs& ka_in, const float* ww, const float* wws, long wws_set_floats, int ctiles, hipStream_t s,
-                      bool novel = false, bool f16 = false) {
+// f16: the float16 model's form (32-channel stages, residual in the epilogue)
+static int launch_h3w(ConvKArgs ka, int ctiles, hipStream_t s, bool novel, bool f16) {
     typedef HGGeom<false> G;
     constexpr size_t smem = (size_t)(G::LDS_UNITS + 64) * 16;   // + the zeroed kilobyte (NBE_WINO_ZROW)
     static_assert(smem <= 160 * 1024, "LDS budget of one CU");
-    ConvKArgs ka = ka_in;
+    if (!h3w_ok(ka, ctiles, novel, f16)) return 2;
+    const float *ww = ka.ww, *wws = ka.wws;
     if (f16) {                                                   // 16-channel chunks -> 32-channel stages
-        if (novel || (ka.nchunk & 1) || (ka.csplit < ka.nchunk && (ka.csplit & 1))) return 1;
-        if (ka.nskip > 0 && ((ka.nskip & 1) || (ka.s_csplit < ka.nskip && (ka.s_csplit & 1)) || (ka.flags & F_SKIP_NODX))) return 1;
-        ka.nchunk /= 2; if (ka.csplit < (1 << 29)) ka.csplit /= 2;
-        ka.nskip /= 2; if (ka.s_csplit < (1 << 29)) ka.s_csplit /= 2;
+        ka.nchunk /= H3W_F16_CHUNKS; if (ka.csplit < (1 << 29)) ka.csplit /= H3W_F16_CHUNKS;
+        ka.nskip /= H3W_F16_CHUNKS; if (ka.s_csplit < (1 << 29)) ka.s_csplit /= H3W_F16_CHUNKS;
     }
-    if (!ww || (!f16 && (ka.flags & F_RES)) || (ka.Dv & 1) || 4 * ka.nchunk > NBE_MAX_WSTAGES || (!novel && !ka.beta)) return 1;
-    if (ka.nskip > 0 && (!wws || 2 * ka.nskip > NBE_MAX_WSKIP)) return 1;
-    if (ctiles != (ka.cout_groups + 7) / 8) return 1;
-    // the raw planes are fetched with buffer loads (32-bit offsets): lane offset + hi -> lo plane distance stay below 2^32
-    if (std::max(ka.in_pstride, ka.csplit < ka.nchunk ? ka.in2_pstride : 0L) * 16 + 16L * (HP_ROWS + 2) * ka.W >= (1L << 32) - (1L << 20)) return 1;
     WinoKArgs wa;
     wa.H = ka.H; wa.W = ka.W; wa.Dv = ka.Dv; wa.Hv = ka.Hv; wa.Wv = ka.Wv; wa.Ho = ka.Ho; wa.Wo = ka.Wo;
     wa.nchunk = ka.nchunk; wa.cout_groups = ka.cout_groups; wa.flags = ka.flags;
     const int trows = novel ? 2 * HP_ROWS : HP_ROWS;
-    wa.tny = (ka.Hv + trows - 1) / trows;
-    wa.tnx = (ka.Wv + HP_COLS - 1) / HP_COLS;
-    wa.ntiles = (ka.Dv / 2) * wa.tny * wa.tnx;
+    wa.ntiles = (int)patch_tiles(ka, trows, HP_COLS, ka.Dv / 2);
+    wa.tny = ka.tny; wa.tnx = ka.tnx;
     wa.y = ka.y; wa.dy = ka.dy; wa.out_pstride = ka.out_pstride; wa.out_g0 = ka.out_g0;
     wa.bias = ka.bias; wa.gout = novel ? nullptr : ka.gout; wa.beta = novel ? nullptr : ka.beta;
     const long rows8 = (long)HP_ROWS * ka.W * 16;                // novel: the "tangent" patch is the input eight rows further down
@@ -918,7 +910,7 @@ static int launch_h3w(const ConvKArgs& ka_in, const float* ww, const float* wws,
     // z pairs per block of the tile order.  A/B (profiles/r02_ab_wino_zblock.txt): all pairs of the launch (z fastest) 1494 ms
     // per box, 1 (x fastest) 1496, 2 / 4 / 8 / 16: 1479 / 1481 / 1477 / 1482
     wa.zblock = std::min(8, ka.Dv / 2);
-    wa.nskip = ka.nskip; wa.dws_delta = wws_set_floats * 4;
+    wa.nskip = ka.nskip; wa.dws_delta = ka.wws_set_floats * 4;
     // stage order: phase 0 = (xi 1 -> A, xi 2 -> B) per chunk, phase 1 = (xi 0 -> A, xi 3 -> B) per chunk
     static const int XI[2][2] = {{1, 2}, {0, 3}};
     static const int PA[4] = {0, 1, 2, 1}, PB[4] = {2, 2, 1, 3};
@@ -928,27 +920,19 @@ static int launch_h3w(const ConvKArgs& ka_in, const float* ww, const float* wws,
         for (int chunk = 0; chunk < ka.nchunk; ++chunk)
             for (int ab = 0; ab < 2; ++ab) {
                 const int xi = XI[ph][ab];
-                const bool second = chunk >= ka.csplit;
-                const long ps = second ? ka.in2_pstride : ka.in_pstride;
-                const char* x = (const char*)(second ? ka.x2 : ka.x);
-                const char* dx = (const char*)(second ? ka.dx2 : ka.dx);
-                const long off = (long)(second ? chunk - ka.csplit : chunk) * 4 * ps * 16;
+                const ChunkSrc c = input_chunk(ka, chunk);
                 WinoSrc& e = wa.st[(ph * ka.nchunk + chunk) * 2 + ab];
-                e.xa = x + off + PA[xi] * plane; e.xb = x + off + PB[xi] * plane; e.dxd = novel ? rows8 : dx - x;
-                e.w = (const char*)ww + (long)(chunk * 4 + xi) * G::WG * 16; e.psb = ps * 16; e.sb = SB[xi]; e.pad_ = 0;
+                e.xa = c.x + PA[xi] * plane; e.xb = c.x + PB[xi] * plane; e.dxd = novel ? rows8 : c.dx - c.x;
+                e.w = (const char*)ww + (long)(chunk * 4 + xi) * G::WG * 16; e.psb = c.psb; e.sb = SB[xi]; e.pad_ = 0;
             }
     // sources of the skip phase: chunk sc of the block input, plane z0 (-> A) and plane z0 + 1 (-> B); ka.xs is already
     // offset so that the centre tap of the patch of output tile (z, y0, x0) is the skip's voxel (the kernel reads that
     // voxel alone, through 64-bit addresses: no bound on the skip tensors' plane strides)
     for (int sc = 0; sc < ka.nskip; ++sc)
         for (int ab = 0; ab < 2; ++ab) {
-            const bool second = sc >= ka.s_csplit;
-            const long ps = second ? ka.s2_pstride : ka.s_pstride;
-            const char* x = (const char*)(second ? ka.xs2 : ka.xs);
-            const char* dx = (const char*)(second ? ka.dxs2 : ka.dxs);
-            const long off = (long)(second ? sc - ka.s_csplit : sc) * 4 * ps * 16 + ab * plane;
+            const ChunkSrc c = skip_chunk(ka, sc);
             WinoSrc& e = wa.st[4 * ka.nchunk + 2 * sc + ab];
-            e.xa = x + off; e.xb = e.xa; e.dxd = novel ? rows8 : dx - x; e.w = (const char*)wws + (long)sc * G::TAPU * 16; e.psb = ps * 16; e.sb = 0.f; e.pad_ = 0;
+            e.xa = c.x + ab * plane; e.xb = e.xa; e.dxd = novel ? rows8 : c.dx - c.x; e.w = (const char*)wws + (long)sc * G::TAPU * 16; e.psb = c.psb; e.sb = 0.f; e.pad_ = 0;
         }
     const bool skip = ka.nskip > 0;
     if (novel) wa.dws_delta = 0;

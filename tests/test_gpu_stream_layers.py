@@ -68,7 +68,7 @@ def loaded(engine_factory):
 
 
 def kernel_name(case, prec, vel):
-    """the profile entry run_conv gives the launch (conv_name, csrc/nbe_engine_net.cpp)"""
+    """the profile entry run_conv gives the launch (conv_label, csrc/nbe_conv_select.h)"""
     tang = "vel,%s" % ("dx" if case.has_dx else "nodx") if vel else "novel,nodx"
     if prec == "f32":
         return "conv_mfma<%s,%s,ni" % (MODE[case.kind], tang)
