@@ -533,6 +533,36 @@ int nbe_zeldovich_spectrum(const void* spectrum, int64_t n, double boxsize, doub
  * receives theta_k = i (2 pi / L) ((m_0 v_0 + m_1 v_1) + m_2 v_2), added in float64 in that order.  Component c is left out
  * where n is even and |m_c| = n/2, as in nbe_zeldovich_spectrum, which keeps the field real.  out must not alias spectra. */
 int nbe_divergence_spectrum(const void* spectra, int64_t n, double boxsize, void* out, void* stream);
+/* Second-order LPT, which the reference leaves at DISCO-DJ's n_order=1 (scripts/core.py:396-397)
+ * although n_order=2 is one argument away.  With nabla^2 phi = delta, nbe_zeldovich_spectrum's psi is -grad phi.  The
+ * derivative number of axis c is d_c = m_c, or 0 where n is even and |m_c| = n/2: nbe_zeldovich_spectrum's Nyquist rule,
+ * applied once per factor.  The three passes, between the caller's transforms:
+ *
+ * nbe_lpt2_hessian_spectrum: the Hessian of phi.  Component p of the pair list (0,0), (1,1), (2,2), (0,1), (0,2), (1,2) is
+ * phi,ij_k = (double)(d_i d_j) / (double)|m|^2 delta_k with the true integer |m|^2, and 0 at m = 0; it is dimensionless (no
+ * box size), and phi,ij = -d_j psi_i holds in the library's own derivative.  out = (count, n, n, n/2+1) receives components
+ * first .. first + count - 1, 0 <= first, 1 <= count, first + count <= NBE_LPT2_COMPONENTS: pieces give the bits of the
+ * whole, so a caller short of memory makes and transforms them a few at a time.  out must not overlap spectrum.
+ *
+ * nbe_lpt2_source: hess = (6, n, n, n) float32, the six real fields in the pair order; out = (n, n, n) float32 receives
+ * S = ((h0 h1 + h0 h2) + h1 h2) - ((h3^2 + h4^2) + h5^2), the sum of the Hessian's principal 2x2 minors, per voxel in
+ * float64 in exactly that order, rounded once.  A product of two float32 is exact in float64, so the result is the bits of
+ * that float64 expression whether or not a product is fused into the add after it.  out must not overlap hess.  A
+ * grid-stride pass; 16-byte accesses where n^3 is a multiple of 4 and both pointers are 16-byte aligned, 4-byte ones
+ * otherwise (component c starts at byte 4 c n^3, so an odd n has no aligned form).
+ *
+ * nbe_lpt2_spectrum: psi_spectrum = (3, n, n, n/2+1) receives psi_c = i (L / 2 pi) d_c / |m|^2 (scale1 delta_k +
+ * scale2 S_k), 0 at m = 0: nbe_zeldovich_spectrum's pass on the sum of two spectra.  With scale1 = a and scale2 =
+ * -D_2 / D_1^2 a^2 (3/7 a^2 in an Einstein-de Sitter universe) it is psi^(1) + psi^(2), div psi^(2) = -scale2 S.
+ * psi_spectrum must not overlap delta_k or source_k; these two may be the same.
+ *
+ * max_blocks as for nbe_gaussian_spectrum: <= 0 the default grid, a positive value caps the workgroups (the same bits). */
+#define NBE_LPT2_COMPONENTS 6
+int nbe_lpt2_hessian_spectrum(const void* spectrum, int64_t n, int first, int count, void* out, int max_blocks,
+                              void* stream);
+int nbe_lpt2_source(const void* hess, int64_t n, void* out, int max_blocks, void* stream);
+int nbe_lpt2_spectrum(const void* delta_k, const void* source_k, int64_t n, double boxsize, double scale1, double scale2,
+                      void* psi_spectrum, int max_blocks, void* stream);
 /* replaces the "fourier" method of upsample_density_with_discodj (scripts/utils.py:186-234), and is its inverse for
  * n_out < n_in: destination mode m = (n_out / n_in)^3 times the source value at m, where the source value at -m is the
  * conjugate of the stored mirror mode.  n_out > n_in: 0 if any |m_c| > n_in / 2, and a factor 1/2 per axis with

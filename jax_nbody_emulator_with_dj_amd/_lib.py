@@ -127,6 +127,10 @@ SIGNATURES = {
                                          C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nbe_zeldovich_spectrum": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "nbe_divergence_spectrum": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
+    "nbe_lpt2_hessian_spectrum": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "nbe_lpt2_source": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
+    "nbe_lpt2_spectrum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                    C.c_int, C.c_void_p]),
     "nbe_spectrum_resize": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "nbe_spectrum_inject": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
                                       C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_void_p]),

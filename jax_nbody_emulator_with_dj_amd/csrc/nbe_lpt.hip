@@ -3,9 +3,11 @@
 // resize_density_grid and its helpers (scripts/utils.py:186-234, :261-346, :349-425, :531-555, :590-591) and
 // dj.evaluate_lpt_psi_at_a(n_order=1) (scripts/core.py:396-397); the divergence has no counterpart there.  The transforms
 // are the caller's (rocFFT); these are the passes between them.  The last section draws the linear field itself from a
-// seed and a tabulated P(k), or colours somebody else's white noise (scripts/core.py:263-302).  No context: no weights.
+// seed and a tabulated P(k), or colours somebody else's white noise (scripts/core.py:263-302).  The second-order LPT
+// section adds what DISCO-DJ's n_order=2 would: the Hessian of the potential, the quadratic source (the one kernel here
+// that walks voxels, not rows) and the displacement of both orders in one pass.  No context: no weights.
 //
-// Every kernel walks rows: a (64, 4) workgroup takes four rows (i0, i1) of the destination at a time, decodes the row
+// Every other kernel walks rows: a (64, 4) workgroup takes four rows (i0, i1) of the destination at a time, decodes the row
 // once (the only 64-bit division) and strides its 64 lanes along the contiguous axis, so that a wave-instruction reads
 // and writes one run of a row.  Factors are formed in float64 and every output word is rounded to float32 once.  No LDS,
 // no atomics: every destination word has one writer, so the results do not depend on the launch geometry.
@@ -71,6 +73,100 @@ __global__ __launch_bounds__(kLanes * kRows) void divergence_kernel(const float2
             const float2 v0 = src[i2], v1 = src[plane + i2], v2 = src[2 * plane + i2];
             const double re = (c0 * v0.x + c1 * v1.x) + c2 * v2.x, im = (c0 * v0.y + c1 * v1.y) + c2 * v2.y;
             dst[i2] = make_float2((float)(-kf * im), (float)(kf * re));
+        }
+    }
+}
+
+// ---- second-order LPT ------------------------------------------------------------------------------------------------------
+
+// The pairs (i, j) of the Hessian's components 0 .. 5: the diagonal first, then (0,1), (0,2), (1,2)
+constexpr int kPairs = NBE_LPT2_COMPONENTS;
+
+// phi,ij = d_i d_j / |m|^2 delta with nabla^2 phi = delta: d_c = m_c, or 0 on the row |m_c| = n/2 of an even n, which is
+// zeldovich_kernel's derivative applied once per factor.  Components first .. first + count - 1 go to out[0 .. count - 1];
+// the six factors are formed for every mode and the loop over them is unrolled, so that they stay in registers.
+__global__ __launch_bounds__(kLanes * kRows) void lpt2_hessian_kernel(const float2* __restrict__ delta,
+                                                                      float2* __restrict__ out, long long n, int first,
+                                                                      int count) {
+    const long long h = n / 2 + 1, rows = n * n, plane = rows * h;
+    const long long nyq = n % 2 == 0 ? n / 2 : -1;
+    NBE_FOR_ROWS(r, rows) {
+        const long long i0 = r / n, i1 = r - i0 * n;
+        const long long m0 = freq(i0, n), m1 = freq(i1, n), q01 = m0 * m0 + m1 * m1;
+        const long long d0 = i0 == nyq ? 0 : m0, d1 = i1 == nyq ? 0 : m1;
+        const float2* src = delta + r * h;
+        float2* dst = out + r * h;
+        for (long long i2 = threadIdx.x; i2 < h; i2 += kLanes) {
+            const long long q = q01 + i2 * i2, d2 = i2 == nyq ? 0 : i2;
+            const long long num[kPairs] = {d0 * d0, d1 * d1, d2 * d2, d0 * d1, d0 * d2, d1 * d2};
+            const float2 v = src[i2];
+#pragma unroll
+            for (int p = 0; p < kPairs; ++p) {
+                if (p < first || p >= first + count) continue;
+                const double f = q ? (double)num[p] / (double)q : 0.0;
+                dst[(p - first) * plane + i2] = make_float2((float)(f * v.x), (float)(f * v.y));
+            }
+        }
+    }
+}
+
+// S = ((h0 h1 + h0 h2) + h1 h2) - ((h3^2 + h4^2) + h5^2) in float64, rounded once.  The product of two float32 is exact
+// in float64, so a product fused into the add that follows it gives the same bits.
+__device__ inline float lpt2_source_word(float h0, float h1, float h2, float h3, float h4, float h5) {
+    const double a0 = h0, a1 = h1, a2 = h2, a3 = h3, a4 = h4, a5 = h5;
+    return (float)(((a0 * a1 + a0 * a2) + a1 * a2) - ((a3 * a3 + a4 * a4) + a5 * a5));
+}
+
+constexpr int kVoxelThreads = 256;      // the real-space pass: a grid-stride loop over the voxels
+constexpr int kVoxelBlocks = 2048;      // 8 workgroups for each of 256 compute units; the loop takes the rest
+
+// One voxel a lane and step.  The path for an odd n, where component c starts at byte 4 c n^3, which 16 does not divide.
+__global__ __launch_bounds__(kVoxelThreads) void lpt2_source_kernel(const float* __restrict__ hess,
+                                                                    float* __restrict__ out, long long cells) {
+    const long long step = (long long)gridDim.x * kVoxelThreads;
+    for (long long i = blockIdx.x * (long long)kVoxelThreads + threadIdx.x; i < cells; i += step)
+        out[i] = lpt2_source_word(hess[i], hess[cells + i], hess[2 * cells + i], hess[3 * cells + i],
+                                  hess[4 * cells + i], hess[5 * cells + i]);
+}
+
+// Four voxels a lane and step, 16 bytes per access: for cells % 4 == 0 and 16-byte aligned pointers (an even n)
+__global__ __launch_bounds__(kVoxelThreads) void lpt2_source4_kernel(const float4* __restrict__ hess,
+                                                                     float4* __restrict__ out, long long quads) {
+    const long long step = (long long)gridDim.x * kVoxelThreads;
+    for (long long i = blockIdx.x * (long long)kVoxelThreads + threadIdx.x; i < quads; i += step) {
+        const float4 h0 = hess[i], h1 = hess[quads + i], h2 = hess[2 * quads + i], h3 = hess[3 * quads + i],
+                     h4 = hess[4 * quads + i], h5 = hess[5 * quads + i];
+        out[i] = make_float4(lpt2_source_word(h0.x, h1.x, h2.x, h3.x, h4.x, h5.x),
+                             lpt2_source_word(h0.y, h1.y, h2.y, h3.y, h4.y, h5.y),
+                             lpt2_source_word(h0.z, h1.z, h2.z, h3.z, h4.z, h5.z),
+                             lpt2_source_word(h0.w, h1.w, h2.w, h3.w, h4.w, h5.w));
+    }
+}
+
+// psi_c = i c d_c / |m|^2 (a delta + b S) with c = L / (2 pi): zeldovich_kernel on the sum of two spectra, which saves
+// the pass that would add them and the three transforms of a second displacement
+__global__ __launch_bounds__(kLanes * kRows) void lpt2_displacement_kernel(const float2* __restrict__ delta,
+                                                                           const float2* __restrict__ source,
+                                                                           float2* __restrict__ psi, long long n, double c,
+                                                                           double a, double b) {
+    const long long h = n / 2 + 1, rows = n * n, plane = rows * h;
+    const long long nyq = n % 2 == 0 ? n / 2 : -1;
+    NBE_FOR_ROWS(r, rows) {
+        const long long i0 = r / n, i1 = r - i0 * n;
+        const long long m0 = freq(i0, n), m1 = freq(i1, n), q01 = m0 * m0 + m1 * m1;
+        const double c0 = i0 == nyq ? 0.0 : c * (double)m0, c1 = i1 == nyq ? 0.0 : c * (double)m1;
+        const float2* sd = delta + r * h;
+        const float2* ss = source + r * h;
+        float2* dst = psi + r * h;
+        for (long long i2 = threadIdx.x; i2 < h; i2 += kLanes) {
+            const long long q = q01 + i2 * i2;
+            const double inv = q ? 1.0 / (double)q : 0.0;
+            const double f0 = c0 * inv, f1 = c1 * inv, f2 = i2 == nyq ? 0.0 : c * (double)i2 * inv;
+            const float2 v = sd[i2], s = ss[i2];
+            const double x = a * v.x + b * s.x, y = a * v.y + b * s.y;
+            dst[i2] = make_float2((float)(-f0 * y), (float)(f0 * x));
+            dst[plane + i2] = make_float2((float)(-f1 * y), (float)(f1 * x));
+            dst[2 * plane + i2] = make_float2((float)(-f2 * y), (float)(f2 * x));
         }
     }
 }
@@ -409,6 +505,18 @@ const dim3 kBlock(kLanes, kRows);
 
 double cube(double x) { return x * x * x; }
 
+// a grid of at most max_blocks workgroups (max_blocks <= 0: as it is); the kernels loop over what is left
+dim3 capped(dim3 grid, int max_blocks) {
+    if (max_blocks > 0 && grid.x > (unsigned)max_blocks) grid.x = (unsigned)max_blocks;
+    return grid;
+}
+
+// whether the byte ranges [a, a + abytes) and [b, b + bbytes) share a byte
+bool overlap(const void* a, long long abytes, const void* b, long long bbytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
+}
+
 }  // namespace
 
 extern "C" {
@@ -431,6 +539,53 @@ int nbe_divergence_spectrum(const void* spectra, int64_t n, double boxsize, void
     hipLaunchKernelGGL(divergence_kernel, row_grid(n), kBlock, 0, (hipStream_t)stream, (const float2*)spectra,
                        (float2*)out, (long long)n, 2.0 * kPi / boxsize);
     return launched("nbe_divergence_spectrum");
+}
+
+int nbe_lpt2_hessian_spectrum(const void* spectrum, int64_t n, int first, int count, void* out, int max_blocks,
+                              void* stream) {
+    if (!spectrum || !out) return fail("nbe_lpt2_hessian_spectrum: NULL argument");
+    if (!size_ok(n)) return fail("nbe_lpt2_hessian_spectrum: n %lld not in %d .. %d", (long long)n, NBE_LPT_MIN_N, NBE_LPT_MAX_N);
+    if (first < 0 || count < 1 || first > kPairs - count)
+        return fail("nbe_lpt2_hessian_spectrum: components %d .. %d not in 0 .. %d", first, first + count - 1, kPairs - 1);
+    const long long words = 8 * n * n * (n / 2 + 1);
+    if (overlap(spectrum, words, out, count * words)) return fail("nbe_lpt2_hessian_spectrum: out aliases spectrum");
+    hipLaunchKernelGGL(lpt2_hessian_kernel, capped(row_grid(n), max_blocks), kBlock, 0, (hipStream_t)stream,
+                       (const float2*)spectrum, (float2*)out, (long long)n, first, count);
+    return launched("nbe_lpt2_hessian_spectrum");
+}
+
+int nbe_lpt2_source(const void* hess, int64_t n, void* out, int max_blocks, void* stream) {
+    if (!hess || !out) return fail("nbe_lpt2_source: NULL argument");
+    if (!size_ok(n)) return fail("nbe_lpt2_source: n %lld not in %d .. %d", (long long)n, NBE_LPT_MIN_N, NBE_LPT_MAX_N);
+    const long long cells = n * n * n;
+    if (overlap(hess, kPairs * 4 * cells, out, 4 * cells)) return fail("nbe_lpt2_source: out aliases hess");
+    const bool wide = cells % 4 == 0 && ((uintptr_t)hess | (uintptr_t)out) % 16 == 0;
+    const long long items = wide ? cells / 4 : cells;
+    long long blocks = (items + kVoxelThreads - 1) / kVoxelThreads;
+    if (blocks > kVoxelBlocks) blocks = kVoxelBlocks;
+    const dim3 grid = capped(dim3((unsigned)blocks), max_blocks);
+    if (wide)
+        hipLaunchKernelGGL(lpt2_source4_kernel, grid, dim3(kVoxelThreads), 0, (hipStream_t)stream, (const float4*)hess,
+                           (float4*)out, items);
+    else
+        hipLaunchKernelGGL(lpt2_source_kernel, grid, dim3(kVoxelThreads), 0, (hipStream_t)stream, (const float*)hess,
+                           (float*)out, items);
+    return launched("nbe_lpt2_source");
+}
+
+int nbe_lpt2_spectrum(const void* delta_k, const void* source_k, int64_t n, double boxsize, double scale1, double scale2,
+                      void* psi_spectrum, int max_blocks, void* stream) {
+    if (!delta_k || !source_k || !psi_spectrum) return fail("nbe_lpt2_spectrum: NULL argument");
+    if (!size_ok(n)) return fail("nbe_lpt2_spectrum: n %lld not in %d .. %d", (long long)n, NBE_LPT_MIN_N, NBE_LPT_MAX_N);
+    if (!(boxsize > 0.0) || !std::isfinite(boxsize) || !std::isfinite(scale1) || !std::isfinite(scale2))
+        return fail("nbe_lpt2_spectrum: bad boxsize %g or scales %g, %g", boxsize, scale1, scale2);
+    const long long words = 8 * n * n * (n / 2 + 1);
+    if (overlap(delta_k, words, psi_spectrum, 3 * words) || overlap(source_k, words, psi_spectrum, 3 * words))
+        return fail("nbe_lpt2_spectrum: psi_spectrum aliases an input");
+    hipLaunchKernelGGL(lpt2_displacement_kernel, capped(row_grid(n), max_blocks), kBlock, 0, (hipStream_t)stream,
+                       (const float2*)delta_k, (const float2*)source_k, (float2*)psi_spectrum, (long long)n,
+                       boxsize / (2.0 * kPi), scale1, scale2);
+    return launched("nbe_lpt2_spectrum");
 }
 
 int nbe_spectrum_resize(const void* src, int64_t n_in, void* dst, int64_t n_out, int sphere, void* stream) {

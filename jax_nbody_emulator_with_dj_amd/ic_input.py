@@ -19,6 +19,10 @@ table) and hands it to first-order LPT.  Here the draw, the displacement and the
 table given at z = 0.  `--fixed_amplitude` draws the Quijote "fixed" fields; `--paired` writes the phase-inverted partner
 as a second set under <dir>_paired.  `--white_noise_file FILE` colours that (N, N, N) field (e.g. the reference's
 white_noise_ngenic.npy) instead of drawing: one output directory, no --seeds, no --fixed_amplitude.
+`--lpt_order 2` also writes <dir>/lpt2_dis.npy, the second-order displacement (lpt.lpt2_displacement): `--growth2 G` is
+-D_2 / D_1^2, by default that of `--z Z --omega_m OM` (cosmology.growth_factor_2) and 3/7 without them; `--lpt2_dealias`
+forms the quadratic source on the mesh of 3 N / 2.  lpt_dis.npy, the emulator's input, stays first order; the order and G
+are recorded in ic_metadata.json.
 """
 
 import argparse
@@ -29,7 +33,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .lpt_input import read_table
+from .lpt_input import lpt2_options, read_table
 
 
 def seed_list(text):
@@ -66,6 +70,10 @@ def build_parser():
     ap.add_argument('--paired', action='store_true', help='Also write the phase-inverted partner under <dir>_paired')
     ap.add_argument('--white_noise_file', type=str, default=None,
                     help='Colour this (N, N, N) white-noise field instead of drawing one (no --seeds)')
+    ap.add_argument('--lpt_order', type=int, default=1, help='2: also write lpt2_dis.npy, the second-order displacement')
+    ap.add_argument('--growth2', type=float, default=None,
+                    help='With --lpt_order 2: -D_2 / D_1^2 (default: from --z / --omega_m, else 3/7)')
+    ap.add_argument('--lpt2_dealias', action='store_true', help='With --lpt_order 2: form the source on the mesh of 3 N / 2')
     ap.add_argument('--no-save-delta', dest='save_delta', action='store_false', help='Do not write delta_linear.npy')
     return ap
 
@@ -95,8 +103,16 @@ def growth_scale(z, omega_m):
     return float(growth_factor(z, omega_m)) / float(growth_factor(0.0, omega_m))
 
 
+def growth2_of(z, omega_m):
+    """-D_2 / D_1^2 at z in flat LambdaCDM: cosmology.growth_factor_2 over the square of the float64 growth factor."""
+    from .cosmology import growth_factor_2, _growth_factor64
+    d1 = float(_growth_factor64(float(z), float(omega_m)))
+    return -float(growth_factor_2(z, omega_m)) / (d1 * d1)
+
+
 def validate(args):
-    """Every argument error before any file is written or any device work: (seeds or None, dirs, k, pk, scale)."""
+    """Every argument error before any file is written or any device work: (seeds or None, dirs, k, pk, scale, growth2);
+    growth2 is None for a first-order run."""
     from . import lpt
     lpt._size(args.npart, '--npart')
     lpt._real(args.boxsize, '--boxsize', positive=True)
@@ -106,6 +122,11 @@ def validate(args):
         raise ValueError('--z and --omega_m go together')
     scale = growth_scale(args.z, args.omega_m) if args.z is not None else 1.0 if args.scale is None else args.scale
     scale = lpt._real(scale, '--scale', positive=True)
+    if args.lpt_order not in (1, 2):
+        raise ValueError(f'--lpt_order must be 1 or 2, got {args.lpt_order}')
+    growth2 = lpt2_options(args, args.lpt_order == 2, '--lpt_order 2')
+    if args.lpt_order == 2 and args.growth2 is None and args.z is not None:
+        growth2 = growth2_of(args.z, args.omega_m)
     if args.white_noise_file is not None:
         if args.seeds is not None:
             raise ValueError('--white_noise_file colours a given field: --seeds is not allowed')
@@ -119,7 +140,7 @@ def validate(args):
     dirs = output_dirs(args.output_dirs, args.seeds)
     k, pk = read_table(args.pk_table)
     lpt._validate_table(k, pk)
-    return args.seeds, dirs, k, pk, scale
+    return args.seeds, dirs, k, pk, scale, growth2
 
 
 def read_white(path, n):
@@ -134,9 +155,11 @@ def read_white(path, n):
     return np.ascontiguousarray(w, dtype=np.float32)
 
 
-def write_set(out_dir, delta, psi, meta, save_delta):
+def write_set(out_dir, delta, psi, meta, save_delta, psi2lpt=None):
     out_dir.mkdir(parents=True, exist_ok=True)
     np.save(out_dir / 'lpt_dis.npy', psi.cpu().numpy())
+    if psi2lpt is not None:
+        np.save(out_dir / 'lpt2_dis.npy', psi2lpt.cpu().numpy())
     if save_delta:
         np.save(out_dir / 'delta_linear.npy', delta.cpu().numpy())
     with open(out_dir / 'ic_metadata.json', 'w') as f:
@@ -150,12 +173,14 @@ def paired_dir(out_dir):
 def run(args):
     from . import lpt
     try:
-        seeds, dirs, k, pk, scale = validate(args)
+        seeds, dirs, k, pk, scale, growth2 = validate(args)
     except ValueError as e:
         sys.exit(str(e))
     n, L = args.npart, args.boxsize
     meta = dict(n=n, boxsize=L, scale=scale, fixed_amplitude=bool(args.fixed_amplitude), invert_phase=False,
-                pk_table=str(args.pk_table), seed=None, white_noise_file=args.white_noise_file)
+                pk_table=str(args.pk_table), seed=None, white_noise_file=args.white_noise_file,
+                lpt_order=args.lpt_order, growth2=growth2)
+    second = dict(growth2=growth2, dealias=bool(args.lpt2_dealias))
     if args.white_noise_file is not None:
         import torch
         from .density import _device
@@ -165,18 +190,23 @@ def run(args):
             w = torch.from_numpy(white if sign > 0 else -white).to(_device())
             delta = lpt.colour_noise(w, L, k, pk, scale=scale)
             psi = lpt.zeldovich_displacement(delta, boxsize=L)
+            psi2lpt = lpt.lpt2_displacement(delta, boxsize=L, **second) if growth2 is not None else None
             out_dir = dirs[0] if sign > 0 else paired_dir(dirs[0])
-            write_set(out_dir, delta, psi, dict(meta, invert_phase=sign < 0), args.save_delta)
+            write_set(out_dir, delta, psi, dict(meta, invert_phase=sign < 0), args.save_delta, psi2lpt)
             print(f'{args.white_noise_file} -> {out_dir / "lpt_dis.npy"}')
         print('\nDone!')
         return
     print(f'Drawing {len(seeds)} field(s) of {n}^3 in a {L} Mpc/h box, scale {scale:.6g}')
     for i, (seed, out_dir) in enumerate(zip(seeds, dirs)):
         for invert in ((False, True) if args.paired else (False,)):
-            delta, psi = lpt.linear_ics(n, L, k, pk, seed, scale=scale, fixed_amplitude=args.fixed_amplitude,
-                                        invert_phase=invert, return_delta=args.save_delta)
+            draw = dict(scale=scale, fixed_amplitude=args.fixed_amplitude, invert_phase=invert,
+                        return_delta=args.save_delta)
+            if growth2 is None:
+                (delta, psi), psi2lpt = lpt.linear_ics(n, L, k, pk, seed, **draw), None
+            else:
+                delta, psi, psi2lpt = lpt.linear_ics(n, L, k, pk, seed, order=2, **second, **draw)
             target = paired_dir(out_dir) if invert else out_dir
-            write_set(target, delta, psi, dict(meta, seed=seed, invert_phase=invert), args.save_delta)
+            write_set(target, delta, psi, dict(meta, seed=seed, invert_phase=invert), args.save_delta, psi2lpt)
             print(f'[{i + 1}/{len(seeds)}] seed {seed}{" (paired)" if invert else ""} -> {target / "lpt_dis.npy"}')
     print('\nDone!')
 

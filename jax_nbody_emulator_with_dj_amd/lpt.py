@@ -32,6 +32,12 @@ Conventions:
     delta = gaussian_field(512, 1000.0, k, pk, seed=7)                    # the field alone: one draw pass, one irfftn
     delta = colour_noise(white, 1000.0, k, pk)                            # somebody else's white noise, coloured
 
+- `lpt2_displacement` and `lpt2_source` add the second order: the initial condition of an N-body
+  run and the stronger baseline beside an emulated box.  The emulator's own input stays first order.
+
+    psi2lpt = lpt2_displacement(delta512, boxsize=1000.0, scale=D, growth2=3 / 7, dealias=True)
+    delta, psi1, psi2lpt = linear_ics(512, 1000.0, k, pk, seed=7, scale=D, order=2)
+
 Residency: NumPy in gives NumPy out; a CUDA torch tensor in gives a CUDA tensor on the same device, with no host copy,
 enqueued on torch's current stream of that device.  There is no CPU fallback: without a device the first device call
 raises NBEError.  Arguments are validated before any device work.
@@ -84,7 +90,8 @@ def _empty_spectrum(n, dev, lead=()):
 
 def zeldovich_displacement(delta, boxsize=1000.0, scale=1.0, _max_batch=None):
     """First-order LPT (Zel'dovich) displacement of a linear density field (reference scripts/core.py:396-397,
-    dj.with_lpt(n_order=1) / dj.evaluate_lpt_psi_at_a(a, n_order=1); 2LPT is not built, the reference uses n_order=1).
+    dj.with_lpt(n_order=1) / dj.evaluate_lpt_psi_at_a(a, n_order=1), the order the reference uses; second order is
+    `lpt2_displacement`).
 
     delta: cubic (n, n, n) float32, NumPy array or CUDA tensor, 2 <= n <= 2048.  boxsize: L (scalar, or a 3-tuple of equal
     values), the unit of the result.  Returns psi, (3, n, n, n) float32, channel c along array axis c: valid input to
@@ -160,6 +167,144 @@ def divergence(field, boxsize=1000.0):
         del spec
         theta = _real_field(theta_k, n)
     return _back(f, theta)
+
+
+# ---- second-order LPT ------------------------------------------------------------------------------------------------------
+
+COMPONENTS = 6                          # include/nbe.h: NBE_LPT2_COMPONENTS, the pairs (0,0) (1,1) (2,2) (0,1) (0,2) (1,2)
+EDS_GROWTH2 = 3.0 / 7.0                 # -D_2 / D_1^2 in an Einstein-de Sitter universe
+
+
+def _dealias_size(n, dealias, what):
+    """The mesh the quadratic source is formed on: n, or 3 n / 2 with `dealias` (a bool), which needs an even n."""
+    if not _flag(dealias, "dealias"):
+        return n
+    if n % 2 or 3 * n // 2 > MAX_N:
+        raise ValueError("%s: dealias=True needs an even n with 3 n / 2 <= %d, got %d" % (what, MAX_N, n))
+    return 3 * n // 2
+
+
+def _validate_lpt2(delta, boxsize, scale, growth2, dealias, what):
+    d, n, L = _field(delta, boxsize, what)
+    return d, n, L, _real(scale, "scale"), _real(growth2, "growth2"), _dealias_size(n, dealias, what)
+
+
+def _lpt2_budget(dev, n, p, what):
+    """NBEError where the six real fields on the p^3 mesh, the source, one transform in flight and the spectra at n do not
+    fit the free memory of the device."""
+    need = (COMPONENTS + 1) * 4 * p ** 3 + 16 * (p ** 3 + 2 * p * p) + 5 * 4 * (n ** 3 + 2 * n * n)
+    density._check_free_memory(dev, need, "%s: the six Hessian fields of %d^3" % (what, p),
+                               "%d fields of 4 n^3 bytes and one transform" % (COMPONENTS + 1))
+
+
+def _source_field(spec, n, p, max_batch, max_blocks=0):
+    """The real source S (p, p, p) of the half spectrum `spec` of an n^3 field: the Hessian spectra `_bk_batch` at a time
+    (nbe_lpt2_hessian_spectrum), each brought to p >= n by nbe_spectrum_resize, one batched irfftn per piece, and
+    nbe_lpt2_source over the six real fields.  Pieces give the bits of the whole."""
+    dev = spec.device
+    l = _lib.lib()
+    hess = torch.empty((COMPONENTS, p, p, p), dtype=torch.float32, device=dev)
+    batch = _bk_batch(dev, p, COMPONENTS, max_batch)
+    for first in range(0, COMPONENTS, batch):
+        count = min(batch, COMPONENTS - first)
+        hk = _empty_spectrum(n, dev, (count,))
+        _lib.check(l.nbe_lpt2_hessian_spectrum(_ptr(spec), n, first, count, _ptr(hk), max_blocks, _stream(dev)))
+        if p != n:
+            up = _empty_spectrum(p, dev, (count,))
+            for c in range(count):
+                _lib.check(l.nbe_spectrum_resize(_ptr(hk[c]), n, _ptr(up[c]), p, 0, _stream(dev)))
+            hk = up
+            del up
+        # a batch through dim=(1, 2, 3) whatever its length: see _inverse_components
+        hess[first:first + count] = torch.fft.irfftn(hk, s=(p, p, p), dim=(1, 2, 3))
+        del hk
+    out = torch.empty((p, p, p), dtype=torch.float32, device=dev)
+    _lib.check(l.nbe_lpt2_source(_ptr(hess), p, _ptr(out), max_blocks, _stream(dev)))
+    return out
+
+
+def _source_spectrum(spec, n, p, max_batch):
+    """The half spectrum (n, n, n // 2 + 1) of the source of `spec`, formed on the p^3 mesh and brought back to n."""
+    s_k = _half_spectrum(_source_field(spec, n, p, max_batch))
+    return s_k if p == n else _resize_spectrum(s_k, p, n)
+
+
+def _psi2_spectrum(spec, s_k, n, L, a, b, max_blocks=0):
+    """nbe_lpt2_spectrum on two contiguous complex64 half spectra on the device: (3, n, n, n // 2 + 1)."""
+    psi_k = _empty_spectrum(n, spec.device, (3,))
+    _lib.check(_lib.lib().nbe_lpt2_spectrum(_ptr(spec), _ptr(s_k), n, L, a, b, _ptr(psi_k), max_blocks,
+                                            _stream(spec.device)))
+    return psi_k
+
+
+def lpt2_source(delta, dealias=False, _max_batch=None):
+    """The source of the second-order LPT displacement, S = sum over i < j of (phi,ii phi,jj - phi,ij^2) with
+    nabla^2 phi = delta: the sum of the principal 2x2 minors of the Hessian of the first-order potential (DISCO-DJ's
+    n_order=2).  S is dimensionless and does not depend on the box size.
+
+    delta: cubic (n, n, n) float32, NumPy array or CUDA tensor, 2 <= n <= 2048.  Returns S, (n, n, n) float32 of the
+    input's kind.
+
+    phi,ij_k = d_i d_j / |m|^2 delta_k with d_c = m_c, or 0 where n is even and |m_c| = n/2 (the Nyquist rule of
+    `zeldovich_displacement`, once per factor, so phi,ij = -d_j psi_i in this module's own derivative); 0 at m = 0.  S is
+    formed per voxel in float64 as ((h0 h1 + h0 h2) + h1 h2) - ((h3^2 + h4^2) + h5^2) over the six fields in the order
+    (0,0), (1,1), (2,2), (0,1), (0,2), (1,2), and rounded once.  A plane wave has S = 0, and the mean of S is 0.
+
+    dealias=True (n even, 3 n / 2 <= 2048) forms the product on the mesh of 3 n / 2 points a side (the 3/2 rule): each
+    Hessian spectrum is Fourier-interpolated upwards, S is formed there, transformed, and brought back to n by the
+    "fourier" downsampling of `resize_density`.  Every mode of the result is then free of aliasing except those on the
+    Nyquist rows |m_c| = n/2 of the (even) n, which the downsampling sums over both signs.
+
+    One rfftn, six inverse transforms (batched as the free memory allows, the same bits), one real-space pass; with
+    dealias two resizing passes per field and two more transforms."""
+    d, n, L, _, _, p = _validate_lpt2(delta, 1.0, 1.0, EDS_GROWTH2, dealias, "lpt2_source")
+    dev = _device_of(d)
+    with torch.cuda.device(dev):
+        _lpt2_budget(dev, n, p, "lpt2_source")
+        spec = _half_spectrum(_to_device(d, dev, (torch.float32,)))
+        if p == n:
+            return _back(d, _source_field(spec, n, n, _max_batch))
+        return _back(d, _real_field(_source_spectrum(spec, n, p, _max_batch), n))
+
+
+def lpt2_displacement(delta, boxsize=1000.0, scale=1.0, growth2=EDS_GROWTH2, dealias=False, return_orders=False,
+                      _max_batch=None):
+    """Second-order LPT displacement of a linear density field: psi = psi1 + psi2, what DISCO-DJ's
+    evaluate_lpt_psi_at_a(a, n_order=2) returns where the reference asks for n_order=1 (scripts/core.py:396-397).  The
+    standard initial condition of an N-body run, and the stronger analytic baseline beside an emulated box; the emulator's
+    own input stays `zeldovich_displacement`.
+
+    delta, boxsize, and the result (3, n, n, n) float32 as in `zeldovich_displacement`.  With a = scale and
+    b = growth2 scale^2,
+
+        psi_k = i k / |k|^2 (a delta_k + b S_k),   S = lpt2_source(delta, dealias),
+
+    so psi1 = `zeldovich_displacement(delta, boxsize, scale)` up to rounding and div psi2 = -b S: collapse speeds up where
+    the three eigenvalues of phi,ij share a sign.  growth2 = -D_2 / D_1^2 at the epoch of the output: 3/7 in an
+    Einstein-de Sitter universe (the default), and -cosmology.growth_factor_2(z, Om) / cosmology.growth_factor(z, Om)^2 in
+    flat LambdaCDM, which stays within half a percent of 3/7.  Any finite value is taken as given; 0 leaves first order.
+
+    The plain call is one pass that reads delta_k and S_k and writes the three spectra, and eleven transforms where
+    first order has four.  return_orders=True returns (psi1, psi2) instead: two nbe_zeldovich_spectrum passes with the
+    scales a and b, and six inverse transforms, so psi1 has the bits of `zeldovich_displacement`.  dealias as in
+    `lpt2_source`.  2LPT velocities, 3LPT, glass pre-initial conditions and non-cubic boxes are not built."""
+    d, n, L, scale, growth2, p = _validate_lpt2(delta, boxsize, scale, growth2, dealias, "lpt2_displacement")
+    return_orders = _flag(return_orders, "return_orders")
+    a, b = scale, growth2 * scale * scale
+    dev = _device_of(d)
+    with torch.cuda.device(dev):
+        _lpt2_budget(dev, n, p, "lpt2_displacement")
+        spec = _half_spectrum(_to_device(d, dev, (torch.float32,)))
+        s_k = _source_spectrum(spec, n, p, _max_batch)
+        if return_orders:
+            psi1 = _inverse_components(_psi_spectrum(spec, n, L, a), n, _max_batch)
+            del spec
+            psi2 = _inverse_components(_psi_spectrum(s_k, n, L, b), n, _max_batch)
+            return _back(d, psi1), _back(d, psi2)
+        psi_k = _psi2_spectrum(spec, s_k, n, L, a, b)
+        del spec, s_k
+        psi = _inverse_components(psi_k, n, _max_batch)
+    return _back(d, psi)
 
 
 # ---- resizing --------------------------------------------------------------------------------------------------------------
@@ -512,9 +657,13 @@ def colour_noise(white, boxsize, k_table, pk_table, scale=1.0):
 
 
 def linear_ics(n, boxsize, k_table, pk_table, seed, scale=1.0, fixed_amplitude=False, invert_phase=False,
-               return_delta=True, device=None, _max_batch=None):
+               return_delta=True, device=None, _max_batch=None, order=1, growth2=EDS_GROWTH2, dealias=False):
     """Initial conditions from a seed: (delta, psi) on the device, the linear field of `gaussian_spectrum` (reference
     scripts/core.py:263-302) and its first-order LPT displacement (scripts/core.py:396-397), without a forward transform.
+
+    order=2 returns (delta, psi1, psi) instead: psi1 is what order=1 returns as psi, bit for bit, and psi is the
+    second-order displacement of `lpt2_displacement` (growth2 and dealias are its arguments), for which the drawn spectrum
+    goes straight into the Hessian pass.  `scale` rides in the field, so psi = psi1 + psi2 with a = 1 and b = growth2.
 
     The drawn spectrum goes straight into nbe_zeldovich_spectrum and through the inverse path of `zeldovich_displacement`
     (batched, or one component at a time where memory is short), so psi has the bits zeldovich_displacement's inverse path
@@ -524,11 +673,23 @@ def linear_ics(n, boxsize, k_table, pk_table, seed, scale=1.0, fixed_amplitude=F
     n, L, table, seed, scale, flags, dev, _ = _validate_draw(n, boxsize, k_table, pk_table, seed, scale, fixed_amplitude,
                                                              invert_phase, device, None, "linear_ics")
     return_delta = _flag(return_delta, "return_delta")
+    if isinstance(order, (bool, np.bool_)) or not isinstance(order, numbers.Integral) or int(order) not in (1, 2):
+        raise ValueError("order must be 1 or 2, got %r" % (order,))
+    growth2 = _real(growth2, "growth2")
+    p = _dealias_size(n, dealias, "linear_ics") if order == 2 else n
     dev = _resolve(dev)
     with torch.cuda.device(dev):
+        if order == 2:
+            _lpt2_budget(dev, n, p, "linear_ics")
         spec = _draw_spectrum(n, L, table, seed, scale, flags, dev)
         psi_k = _psi_spectrum(spec, n, L, 1.0)
         delta = _real_field(spec, n) if return_delta else None
+        if order == 1:
+            del spec
+            return delta, _inverse_components(psi_k, n, _max_batch)
+        psi1 = _inverse_components(psi_k, n, _max_batch)
+        del psi_k
+        psi_k = _psi2_spectrum(spec, _source_spectrum(spec, n, p, _max_batch), n, L, 1.0, growth2)
         del spec
         psi = _inverse_components(psi_k, n, _max_batch)
-    return delta, psi
+    return delta, psi1, psi

@@ -15,6 +15,10 @@ grid with `resize_density_grid`, take the first-order LPT displacement.  Here bo
 `--gaussian_sigma X` (Mpc/h) is the smoothing of `--downsample_method gaussian` (default boxsize / npart).
 `--upsample_method mode_inject` needs `--pk_table FILE`, the two columns k [h/Mpc] and P(k) [(Mpc/h)^3] that the
 reference writes with np.savetxt (`scripts/core.py:284-288`), and takes `--seed N`.
+`--lpt2` also writes <output_dir>/lpt2_dis.npy, the second-order displacement lpt2_displacement(resized, scale, growth2):
+the initial condition of an N-body run and the stronger baseline beside the emulated box.  `--growth2 G` is -D_2 / D_1^2
+(default 3/7, Einstein-de Sitter) and `--lpt2_dealias` forms the quadratic source on the mesh of 3 N / 2 (N even,
+3 N / 2 <= 2048).  lpt_dis.npy, the emulator's input, stays first order.
 """
 
 import argparse
@@ -42,6 +46,9 @@ def build_parser():
     ap.add_argument('--pk_table', type=str, default=None,
                     help='Two-column text file k, P(k) for --upsample_method mode_inject')
     ap.add_argument('--seed', type=int, default=0, help='Seed of the injected modes (default: 0)')
+    ap.add_argument('--lpt2', action='store_true', help='Also write lpt2_dis.npy, the second-order LPT displacement')
+    ap.add_argument('--growth2', type=float, default=None, help='With --lpt2: -D_2 / D_1^2 (default: 3/7)')
+    ap.add_argument('--lpt2_dealias', action='store_true', help='With --lpt2: form the source on the mesh of 3 N / 2')
     return ap
 
 
@@ -65,6 +72,17 @@ def read_delta(path):
     return np.ascontiguousarray(delta, dtype=np.float32)
 
 
+def lpt2_options(args, second_order, flag):
+    """growth2 of a second-order run (None: first order), after checking --growth2 and --lpt2_dealias against --npart."""
+    from . import lpt
+    if not second_order:
+        if args.growth2 is not None or args.lpt2_dealias:
+            raise ValueError(f'--growth2 and --lpt2_dealias need {flag}')
+        return None
+    lpt._dealias_size(args.npart, bool(args.lpt2_dealias), '--lpt2_dealias')
+    return lpt.EDS_GROWTH2 if args.growth2 is None else lpt._real(args.growth2, '--growth2')
+
+
 def run(args):
     from . import lpt
     if len(args.delta_files) != len(args.output_dirs):
@@ -84,6 +102,7 @@ def run(args):
             k, pk = read_table(args.pk_table)
             lpt._validate_table(k, pk)
             lpt._seed(args.seed)
+        growth2 = lpt2_options(args, args.lpt2, '--lpt2')
     except ValueError as e:
         sys.exit(str(e))
     import torch
@@ -102,6 +121,10 @@ def run(args):
                                      k_target=k, pk_target=pk, seed=args.seed)
         psi = lpt.zeldovich_displacement(resized, boxsize=args.boxsize, scale=args.scale)
         np.save(out_dir / 'lpt_dis.npy', psi.cpu().numpy())
+        if args.lpt2:
+            psi = lpt.lpt2_displacement(resized, boxsize=args.boxsize, scale=args.scale, growth2=growth2,
+                                        dealias=args.lpt2_dealias)
+            np.save(out_dir / 'lpt2_dis.npy', psi.cpu().numpy())
         print(f'[{i + 1}/{len(args.delta_files)}] {delta.shape[0]}^3 -> {out_dir / "lpt_dis.npy"}')
     print('\nDone!')
 
