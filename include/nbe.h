@@ -620,6 +620,53 @@ int nbe_block_average(const void* src, int64_t n_in, void* dst, int64_t n_out, v
  * periodic trilinear interpolation of src (n_in^3 float32) at the nodes i n_in / n_out; n_in divides n_out */
 int nbe_trilinear_upsample(const void* src, int64_t n_in, void* dst, int64_t n_out, void* stream);
 
+/* ---- Pairwise velocities (no context) ------------------------------------------------------------------
+ * Velocity moments per bin of separation: the mean pairwise (streaming) velocity v12(r) and the
+ * dispersions sigma_r(r), sigma_t(r) of the streaming model (Peebles 1980; Fisher 1995; Scoccimarro 2004), the
+ * pairwise-velocity statistics that go with the counts of Corrfunc's theory module (theory.DD, theory.vpf), and the infall
+ * and dispersion profile of matter about halos.  The reference has no such step: it checks its velocity field only through
+ * redshift-space positions.  Pointers, `stream` and asynchrony as for "Density"; records, sorted keys, thresholds, the rule
+ * T_b < q <= T_{b+1}, ncell and its adjacency condition exactly as for "Pairs", whose code decides every bin.
+ *
+ * One exponent e per call with max |v_c| < 2^e over all components of all catalogues of the call; W_c = rint(v_c 2^(20 - e)).
+ * For a pair (a, o) in a bin: d_c = the minimum-image X_c(o) - X_c(a), dW_c = W_c(o) - W_c(a), u = sum dW_c d_c (int64), the
+ * radial word vr = sign(u) floor(|u| / sqrt(q) + 1/2), decided by 128-bit integer comparisons (vr = 0 for q = 0; vr < 0 is
+ * approach), and |dW|^2 = sum dW_c^2.  A bin holds six 64-bit words: N, S1 = sum vr, sum (vr^2 & (2^24 - 1)),
+ * sum (vr^2 >> 24), and the same two for |dW|^2; vr^2, |dW|^2 < 2^44, so no word overflows below 2^39 pairs a bin.  All are
+ * sums of integers fixed by the pair alone: the same bits for every launch geometry, form, row order and stream.  The calls,
+ * per catalogue: nbe_pair_coords or nbe_fof_cells, the caller's sort of `keys`, nbe_fof_gather, nbe_velocity_words; then
+ * nbe_pair_velocity or nbe_halo_velocity_profiles. */
+#define NBE_VELOCITY_BITS 20
+#define NBE_VELOCITY_SUMS 6
+/* velocity = (count, 3) row-major float32 / float64 (lattice 0; dtype NBE_F32 / NBE_F64) or (3, count) float32 / float16
+ * (lattice 1; NBE_F32 / NBE_F16), finite with |v| < 2^exponent (the caller's check: nbe_quantity_range); sorted =
+ * nbe_fof_gather's records of the catalogue, whose p is the order of the sort.  words = count records of 4 int32 (W_0, W_1,
+ * W_2, 0) receives the words of row sorted[j].p at position j: the word and the gather in one pass. */
+int nbe_velocity_words(const void* velocity, int dtype, int lattice, int64_t count, int exponent, const void* sorted,
+                       int max_blocks, void* words, void* stream);
+/* nbe_pair_count's arguments with nmu = 1 and the velocity records wordsA / wordsB beside the sorted records (sortedB, keysB,
+ * wordsB all NULL: the auto count, each unordered pair once -- the terms do not depend on which row is called a).  sums =
+ * (nbins, 6) 64-bit words, zeroed by the caller: N (unsigned) and the five sums (two's complement).  One thread per sorted
+ * row of A, a per-workgroup LDS image of 6 nbins words flushed once with 64-bit global atomics. */
+int nbe_pair_velocity(const void* sortedA, const void* keysA, const void* wordsA, int64_t countA, const void* sortedB,
+                      const void* keysB, const void* wordsB, int64_t countB, int ncell, const int64_t* thresholds, int nbins,
+                      int max_blocks, void* sums, void* stream);
+/* nbe_pair_velocity with its form chosen by the caller (tools/time_pairvel.py and the tests; the same bits): 0 the LDS image,
+ * 1 every term added to the global table directly. */
+int nbe_pair_velocity_form(const void* sortedA, const void* keysA, const void* wordsA, int64_t countA, const void* sortedB,
+                           const void* keysB, const void* wordsB, int64_t countB, int ncell, const int64_t* thresholds,
+                           int nbins, int max_blocks, int form, void* sums, void* stream);
+/* nbe_halo_profiles's arguments with the velocity records: wordsA those of the centres, or NULL for centres at rest (the
+ * matter velocity in the box frame); wordsB those of the matter.  sums = (countA, nbins, 6) int64 row-major, NOT zeroed by
+ * the caller: row p (the centre's index before the sort) is written whole with plain stores by the workgroup (form 0) or
+ * wave (form 1) that owns it.  The form is chosen as nbe_halo_profiles chooses its own. */
+int nbe_halo_velocity_profiles(const void* sortedA, const void* keysA, const void* wordsA, int64_t countA, const void* sortedB,
+                               const void* keysB, const void* wordsB, int64_t countB, int ncell, const int64_t* thresholds,
+                               int nbins, int max_blocks, void* sums, void* stream);
+int nbe_halo_velocity_profiles_form(const void* sortedA, const void* keysA, const void* wordsA, int64_t countA,
+                                    const void* sortedB, const void* keysB, const void* wordsB, int64_t countB, int ncell,
+                                    const int64_t* thresholds, int nbins, int max_blocks, int form, void* sums, void* stream);
+
 /* ---- Profiles (no context) ---------------------------------------------------------------------------
  * Radial count profiles around centres: one histogram of separations per centre, from which the
  * host forms density profiles and spherical-overdensity radii and masses.  The reference has no such step: its

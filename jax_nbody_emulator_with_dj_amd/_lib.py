@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NBE_LIB") or os.path.join(_HERE, "libnbe.so")   # NBE_LIB: timing-probe builds only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ("nbe_kernels.hip", "nbe_kernels_h3.hip", "nbe_density.hip", "nbe_lpt.hip", "nbe_fof.hip", "nbe_pairs.hip",
-           "nbe_profiles.hip", "nbe_engine.cpp", "nbe_engine_net.cpp", "nbe_engine_weights.cpp", "nbe_engine_box.cpp", "nbe_engine_brick.cpp",
+           "nbe_profiles.hip", "nbe_pairvel.hip", "nbe_engine.cpp", "nbe_engine_net.cpp", "nbe_engine_weights.cpp", "nbe_engine_box.cpp", "nbe_engine_brick.cpp",
            "nbe_engine_probe.cpp", "nbe_engine_test.cpp")
 
 
@@ -125,6 +125,19 @@ SIGNATURES = {
                                     C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nbe_halo_profiles_form": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                          C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nbe_velocity_words": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                     C.c_void_p]),
+    "nbe_pair_velocity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nbe_pair_velocity_form": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p]),
+    "nbe_halo_velocity_profiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p]),
+    "nbe_halo_velocity_profiles_form": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int,
+                                                  C.c_int, C.c_void_p, C.c_void_p]),
     "nbe_zeldovich_spectrum": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "nbe_divergence_spectrum": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
     "nbe_lpt2_hessian_spectrum": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),

@@ -23,7 +23,18 @@ xi = DD / RR - 1 on the host in float64 with the analytic RR = N (N - 1) / 2 V_b
 (cross), V_b = 4 pi / 3 (r_{b+1}^3 - r_b^3), dmu = 1 / nmu (1 without mu bins), and xi_l(s_b) = (2 l + 1) sum_m xi(s_b, mu_m)
 int_{m / nmu}^{(m + 1) / nmu} L_l(mu) dmu for l = 0, 2, 4 with the exact polynomial integrals.
 
-Not built: weights, non-uniform mu bins, r_max >= L / 3, and the mesh-based xi(r) (an inverse FFT of |delta_k|^2).
+Pairwise velocities (tests/pairvel_ref.py restates them): pairwise_velocity gives, per radial bin of
+the same pairs, the mean streaming velocity v12(r) and the dispersions sigma_r(r), sigma_t(r) of the streaming model.  One
+exponent e per call with max |v_c| < 2^e over all components of both catalogues; W_c = rint(v_c 2^(20 - e)).  For a pair (a, o):
+d_c the minimum-image X_c(o) - X_c(a), dW_c = W_c(o) - W_c(a), u = sum dW_c d_c in int64 and the radial word vr = sign(u)
+floor(|u| / |d| + 1/2), decided by 128-bit integer comparisons (0 for d = 0; vr < 0 is approach).  A bin holds N and five
+int64 sums: S1 = sum vr, sum (vr^2 & (2^24 - 1)), sum (vr^2 >> 24) and the same two of |dW|^2, all fixed by the pair alone,
+hence the same bits for every launch geometry, form, row order and stream.  On the host in float64: v12 = 2^(e - 20) S1 / N,
+<v_r^2> = 4^(e - 20) (2^24 hi + lo) / N, sigma_r^2 = <v_r^2> - v12^2, <v_t^2> = (<|dv|^2> - <v_r^2>) / 2 per transverse
+direction, NaN where N = 0.
+
+Not built: weights, non-uniform mu bins, r_max >= L / 3, the mesh-based xi(r) (an inverse FFT of |delta_k|^2), and for the
+velocities mu bins, pair weights and line-of-sight moments in (r, mu).
 
 Residency as in density.py: NumPy in gives NumPy out, CUDA tensors in give CUDA tensors on their device, on torch's current
 stream.  There is no CPU fallback.  Arguments are validated before any device work.
@@ -44,7 +55,8 @@ try:
 except Exception:  # pragma: no cover
     torch = None
 
-__all__ = ["pair_counts", "correlation_function", "pair_geometry", "analytic_rr", "legendre_bin_integrals", "multipoles"]
+__all__ = ["pair_counts", "correlation_function", "pair_geometry", "analytic_rr", "legendre_bin_integrals", "multipoles",
+           "pairwise_velocity", "velocity_moments"]
 
 _U = 1 << 30                    # include/nbe.h, "Halos": coordinate units per box side
 _MIN_N, _MAX_N = 2, 1024        # NBE_FOF_MIN_N, NBE_FOF_MAX_N
@@ -260,4 +272,168 @@ def correlation_function(a, boxsize, r_edges, b=None, nmu=None, los=2):
         new["xi0"], new["xi2"], new["xi4"] = multipoles(xi)
     for k, v in new.items():
         out[k] = torch.from_numpy(v).to(dev) if tens else v
+    return out
+
+
+# ---- pairwise velocities ------------------------------------------------------------------------
+
+VELOCITY_BITS, VELOCITY_SPLIT = 20, 24          # NBE_VELOCITY_BITS; a square below 2^44 is summed as its low 24 bits and the rest
+MAX_PAIRS_PER_BIN = 1 << 39                     # beyond it a sum of squares' high parts could leave int64
+VELOCITY_BYTES = 16                             # a velocity record per row, beside BYTES_PER_PARTICLE
+VELOCITY_FORMS = (0, 1)                         # nbe_pair_velocity_form: the LDS image, global atomics
+
+
+def _velocity(v, cat, name, what):
+    """The velocity array of the catalogue `cat` (_catalogue's triple), validated: its shape, and float32 / float64 for
+    positions, float32 / float16 for a lattice."""
+    v = _check_array(v, name)
+    if tuple(v.shape) != tuple(cat[0].shape):
+        raise ValueError("%s: %s must have its catalogue's shape %s, got %s" % (what, name, tuple(cat[0].shape), tuple(v.shape)))
+    ok = ("float32", "float64") if cat[1] == "positions" else ("float32", "float16")
+    if _dtype_name(v) not in ok:
+        raise ValueError("%s: %s must be %s or %s, got %s" % (what, name, ok[0], ok[1], _dtype_name(v)))
+    _same_kind(cat[0], v, "%s: the catalogue" % what, name)
+    return v
+
+
+def _velocity_exponent(l, tensors, s, dev, what):
+    """The exponent e of a call, max |v| < 2^e over every device tensor given (0 for all zeros): nbe_quantity_range on the
+    values as one channel, the float64 maximum for float64.  ValueError for a non-finite value."""
+    top, bad = 0.0, 0
+    for vd in tensors:
+        if vd.dtype == torch.float64:
+            bad += int((~torch.isfinite(vd)).sum().item())
+            top = max(top, float(torch.nan_to_num(vd, nan=0.0, posinf=0.0, neginf=0.0).abs().max().item()))
+            continue
+        rng = torch.zeros(2, dtype=torch.int32, device=dev)
+        _lib.check(l.nbe_quantity_range(_ptr(vd), 1 if vd.dtype == torch.float16 else 0, 1, vd.numel(), _ptr(rng), s))
+        r = rng.cpu().numpy()
+        bad += int(r[1:].view(np.uint32)[0])
+        top = max(top, float(r[:1].view(np.float32)[0]))
+    if bad:
+        raise ValueError("%s: %d value(s) of the velocity are not finite" % (what, bad))
+    return int(math.frexp(top)[1])
+
+
+def _velocity_words(l, vd, kind, rows, e, P, blocks, dev, s):
+    """The velocity records (rows, 4) int32 parallel to the sorted records P."""
+    W = torch.empty((rows, 4), dtype=torch.int32, device=dev)
+    dtype = {torch.float32: 0, torch.float16: 1, torch.float64: 2}[vd.dtype]
+    _lib.check(l.nbe_velocity_words(_ptr(vd), dtype, 1 if kind == "lattice" else 0, rows, e, _ptr(P), blocks, _ptr(W), s))
+    return W
+
+
+def _moments(A, VA, B, VB, L, T, ncell, blocks, form=None, timer=None, records=None):
+    """Device work of pairwise_velocity: ((nb, 6) int64 tensor of N and the five sums, the exponent).  `form` as
+    nbe_pair_velocity_form (None: the library's choice); `timer` and `records` as profiles._count (tools/time_pairvel.py)."""
+    l = _lib.lib()
+    dev = _device_of(A[0])
+    tick = timer or (lambda name: None)
+    nb = len(T) - 1
+    thresholds = (C.c_int64 * (nb + 1))(*T)
+    with torch.cuda.device(dev):
+        s = _stream(dev)
+        tick("range")
+        va = _on_device(VA, dev)
+        vb = None if B is None else _on_device(VB, dev)
+        e = _velocity_exponent(l, [va] if vb is None else [va, vb], s, dev, "pairwise_velocity")
+        PA, skA = _sorted_records(l, A[0], A[1], A[2], L, ncell, blocks, dev, s, tick)
+        PB = skB = WB = None
+        if B is not None:
+            PB, skB = _sorted_records(l, B[0], B[1], B[2], L, ncell, blocks, dev, s, tick)
+        tick("words")
+        WA = _velocity_words(l, va, A[1], A[2], e, PA, blocks, dev, s)
+        if B is not None:
+            WB = _velocity_words(l, vb, B[1], B[2], e, PB, blocks, dev, s)
+        tick("moments")
+        sums = torch.zeros((nb, 6), dtype=torch.int64, device=dev)
+        opt = lambda t: _ptr(t) if t is not None else None
+        args = (_ptr(PA), _ptr(skA), _ptr(WA), A[2], opt(PB), opt(skB), opt(WB), B[2] if B is not None else 0, ncell,
+                thresholds, nb, blocks)
+        if form is None:
+            _lib.check(l.nbe_pair_velocity(*args, _ptr(sums), s))
+        else:
+            _lib.check(l.nbe_pair_velocity_form(*args, int(form), _ptr(sums), s))
+        tick(None)
+        if records is not None:
+            records.update(PA=PA, skA=skA, WA=WA, PB=PB, skB=skB, WB=WB)
+    return sums, e
+
+
+def check_pairs_per_bin(npairs, what):
+    """NBEError where a bin holds more than 2^39 pairs: vr^2, |dW|^2 < 2^44 keep the low sums below 2^63 for any count, the
+    high sums (below 2^20 a pair) only up to 2^43 pairs, and S1 (|vr| < 2^23) up to 2^40; 2^39 leaves a factor of two."""
+    top = int(np.max(npairs)) if np.size(npairs) else 0
+    if top > MAX_PAIRS_PER_BIN:
+        raise _lib.NBEError("%s: %d pairs in one bin exceed 2^39: the velocity sums could leave int64" % (what, top))
+
+
+def velocity_moments(npairs, sums, exponent):
+    """The float64 moments of the exact integers, on the host: a dict v12, vr2, sigma_r, vt2, sigma_t of the shape of npairs.
+    npairs (...,) and sums (..., 5) are pairwise_velocity's (or radial_velocity_moments's counts and sums, or sums of them
+    over halos); exponent its e.  v12 = 2^(e - 20) S1 / N; vr2 = <v_r^2> = 4^(e - 20) (2^24 hi + lo) / N; sigma_r =
+    sqrt(max(vr2 - v12^2, 0)); vt2 = (<|dv|^2> - vr2) / 2, per transverse direction; sigma_t = sqrt(max(vt2, 0)) -- the
+    rounding of a radial word can carry vr2 past <|dv|^2> by a unit of 4^(e - 20) where the motion is radial.  NaN where
+    N = 0."""
+    host = lambda a: a.cpu().numpy() if _is_torch(a) else np.asarray(a)
+    n, s = host(npairs), host(sums)
+    if n.dtype.kind not in "iu" or s.dtype.kind not in "iu" or s.shape != n.shape + (5,):
+        raise ValueError("velocity_moments: npairs must be an integer table and sums its (..., 5) sums, got %s %s and %s %s"
+                         % (n.dtype, n.shape, s.dtype, s.shape))
+    if isinstance(exponent, (bool, np.bool_)) or not isinstance(exponent, numbers.Integral):
+        raise ValueError("velocity_moments: exponent must be an int, got %r" % (exponent,))
+    nf, f = n.astype(np.float64), s.astype(np.float64)
+    unit, split = math.ldexp(1.0, int(exponent) - VELOCITY_BITS), float(1 << VELOCITY_SPLIT)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v12 = unit * f[..., 0] / nf
+        vr2 = unit * unit * (split * f[..., 2] + f[..., 1]) / nf
+        dv2 = unit * unit * (split * f[..., 4] + f[..., 3]) / nf
+        vt2 = 0.5 * (dv2 - vr2)
+        return {"v12": v12, "vr2": vr2, "sigma_r": np.sqrt(np.maximum(vr2 - v12 * v12, 0.0)), "vt2": vt2,
+                "sigma_t": np.sqrt(np.maximum(vt2, 0.0))}
+
+
+def _check_form(form, forms, what):
+    if form is not None and (isinstance(form, (bool, np.bool_)) or form not in forms):
+        raise ValueError("%s: _form must be None or one of %s, got %r" % (what, forms, form))
+    return form
+
+
+def pairwise_velocity(a, vel_a, boxsize, r_edges, b=None, vel_b=None, _max_blocks=None, _form=None):
+    """The mean pairwise (streaming) velocity v12(r) and the pairwise dispersions sigma_r(r), sigma_t(r) of one catalogue
+    (b=None: each unordered pair of distinct rows once) or between two: the ingredients of the streaming model of
+    xi(s, mu).  The module docstring has the definition.
+
+    a, b: catalogues as pair_counts takes them.  vel_a, vel_b: their velocities, of the catalogue's shape -- (count, 3)
+    float32 / float64 beside positions, (3, n, n, n) float32 / float16 beside a displacement --, finite, of the catalogue's
+    kind and device; vel_b goes with b.  boxsize, r_edges: as pair_counts.  `_max_blocks` caps the grid of every launch and
+    `_form` picks the kernel's form (0 the LDS image, 1 global atomics) for the tests: the sums depend on neither.
+
+    Returns a dict: npairs int64 (nb,), the bits of pair_counts's; sums int64 (nb, 5): S1, vr^2 low and high, |dW|^2 low and
+    high; v12, vr2, sigma_r, vt2, sigma_t float64 (nb,) as velocity_moments forms them (v12 < 0: approach); r_edges float64;
+    thresholds int64 -- NumPy arrays for NumPy input, tensors on the input's device for tensors --, exponent, ncell, count_a
+    and count_b (ints; count_b is None for an auto count).
+
+    Raises ValueError, before any device work, for bad shapes, kinds or edges; ValueError for a non-finite velocity or
+    position or |x_c / L| >= 2^20 (no partial result is returned); NBEError when the device's free memory cannot take 112
+    bytes per row, or when a bin holds more than 2^39 pairs."""
+    A, B, L, edges, T, ncell, _, _, blocks = _validate(a, boxsize, r_edges, b, None, 2, _max_blocks)
+    if (B is None) != (vel_b is None):
+        raise ValueError("pairwise_velocity: b and vel_b go together")
+    VA = _velocity(vel_a, A, "vel_a", "pairwise_velocity")
+    VB = None if B is None else _velocity(vel_b, B, "vel_b", "pairwise_velocity")
+    form = _check_form(_form, VELOCITY_FORMS, "pairwise_velocity")
+    dev = _device_of(A[0])
+    rows, each = A[2] + (B[2] if B is not None else 0), BYTES_PER_PARTICLE + VELOCITY_BYTES
+    _check_free_memory(dev, each * rows, "pairwise_velocity: %d rows" % rows, "%d bytes each" % each)
+    table, e = _moments(A, VA, B, VB, L, T, ncell, blocks, form)
+    host = table.cpu().numpy()
+    check_pairs_per_bin(host[:, 0], "pairwise_velocity")
+    tens = _is_torch(A[0])
+    kind = (lambda v: torch.from_numpy(v).to(dev)) if tens else (lambda v: v)
+    out = {"npairs": table[:, 0].contiguous() if tens else host[:, 0].copy(),
+           "sums": table[:, 1:].contiguous() if tens else host[:, 1:].copy()}
+    out.update({k: kind(v) for k, v in velocity_moments(host[:, 0], host[:, 1:], e).items()})
+    out.update(r_edges=kind(edges), thresholds=kind(np.array(T, dtype=np.int64)), exponent=e, ncell=ncell, count_a=A[2],
+               count_b=None if B is None else B[2])
     return out

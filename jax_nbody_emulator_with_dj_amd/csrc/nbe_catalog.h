@@ -1,6 +1,6 @@
-// The integer layer of the catalogue kernels (nbe_fof.hip, nbe_pairs.hip, nbe_profiles.hip; DESIGN.md sections 12.5, 12.7,
-// 12.8): coordinates, cells and keys, the union-find, the bin of a pair, the ranges of sorted records that a particle meets
-// and the per-row bodies of the coordinate and gather kernels.  Every function is inline and __host__ __device__ (or host
+// The integer layer of the catalogue kernels (nbe_fof.hip, nbe_pairs.hip, nbe_profiles.hip, nbe_pairvel.hip; DESIGN.md
+// sections 12.5, 12.7, 12.8, 12.9): coordinates, cells and keys, the union-find, the bin of a pair, the ranges of sorted
+// records that a particle meets, the velocity moments of a pair and the per-row bodies of the coordinate and gather kernels.  Every function is inline and __host__ __device__ (or host
 // only): no kernel, no entry point, no LDS, no wave intrinsic.  The kernels are loops around these bodies, and
 // tools/catalog_host_walk.hip walks the same bodies serially on the host.
 //
@@ -372,6 +372,125 @@ __host__ __device__ inline void profile_stream(const FofParticle& me, const FofP
         long long at = q;
         const int t = pair_ranges_locate(rlen, &at);
         add(pair_bin(me, B[rlo[t] + at], T, nb, s, 1, 0));
+    }
+}
+
+// ---- velocity moments of a pair (nbe_pairvel.hip) -------------------------------------------------
+//
+// One exponent e per call with max |v_c| < 2^e over every component of every catalogue of the call; W_c = rint(v_c 2^(20 - e)),
+// |W_c| <= 2^20.  For a pair (a, o) with d_c = fof_diff(X_c(o), X_c(a)), q = sum d_c^2 > 0 and dW_c = W_c(o) - W_c(a)
+// (|dW_c| <= 2^21): u = sum dW_c d_c, an exact 64-bit integer (|u| <= |dW| sqrt(q) < 2^52); the radial word is
+// vr = sign(u) k with k = floor(|u| / sqrt(q) + 1/2), the k >= 0 with (2 k - 1)^2 q <= 4 u^2 < (2 k + 1)^2 q, decided by
+// 128-bit products (k <= |dW| + 1/2 < 2^23, so both sides stay below 2^107); vr = 0 for q = 0.  |dW|^2 = sum dW_c^2 needs no
+// rounding.  A tie 4 u^2 = (2 k + 1)^2 q cannot occur for u != 0 (section 12.9), and d -> -d, dW -> -dW leaves u alone: the
+// terms of a pair do not depend on which of its rows is called a.
+
+constexpr int kVelBits = NBE_VELOCITY_BITS;                // |W_c| <= 2^20
+constexpr int kVelSplit = 24;                              // a square x < 2^44 is summed as x & (2^24 - 1) and x >> 24
+constexpr int kVelSums = NBE_VELOCITY_SUMS;                              // per bin: N, S1, vr^2 lo, vr^2 hi, |dW|^2 lo, |dW|^2 hi
+
+struct VelWord { int w0, w1, w2, pad; };                   // parallel to the sorted FofParticle records, one 16-byte load
+
+// W = rint(v 2^(20 - e)); 0 for a value that is not finite or not below 2^e, which the caller has excluded
+__host__ __device__ inline int velocity_word(double v, int e) {
+    const double t = ldexp(v, kVelBits - e);
+    return fabs(t) <= 1048576.0 ? (int)rint(t) : 0;
+}
+
+__host__ __device__ inline double velocity_load(const void* p, int dtype, long long i) {
+    return dtype == NBE_F64 ? ((const double*)p)[i] : dtype == NBE_F16 ? (double)(float)((const _Float16*)p)[i]
+                                                                       : (double)((const float*)p)[i];
+}
+
+// the velocity record at sorted position j: the words of row P[j].p of vel, which is (count, 3) row-major (lattice = 0) or
+// (3, count) (lattice = 1)
+__host__ __device__ inline VelWord velocity_gather_record(const void* vel, int dtype, int lattice, long long count, int e,
+                                                          const FofParticle* P, long long j) {
+    const long long p = P[j].p;
+    VelWord w;
+    w.w0 = velocity_word(velocity_load(vel, dtype, lattice ? p : 3 * p), e);
+    w.w1 = velocity_word(velocity_load(vel, dtype, lattice ? count + p : 3 * p + 1), e);
+    w.w2 = velocity_word(velocity_load(vel, dtype, lattice ? 2 * count + p : 3 * p + 2), e);
+    w.pad = 0;
+    return w;
+}
+
+struct PairVelocity { long long vr, vr2, dw2; };
+
+// (2 k + j)^2 q <= 4 u^2 for j = -1 or +1 and 2 k + j >= 0, exactly
+__host__ __device__ inline bool pair_vr_le(unsigned long long k, int j, unsigned long long q, unsigned long long au) {
+    const unsigned long long m = 2 * k + j;
+    return (unsigned __int128)(m * m) * q <= (unsigned __int128)(2 * au) * (2 * au);
+}
+
+// the terms of the pair (a, o) with the velocity records wa, wo (see above).  The float estimate of k only says where the
+// exact comparisons start.
+__host__ __device__ inline PairVelocity pair_velocity_terms(const FofParticle& a, const VelWord& wa, const FofParticle& o,
+                                                            const VelWord& wo) {
+    const long long d0 = fof_diff(o.x0, a.x0), d1 = fof_diff(o.x1, a.x1), d2 = fof_diff(o.x2, a.x2);
+    const long long e0 = (long long)wo.w0 - wa.w0, e1 = (long long)wo.w1 - wa.w1, e2 = (long long)wo.w2 - wa.w2;
+    PairVelocity r;
+    r.dw2 = e0 * e0 + e1 * e1 + e2 * e2;
+    r.vr = r.vr2 = 0;
+    const unsigned long long q = (unsigned long long)(d0 * d0 + d1 * d1 + d2 * d2);
+    const long long u = e0 * d0 + e1 * d1 + e2 * d2;
+    if (q == 0 || u == 0) return r;
+    const unsigned long long au = (unsigned long long)(u < 0 ? -u : u);
+    unsigned long long k = (unsigned long long)((double)au / sqrt((double)q) + 0.5);
+    while (k > 0 && !pair_vr_le(k, -1, q, au)) --k;       // (2 k - 1)^2 q <= 4 u^2
+    while (pair_vr_le(k, 1, q, au)) ++k;                   // 4 u^2 < (2 k + 1)^2 q
+    r.vr = u < 0 ? -(long long)k : (long long)k;
+    r.vr2 = (long long)(k * k);
+    return r;
+}
+
+// image[6 b ..] += (1, vr, vr^2 lo, vr^2 hi, |dW|^2 lo, |dW|^2 hi) through add(index, unsigned 64-bit word); the signed vr
+// is added as its two's-complement word
+template <typename Add>
+__host__ __device__ inline void pair_velocity_add(int b, const PairVelocity& t, Add add) {
+    const unsigned long long mask = (1ull << kVelSplit) - 1;
+    add(kVelSums * b, 1ull);
+    add(kVelSums * b + 1, (unsigned long long)t.vr);
+    add(kVelSums * b + 2, (unsigned long long)t.vr2 & mask);
+    add(kVelSums * b + 3, (unsigned long long)t.vr2 >> kVelSplit);
+    add(kVelSums * b + 4, (unsigned long long)t.dw2 & mask);
+    add(kVelSums * b + 5, (unsigned long long)t.dw2 >> kVelSplit);
+}
+
+// pair_count_particle with nmu = 1 and the velocity records VA, VB beside A, B: the record of B is read only for a pair
+// that is in a bin
+template <typename Add>
+__host__ __device__ inline void pair_velocity_particle(const FofParticle* A, const VelWord* VA, long long i, const FofParticle* B,
+                                                       const VelWord* VB, const long long* skB, long long countB, int ncell,
+                                                       bool half, const long long* T, int nb, int s, Add add) {
+    const FofParticle me = A[i];
+    const VelWord mine = VA[i];
+    const int c0 = fof_cell(me.x0, ncell), c1 = fof_cell(me.x1, ncell), c2 = fof_cell(me.x2, ncell);
+    for (int t = 0; t < (half ? 10 : kPairRanges); ++t) {
+        long long lo, hi;
+        pair_range(skB, countB, c0, c1, c2, ncell, half, t, &lo, &hi);
+        if (half && t == 0) lo = i + 1;                    // the rest of the own cell: i lies inside this range
+        for (long long j = lo; j < hi; ++j) {
+            const FofParticle o = B[j];
+            const int b = pair_bin(me, o, T, nb, s, 1, 0);
+            if (b >= 0) pair_velocity_add(b, pair_velocity_terms(me, mine, o, VB[j]), add);
+        }
+    }
+}
+
+// profile_stream with the velocity record `mine` of the centre (zero: the box frame) and VB beside B
+template <typename Add>
+__host__ __device__ inline void profile_velocity_stream(const FofParticle& me, const VelWord& mine, const FofParticle* B,
+                                                        const VelWord* VB, const long long* rlo, const long long* rlen,
+                                                        long long total, long long first, long long step, const long long* T,
+                                                        int nb, int s, Add add) {
+    for (long long q = first; q < total; q += step) {
+        long long at = q;
+        const int t = pair_ranges_locate(rlen, &at);
+        const long long j = rlo[t] + at;
+        const FofParticle o = B[j];
+        const int b = pair_bin(me, o, T, nb, s, 1, 0);
+        if (b >= 0) pair_velocity_add(b, pair_velocity_terms(me, mine, o, VB[j]), add);
     }
 }
 

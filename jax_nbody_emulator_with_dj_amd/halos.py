@@ -14,10 +14,13 @@ Here the displacement stays where `process_box` left it:
     hb = halo_bias(cat, delta_m, 1000.0, min_length=100)                            # P_hh, P_mm, P_hm, r(k), bias, shot noise
     xi = halo_correlation(cat, 1000.0, np.linspace(1.0, 50.0, 21), min_length=100)  # xi_hh(r) by pair counts; matter=: xi_hm
     hp = halo_profiles(cat, displacement, 1000.0, profile_edges(0.05, 5.0, 20), overdensity=200.0)   # counts (H, 20), R, N
+    vp = halo_velocity_profiles(cat, displacement, velocity, 1000.0, edges)         # v_r, sigma_r, sigma_t (H, nb); cat with CMVelocity
+    v12 = halo_pairwise_velocity(cat, 1000.0, np.linspace(1.0, 50.0, 21))           # v12, sigma_r, sigma_t of the halos
 
     python -m jax_nbody_emulator_with_dj_amd.halos --displacement_file emu_dis.npy --output_dir out/ [--halo_pk 256]
         [--halo_xi [--xi_rmin 1 --xi_rmax 50 --xi_nbins 20 --xi_log] [--xi_nmu N]]
         [--halo_profiles [--profile_rmin 0.05 --profile_rmax 5 --profile_nbins 20] [--so_overdensity 200 --so_reference mean]]
+        [--velocity_file emu_vel.npy [--halo_vprofiles] [--halo_v12]]
 
 Definition (DESIGN.md section 12.5 has the proofs; tests/fof_ref.py restates it in NumPy).  With U = 2^30, particle
 p = (i0 n + i1) n + i2 of the (n, n, n) lattice has the integer coordinates X_c = rint((i_c / n + psi_c / L) U) mod U,
@@ -56,7 +59,7 @@ except Exception:  # pragma: no cover
     torch = None
 
 __all__ = ["fof_halos", "particle_mass", "halo_mass_function", "density_slab", "paint_halos", "halo_bias",
-           "halo_correlation", "halo_profiles"]
+           "halo_correlation", "halo_profiles", "halo_velocity_profiles", "halo_pairwise_velocity"]
 
 _U = 1 << 30                    # include/nbe.h, "Halos": coordinate units per box side
 _MIN_N, _MAX_N = 2, 1024        # NBE_FOF_MIN_N, NBE_FOF_MAX_N
@@ -405,8 +408,50 @@ def halo_profiles(cat, matter, boxsize, r_edges, min_length=None, max_length=Non
     return out
 
 
+def _select_moving_halos(cat, min_length, max_length, what):
+    """_select_halos for a function that reads CMVelocity: (rows mask or None, count)."""
+    if isinstance(cat, dict) and "CMPosition" in cat and "CMVelocity" not in cat:
+        raise ValueError("%s needs a catalogue with CMVelocity (fof_halos(..., velocity=v))" % what)
+    return _select_halos(cat, None, min_length, max_length, False)
+
+
+def halo_velocity_profiles(cat, displacement, velocity, boxsize, r_edges, min_length=None, max_length=None):
+    """The infall and velocity-dispersion profile of the matter about every halo of a catalogue
+    (profiles.radial_velocity_moments with fof_halos's CMPosition and CMVelocity as the centres and their velocities; the
+    velocity-profile step of a halo finder such as Rockstar or AHF, which the reference does not have).
+
+    cat, min_length, max_length: the halos and their selection as paint_halos; the catalogue needs CMVelocity.
+    displacement, velocity: the matter, (count, 3) positions with (count, 3) velocities or the (3, n, n, n) fields, of the
+    catalogue's kind.  boxsize, r_edges: as profiles.radial_counts.  Returns radial_velocity_moments's dict (counts, sums,
+    exponent, r_edges, thresholds, ncell, count_a, count_b) with v_r, sigma_r, sigma_t, vr2, vt2 (H, nb) of
+    profiles.velocity_profile (host float64; v_r < 0 is infall), Length, the selected halos' lengths in the kind of the
+    catalogue, and count, their number, added."""
+    from .profiles import radial_velocity_moments, velocity_profile
+    keep, count = _select_moving_halos(cat, min_length, max_length, "halo_velocity_profiles")
+    rows = (lambda a: a) if keep is None else (lambda a: a[keep])
+    out = radial_velocity_moments(rows(cat["CMPosition"]), rows(cat["CMVelocity"]), displacement, velocity, boxsize, r_edges)
+    out.update(velocity_profile(out["counts"], out["sums"], out["exponent"]))
+    out["Length"] = rows(cat["Length"])
+    out["count"] = count
+    return out
+
+
+def halo_pairwise_velocity(cat, boxsize, r_edges, min_length=None, max_length=None):
+    """The mean pairwise velocity v12(r) and the pairwise dispersions of a halo catalogue
+    (correlation.pairwise_velocity of fof_halos's CMPosition and CMVelocity).  cat, min_length, max_length: the halos and
+    their selection as paint_halos; the catalogue needs CMVelocity.  Returns pairwise_velocity's dict with count, the halos
+    selected, added."""
+    from .correlation import pairwise_velocity
+    keep, count = _select_moving_halos(cat, min_length, max_length, "halo_pairwise_velocity")
+    rows = (lambda a: a) if keep is None else (lambda a: a[keep])
+    out = pairwise_velocity(rows(cat["CMPosition"]), rows(cat["CMVelocity"]), boxsize, r_edges)
+    out["count"] = count
+    return out
+
+
 HALO_DELTA_FILE, HALO_PK_FILE, HALO_XI_FILE = "halo_delta.npy", "halo_pk.npz", "halo_xi.npz"
 HALO_PROFILES_FILE = "halo_profiles.npz"
+HALO_VPROFILES_FILE, HALO_V12_FILE = "halo_vprofiles.npz", "halo_v12.npz"
 HALO_WEIGHT_NAMES = {"number": None, "length": "Length"}
 
 
@@ -501,6 +546,10 @@ def build_parser():
                     help="with --halo_pk: count halos, or weight each by its particle count (default: number)")
     add_xi_arguments(ap)
     add_profile_arguments(ap)
+    ap.add_argument("--velocity_file", default=None,
+                    help="the velocity of the same particles, (3, N, N, N) or (N, N, N, 3) (.npy): the catalogue's CMVelocity, "
+                         "for --halo_vprofiles and --halo_v12")
+    add_velocity_arguments(ap)
     return ap
 
 
@@ -528,6 +577,8 @@ def xi_options(args, boxsize, die):
     if getattr(args, "xi_log", False):
         given.append("xi_log")
     if not getattr(args, "halo_xi", False):
+        if getattr(args, "halo_v12", False):                # --halo_v12 takes its edges from the same options
+            given = [n for n in given if n == "xi_nmu"]
         if given:
             die("--%s needs --halo_xi" % given[0])
         return None
@@ -573,6 +624,8 @@ def profile_options(args, boxsize, die):
     names = ("profile_rmin", "profile_rmax", "profile_nbins", "so_overdensity", "so_reference")
     given = [n for n in names if getattr(args, n, None) is not None]
     if not getattr(args, "halo_profiles", False):
+        if getattr(args, "halo_vprofiles", False):          # --halo_vprofiles takes its edges from the same options
+            given = [n for n in given if n.startswith("so_")]
         if given:
             die("--%s needs --halo_profiles" % given[0])
         return None
@@ -614,6 +667,79 @@ def save_halo_profiles(out_dir, arrs):
     np.savez(os.path.join(str(out_dir), HALO_PROFILES_FILE), **arrs)
 
 
+def add_velocity_arguments(ap, suppress=False):
+    """The options --halo_vprofiles and --halo_v12, shared with run_emulator as add_xi_arguments's are."""
+    flag = argparse.SUPPRESS if suppress else False
+    ap.add_argument("--halo_vprofiles", action="store_true", default=flag,
+                    help="with a velocity: also the infall and dispersion profile of the matter about every halo, in the "
+                         "shells of --profile_rmin / --profile_rmax / --profile_nbins: %s (r_edges, r_mid, counts, sums, exponent, "
+                         "v_r, sigma_r, sigma_t, Length, count) inside the output directory" % HALO_VPROFILES_FILE)
+    ap.add_argument("--halo_v12", action="store_true", default=flag,
+                    help="with a velocity: also the mean pairwise velocity and the pairwise dispersions of the halos, in the "
+                         "bins of --xi_rmin / --xi_rmax / --xi_nbins / --xi_log: %s (r_edges, r_mid, npairs, sums, exponent, v12, "
+                         "sigma_r, sigma_t, count) inside the output directory" % HALO_V12_FILE)
+
+
+def velocity_moment_options(args, boxsize, have_velocity, die, need="--velocity_file"):
+    """The settings of --halo_vprofiles and --halo_v12 of a parsed command line as a dict (vprofiles: r_edges or None, v12:
+    r_edges or None), or None without either; `die(message)` where the velocity they need (`need` names its option) is
+    missing and for edges that pair_counts would refuse."""
+    from .correlation import pair_geometry
+    from .profiles import profile_edges
+    vp, v12 = bool(getattr(args, "halo_vprofiles", False)), bool(getattr(args, "halo_v12", False))
+    if not (vp or v12):
+        return None
+    if not have_velocity:
+        die("--%s needs %s" % ("halo_vprofiles" if vp else "halo_v12", need))
+    get = lambda n, d: d if getattr(args, n, None) is None else getattr(args, n)
+    out = dict(vprofiles=None, v12=None)
+    try:
+        if vp:
+            out["vprofiles"] = profile_edges(get("profile_rmin", 0.05), get("profile_rmax", 5.0), get("profile_nbins", 20))
+            pair_geometry(boxsize, out["vprofiles"])
+        if v12:
+            out["v12"] = xi_edges(get("xi_rmin", 1.0), get("xi_rmax", 50.0), get("xi_nbins", 20), bool(getattr(args, "xi_log", False)))
+            pair_geometry(boxsize, out["v12"])
+    except ValueError as e:
+        die(str(e))
+    return out
+
+
+def halo_vprofile_arrays(cat, matter, velocity, boxsize, r_edges):
+    """The arrays of halo_vprofiles.npz for a catalogue with CMVelocity and the displacement and velocity it was found in:
+    r_edges, r_mid, counts, sums, exponent, v_r, sigma_r, sigma_t, Length, count -- or None for a catalogue without a halo."""
+    if int(cat["Length"].shape[0]) == 0:
+        return None
+    out = halo_velocity_profiles(cat, matter, velocity, boxsize, r_edges)
+    to_np = lambda a: a.cpu().numpy() if _is_torch(a) else np.asarray(a)
+    edges = to_np(out["r_edges"])
+    return dict(r_edges=edges, r_mid=0.5 * (edges[1:] + edges[:-1]), counts=to_np(out["counts"]), sums=to_np(out["sums"]),
+                exponent=np.int64(out["exponent"]), v_r=out["v_r"], sigma_r=out["sigma_r"], sigma_t=out["sigma_t"],
+                Length=to_np(out["Length"]).astype(np.int64), count=np.int64(out["count"]))
+
+
+def halo_v12_arrays(cat, boxsize, r_edges):
+    """The arrays of halo_v12.npz for a catalogue with CMVelocity: r_edges, r_mid, npairs, sums, exponent, v12, sigma_r,
+    sigma_t, count -- or None for a catalogue without a halo."""
+    if int(cat["Length"].shape[0]) == 0:
+        return None
+    out = halo_pairwise_velocity(cat, boxsize, r_edges)
+    to_np = lambda a: a.cpu().numpy() if _is_torch(a) else np.asarray(a)
+    edges = to_np(out["r_edges"])
+    arrs = {k: to_np(out[k]) for k in ("npairs", "sums", "v12", "sigma_r", "sigma_t")}
+    arrs.update(r_edges=edges, r_mid=0.5 * (edges[1:] + edges[:-1]), exponent=np.int64(out["exponent"]),
+                count=np.int64(out["count"]))
+    return arrs
+
+
+def save_halo_velocity(out_dir, name, arrs):
+    """Write halo_vprofiles.npz or halo_v12.npz (`name`), or print the one line that says why not (None for no halo)."""
+    if arrs is None:
+        print("no halo in the catalogue: %s is not written" % name)
+        return
+    np.savez(os.path.join(str(out_dir), name), **arrs)
+
+
 def save_halo_spectra(out_dir, spectra):
     """Write halo_delta.npy and halo_pk.npz, or print the one line that says why not (halo_spectra's None)."""
     if spectra is None:
@@ -643,9 +769,18 @@ def main(argv=None):
         sys.exit("--halo_pk must be >= 1, got %d" % a.halo_pk)
     xi = xi_options(a, a.boxsize, sys.exit)
     prof = profile_options(a, a.boxsize, sys.exit)
+    vmom = velocity_moment_options(a, a.boxsize, a.velocity_file is not None, sys.exit)
+    if a.velocity_file is not None and vmom is None:
+        sys.exit("--velocity_file needs --halo_vprofiles or --halo_v12")
     disp = load_displacement(a.displacement_file)
+    vel = None
+    if vmom is not None:
+        vel = load_displacement(a.velocity_file)
+        if vel.shape != disp.shape:
+            sys.exit("--velocity_file has shape %s, the displacement %s." % (tuple(vel.shape), tuple(disp.shape)))
     try:
-        cat = fof_halos(disp, boxsize=a.boxsize, linking_length=a.linking_length, nmin=a.nmin, absolute=a.absolute_linking)
+        cat = fof_halos(disp, boxsize=a.boxsize, linking_length=a.linking_length, nmin=a.nmin, absolute=a.absolute_linking,
+                        velocity=vel)
     except ValueError as e:
         sys.exit(str(e))
     os.makedirs(a.output_dir, exist_ok=True)
@@ -662,6 +797,10 @@ def main(argv=None):
     if prof is not None:
         save_halo_profiles(a.output_dir, halo_profile_arrays(cat, disp, a.boxsize, disp.shape[1], a.omega_m, prof["r_edges"],
                                                              prof["overdensity"], prof["reference"]))
+    if vmom is not None and vmom["vprofiles"] is not None:
+        save_halo_velocity(a.output_dir, HALO_VPROFILES_FILE, halo_vprofile_arrays(cat, disp, vel, a.boxsize, vmom["vprofiles"]))
+    if vmom is not None and vmom["v12"] is not None:
+        save_halo_velocity(a.output_dir, HALO_V12_FILE, halo_v12_arrays(cat, a.boxsize, vmom["v12"]))
 
 
 if __name__ == "__main__":

@@ -21,7 +21,14 @@ Omega_m(z) ("critical").  j* is the smallest j with D_j < Delta; j* = 0 gives fl
 edge), no such j flag 2 (r_max too small), both with NaN radius and mass; otherwise ln R is the linear interpolation in
 (ln r, ln D) between (r_{j*}, D_{j*-1}) and (r_{j*+1}, D_{j*}), and N = Delta nbar 4 pi / 3 R^3.
 
-Not built: velocity profiles and infall, unbinding, an exact sort-based R_Delta, most-bound centres, weights, r_max >= L / 3.
+Velocity profiles: radial_velocity_moments adds, beside every count, the five integer sums of
+correlation.pairwise_velocity for the pairs (centre, row of matter), and velocity_profile forms the infall v_r and the
+dispersions sigma_r, sigma_t per shell from them.
+
+    vm = radial_velocity_moments(cat["CMPosition"], cat["CMVelocity"], displacement, velocity, 1000.0, edges)
+    vp = velocity_profile(vm["counts"], vm["sums"], vm["exponent"])                 # v_r, sigma_r, sigma_t (H, 20)
+
+Not built: unbinding, an exact sort-based R_Delta, most-bound centres, weights, r_max >= L / 3.
 
 Residency as in correlation.py: NumPy in gives NumPy out, CUDA tensors in give CUDA tensors on their device, on torch's
 current stream.  There is no CPU fallback.  Arguments are validated before any device work.
@@ -43,6 +50,8 @@ except Exception:  # pragma: no cover
     torch = None
 
 __all__ = ["radial_counts", "density_profile", "spherical_overdensity", "stack_profiles", "profile_edges"]
+# the velocity functions (radial_velocity_moments, velocity_profile, stack_velocity_profiles) are imported by name: the
+# star-import surface stays what tests/test_profiles_host.py pins
 
 FORMS = (0, 1)                  # nbe_halo_profiles_form: a workgroup per centre, a wave per centre
 
@@ -227,3 +236,96 @@ def stack_profiles(counts, lengths, length_edges):
     np.add.at(stacked, which[inside], c[inside].astype(np.int64))
     np.add.at(halos, which[inside], 1)
     return stacked, halos
+
+
+# ---- velocity moments about centres ---------------------------------------------------------------
+
+def _velocity_count(A, VA, B, VB, L, T, ncell, blocks, form=None, timer=None, records=None):
+    """Device work of radial_velocity_moments: ((H, nb, 6) int64 tensor of N and the five sums, the exponent).  VA None:
+    centres at rest.  `form`, `timer` and `records` as _count (tools/time_pairvel.py)."""
+    l = _lib.lib()
+    dev = _device_of(A[0])
+    tick = timer or (lambda name: None)
+    nb = len(T) - 1
+    thresholds = (C.c_int64 * (nb + 1))(*T)
+    with torch.cuda.device(dev):
+        s = _stream(dev)
+        tick("range")
+        va = None if VA is None else CF._on_device(VA, dev)
+        vb = CF._on_device(VB, dev)
+        e = CF._velocity_exponent(l, [vb] if va is None else [va, vb], s, dev, "radial_velocity_moments")
+        PA, skA = CF._sorted_records(l, A[0], A[1], A[2], L, ncell, blocks, dev, s, tick)
+        PB, skB = CF._sorted_records(l, B[0], B[1], B[2], L, ncell, blocks, dev, s, tick)
+        tick("words")
+        WA = None if va is None else CF._velocity_words(l, va, A[1], A[2], e, PA, blocks, dev, s)
+        WB = CF._velocity_words(l, vb, B[1], B[2], e, PB, blocks, dev, s)
+        tick("moments")
+        sums = torch.empty((A[2], nb, 6), dtype=torch.int64, device=dev)            # every row is written whole
+        args = (_ptr(PA), _ptr(skA), _ptr(WA) if WA is not None else None, A[2], _ptr(PB), _ptr(skB), _ptr(WB), B[2], ncell,
+                thresholds, nb, blocks)
+        if form is None:
+            _lib.check(l.nbe_halo_velocity_profiles(*args, _ptr(sums), s))
+        else:
+            _lib.check(l.nbe_halo_velocity_profiles_form(*args, int(form), _ptr(sums), s))
+        tick(None)
+        if records is not None:
+            records.update(PA=PA, skA=skA, WA=WA, PB=PB, skB=skB, WB=WB)
+    return sums, e
+
+
+def radial_velocity_moments(centres, centre_velocity, matter, matter_velocity, boxsize, r_edges, _max_blocks=None, _form=None):
+    """The velocity moments of `matter` per shell about every centre: radial_counts's counts and, beside each, the five
+    integer sums of correlation.pairwise_velocity for the pairs (centre, row of matter) -- infall and dispersion profiles.
+    correlation's module docstring has the definition; the velocity of a pair is the matter's minus the centre's, and its
+    radial word is negative for infall.
+
+    centres, matter, boxsize, r_edges: as radial_counts.  centre_velocity: (H, 3) float32 / float64, or None for centres at
+    rest (the matter velocity is then taken in the box frame).  matter_velocity: of the shape of matter, (count, 3) float32
+    / float64 or (3, n, n, n) float32 / float16.  All of one kind and device.  `_max_blocks` and `_form` as radial_counts:
+    the sums depend on neither.
+
+    Returns a dict: counts int64 (H, nb), the bits of radial_counts's; sums int64 (H, nb, 5): S1, vr^2 low and high, |dW|^2
+    low and high; r_edges float64; thresholds int64 -- NumPy arrays for NumPy input, tensors on the input's device for
+    tensors --, exponent, ncell, count_a (H) and count_b (ints).  velocity_profile turns counts and sums into v_r, sigma_r
+    and sigma_t.  The column sums over the centres are pairwise_velocity(a=centres, b=matter)'s.
+
+    Raises as radial_counts, and ValueError for a non-finite velocity; the memory check takes 112 bytes per row of both
+    catalogues plus 48 H nb."""
+    A, B, L, edges, T, ncell, blocks, form = _validate(centres, matter, boxsize, r_edges, _max_blocks, _form)
+    VA = None if centre_velocity is None else CF._velocity(centre_velocity, A, "centre_velocity", "radial_velocity_moments")
+    VB = CF._velocity(matter_velocity, B, "matter_velocity", "radial_velocity_moments")
+    dev = _device_of(A[0])
+    rows, H, nb = A[2] + B[2], A[2], len(T) - 1
+    each = CF.BYTES_PER_PARTICLE + CF.VELOCITY_BYTES
+    _check_free_memory(dev, each * rows + 48 * H * nb, "radial_velocity_moments: %d rows and %d x %d x 6 sums" % (rows, H, nb),
+                       "%d bytes a row, 48 a bin" % each)
+    table, e = _velocity_count(A, VA, B, VB, L, T, ncell, blocks, form)
+    tens = _is_torch(A[0])
+    kind = (lambda v: torch.from_numpy(v).to(dev)) if tens else (lambda v: v)
+    host = None if tens else table.cpu().numpy()
+    return {"counts": table[:, :, 0].contiguous() if tens else host[:, :, 0].copy(),
+            "sums": table[:, :, 1:].contiguous() if tens else host[:, :, 1:].copy(), "r_edges": kind(edges),
+            "thresholds": kind(np.array(T, dtype=np.int64)), "exponent": e, "ncell": ncell, "count_a": A[2], "count_b": B[2]}
+
+
+def velocity_profile(counts, sums, exponent):
+    """The infall and dispersion profile of radial_velocity_moments's tables, on the host in float64 from the exact integers
+    (correlation.velocity_moments): a dict with v_r, the mean radial velocity of the matter about the centre (negative:
+    infall), sigma_r, the radial dispersion about that mean, and sigma_t, the dispersion per transverse direction, each
+    of the shape of counts and NaN for an empty shell; vr2 and vt2, the second moments they come from.  counts (..., nb) and
+    sums (..., nb, 5) may be a table per centre or integer sums of such tables over halos (stack_velocity_profiles)."""
+    m = CF.velocity_moments(counts, sums, exponent)
+    return {"v_r": m["v12"], "sigma_r": m["sigma_r"], "sigma_t": m["sigma_t"], "vr2": m["vr2"], "vt2": m["vt2"]}
+
+
+def stack_velocity_profiles(counts, sums, lengths, length_edges):
+    """stack_profiles for radial_velocity_moments's tables: (stacked counts (nl, nb), stacked sums (nl, nb, 5), halos (nl,)),
+    all int64 -- every sum is an integer, so a stack of halos is the sum of their rows, and velocity_profile takes it as it
+    takes one halo's."""
+    c, s = _host(counts), _host(sums)
+    if c.ndim != 2 or s.shape != c.shape + (5,) or s.dtype.kind not in "iu":
+        raise ValueError("stack_velocity_profiles: counts must be an (H, nb) integer table and sums (H, nb, 5), got %s and %s"
+                         % (c.shape, s.shape))
+    stacked, halos = stack_profiles(c, lengths, length_edges)
+    ssum, _ = stack_profiles(s.reshape(c.shape[0], -1), lengths, length_edges)
+    return stacked, ssum.reshape(stacked.shape + (5,)), halos

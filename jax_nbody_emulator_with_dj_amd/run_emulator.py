@@ -48,8 +48,11 @@ pairs (halos.halo_correlation; `--xi_rmin 1 --xi_rmax 50 --xi_nbins 20 [--xi_log
 xi4), and `--halo_profiles` counts the matter in shells about every halo (halos.halo_profiles; `--profile_rmin 0.05
 --profile_rmax 5 --profile_nbins 20 [--so_overdensity 200 --so_reference mean|critical]`) and writes
 <output_dir>/halo_profiles.npz (r_edges, r_mid, counts, rho, Length, R_delta, N_delta, M_delta, flag, overdensity,
-reference, count; the spherical-overdensity radii and masses at the box's redshift); a box without a halo writes none of
-these and says so.  `--xcorr FILE` (with --density_res) writes <output_dir>/emu_xcorr.npz, density.cross_correlation of
+reference, count; the spherical-overdensity radii and masses at the box's redshift), and with `--vel` `--halo_vprofiles`
+writes <output_dir>/halo_vprofiles.npz (halos.halo_velocity_profiles in the shells of --profile_*: r_edges, r_mid, counts,
+sums, exponent, v_r, sigma_r, sigma_t, Length, count) and `--halo_v12` <output_dir>/halo_v12.npz
+(halos.halo_pairwise_velocity in the bins of --xi_*: r_edges, r_mid, npairs, sums, exponent, v12, sigma_r, sigma_t, count),
+the catalogue's CMVelocity coming from the emulated velocity; a box without a halo writes none of these and says so. `--xcorr FILE` (with --density_res) writes <output_dir>/emu_xcorr.npz, density.cross_correlation of
 emu_delta against the saved (N, N, N) field FILE (k, p_aa, p_bb, p_ab, nmodes, r, transfer, bias): the reference's
 emulator-against-target check (scripts/utils.py:1451-1470).
 
@@ -229,6 +232,8 @@ def build_parser():
     add_xi_arguments(ap, suppress=True)                      # --halo_xi, --xi_rmin, --xi_rmax, --xi_nbins, --xi_log, --xi_nmu
     from .halos import add_profile_arguments
     add_profile_arguments(ap, suppress=True)                 # --halo_profiles, --profile_rmin / _rmax / _nbins, --so_overdensity / _reference
+    from .halos import add_velocity_arguments
+    add_velocity_arguments(ap, suppress=True)                # --halo_vprofiles, --halo_v12
     ap.add_argument('--xcorr', type=Path, metavar='FILE', default=argparse.SUPPRESS,
                     help='With --density_res: also write r(k), transfer and bias of emu_delta against the saved (N, N, N) '
                          'float32 field FILE to <output_dir>/emu_xcorr.npz')
@@ -386,6 +391,17 @@ def halo_profile_options(args):
     return prof
 
 
+def halo_velocity_options(args):
+    """The settings of --halo_vprofiles and --halo_v12 (halos.velocity_moment_options: vprofiles, v12), or None without
+    either.  They need --fof and --vel."""
+    from .halos import velocity_moment_options
+    vmom = velocity_moment_options(args, float(getattr(args, 'boxsize', 1000.0)), bool(getattr(args, 'vel', True)), _die,
+                                   need='--vel')
+    if vmom is not None and not getattr(args, 'fof', False):
+        _die('--%s needs --fof' % ('halo_vprofiles' if vmom['vprofiles'] is not None else 'halo_v12'))
+    return vmom
+
+
 def xcorr_option(args):
     """The (N, N, N) float32 field of --xcorr, or None without it.  It needs --density_res and that mesh size."""
     path = getattr(args, 'xcorr', None)
@@ -401,13 +417,16 @@ def xcorr_option(args):
     return np.ascontiguousarray(field, dtype=np.float32)
 
 
-def fof_catalog(disp, fof, Om, halo=None, xi=None, profiles=None, z=0.0):
+def fof_catalog(disp, fof, Om, halo=None, xi=None, profiles=None, z=0.0, vel=None, vmom=None):
     """The arrays of fof_catalog.npz for the device displacement of one box, as {'fof': arrays}; with the settings of
     --halo_pk also 'halo': halos.halo_spectra's result (None for a box without a halo); with those of --halo_xi also
     'halo_xi': halos.halo_xi_arrays's; with those of --halo_profiles also 'halo_profiles': halos.halo_profile_arrays's at
-    redshift z."""
-    from .halos import catalog_arrays, fof_halos, halo_profile_arrays, halo_spectra, halo_xi_arrays
-    cat = fof_halos(disp, boxsize=fof['boxsize'], linking_length=fof['linking_length'], nmin=fof['nmin'])
+    redshift z; with those of --halo_vprofiles / --halo_v12 (vmom, and the device velocity vel, which then gives the
+    catalogue its CMVelocity) also 'halo_vprofiles': halos.halo_vprofile_arrays's and 'halo_v12': halos.halo_v12_arrays's."""
+    from .halos import (catalog_arrays, fof_halos, halo_profile_arrays, halo_spectra, halo_v12_arrays, halo_vprofile_arrays,
+                        halo_xi_arrays)
+    cat = fof_halos(disp, boxsize=fof['boxsize'], linking_length=fof['linking_length'], nmin=fof['nmin'],
+                    velocity=vel if vmom is not None else None)
     out = {'fof': catalog_arrays(cat, int(disp.shape[1]), fof['boxsize'], Om, fof['linking_length'], False, fof['nmin'])}
     if halo is not None:
         out['halo'] = halo_spectra(cat, disp, fof['boxsize'], halo['res'], halo['worder'], halo['weight'])
@@ -416,6 +435,10 @@ def fof_catalog(disp, fof, Om, halo=None, xi=None, profiles=None, z=0.0):
     if profiles is not None:
         out['halo_profiles'] = halo_profile_arrays(cat, disp, fof['boxsize'], int(disp.shape[1]), Om, profiles['r_edges'],
                                                    profiles['overdensity'], profiles['reference'], z=z)
+    if vmom is not None and vmom['vprofiles'] is not None:
+        out['halo_vprofiles'] = halo_vprofile_arrays(cat, disp, vel, fof['boxsize'], vmom['vprofiles'])
+    if vmom is not None and vmom['v12'] is not None:
+        out['halo_v12'] = halo_v12_arrays(cat, fof['boxsize'], vmom['v12'])
     return out
 
 
@@ -474,6 +497,7 @@ def run(args):
     halo = halo_options(args)
     halo_xi = halo_xi_options(args)
     halo_prof = halo_profile_options(args)
+    halo_vmom = halo_velocity_options(args)
     target = xcorr_option(args)
     if bispec:
         for k1, k2 in BISPECTRUM_CONFIGS:                    # density.bispectrum's closure condition, before any work
@@ -490,7 +514,8 @@ def run(args):
         print(f"  Halos: FoF b = {fof['linking_length']}, nmin {fof['nmin']}, boxsize {fof['boxsize']}"
               + (f", halo spectra on a {halo['res']}^3 mesh" if halo is not None else "")
               + (f", halo pairs in {len(halo_xi['r_edges']) - 1} bins" if halo_xi is not None else "")
-              + (f", halo profiles in {len(halo_prof['r_edges']) - 1} bins" if halo_prof is not None else ""))
+              + (f", halo profiles in {len(halo_prof['r_edges']) - 1} bins" if halo_prof is not None else "")
+              + (", halo velocity moments" if halo_vmom is not None else ""))
     print()
 
     shape = None
@@ -535,6 +560,10 @@ def run(args):
         if extra is not None and 'halo_profiles' in extra:
             from .halos import save_halo_profiles
             save_halo_profiles(out_dir, extra['halo_profiles'])
+        for key in ('halo_vprofiles', 'halo_v12'):
+            if extra is not None and key in extra:
+                from .halos import save_halo_velocity
+                save_halo_velocity(out_dir, key + '.npz', extra[key])
         if extra is not None and 'delta' in extra:
             np.save(out_dir / 'emu_delta.npy', extra['delta'])
             if 'pk' in extra:
@@ -569,7 +598,8 @@ def run(args):
         box_t = torch.from_numpy(np.ascontiguousarray(dis_in)).to('cuda')
         result = emu.process_box(box_t, z=z, Om=Om, show_progress=not args.quiet)
         disp = result[0] if args.vel else result
-        extra = {} if fof is None else fof_catalog(disp, fof, Om, halo, halo_xi, halo_prof, float(z))
+        extra = {} if fof is None else fof_catalog(disp, fof, Om, halo, halo_xi, halo_prof, float(z),
+                                                   vel=result[1] if halo_vmom is not None else None, vmom=halo_vmom)
         out_dt = np.dtype(args.output_precision)
         if dens is None:
             host = tuple(t.cpu().numpy().astype(out_dt, copy=False) for t in (result if args.vel else (result,)))

@@ -9,7 +9,7 @@
 //
 // tests/test_catalog_host_walk.py builds the same program without the sanitizers and runs the same cases.
 //
-//     catalog_host_walk fof|pairs|profiles CASE RESULT
+//     catalog_host_walk fof|pairs|profiles|velocity CASE RESULT
 //
 // A catalogue in a case file is (kind, rows) in the header and its array in the body.  kind: 0 (rows, 3) float32 positions,
 // 1 (rows, 3) float64 positions, 2 a (3, n, n, n) float32 displacement with rows = n, 3 the same in float16, -1 no catalogue
@@ -21,6 +21,11 @@
 //             counts (nb, nmu) int64.
 //   profiles  int64 kindA, rowsA, kindB, rowsB, ncell, nb; float64 L; int64 T[nb + 1]; the centres; the matter.  Result:
 //             int64 bad; counts (rowsA, nb) int64 as a workgroup of 256 lanes walks a centre; the same for a wave of 64.
+//   velocity  int64 kindA, rowsA, kindB, rowsB, ncell, nb, e, has_va; float64 L; int64 T[nb + 1]; A; with has_va the velocity of
+//             A in the layout and dtype of A's kind; B; the velocity of B.  Result: int64 bad; the (nb, 6) words of
+//             nbe_pair_velocity (zero without has_va); with a catalogue B the (rowsA, nb, 6) words of
+//             nbe_halo_velocity_profiles as a workgroup of 256 lanes walks a centre (at rest without has_va), and as a wave of
+//             64 does.  The program is held to tests/pairvel_ref.py (tests/test_pairvel_host_walk.py).
 
 #include "../jax_nbody_emulator_with_dj_amd/csrc/nbe_catalog.h"
 
@@ -179,11 +184,72 @@ static void walk_profiles(FILE* f, FILE* o) {
     write_n(o, wave);
 }
 
+// nbe_velocity_words: the velocity of a catalogue of `kind` (its layout and dtype) as records beside c.P
+static std::vector<VelWord> load_words(FILE* f, long long kind, const Catalogue& c, int e) {
+    const long long count = (long long)c.P.size();
+    const int dtype = kind == 1 ? NBE_F64 : kind == 3 ? NBE_F16 : NBE_F32;
+    const std::vector<char> vel = read_n<char>(f, (size_t)(3 * count * (kind == 1 ? 8 : kind == 3 ? 2 : 4)));
+    std::vector<VelWord> w((size_t)count);
+    for (long long j = 0; j < count; ++j) w[(size_t)j] = velocity_gather_record(vel.data(), dtype, kind >= 2, count, e, c.P.data(), j);
+    return w;
+}
+
+// one centre as a group of `lanes` lanes takes it in nbe_halo_velocity_profiles: the ranges, the image of 6 nb words, the row
+static void walk_velocity_centre(const FofParticle& me, const VelWord& mine, const Catalogue& B, const std::vector<VelWord>& WB,
+                                 int ncell, const std::vector<long long>& T, int nb, int s, int lanes,
+                                 std::vector<long long>& sums) {
+    std::vector<long long> rlo(kPairRanges), rlen(kPairRanges);
+    for (int t = 0; t < kPairRanges; ++t) profile_range(me, B.sk.data(), (long long)B.P.size(), ncell, t, rlo.data(), rlen.data());
+    const long long total = pair_ranges_total(rlen.data());
+    std::vector<unsigned long long> image((size_t)nb * kVelSums, 0ull);
+    for (int lane = lanes - 1; lane >= 0; --lane)
+        profile_velocity_stream(me, mine, B.P.data(), WB.data(), rlo.data(), rlen.data(), total, lane, lanes, T.data(), nb, s,
+                                [&](int at, unsigned long long v) { image.at((size_t)at) += v; });
+    for (int k = 0; k < nb * kVelSums; ++k) sums.at((size_t)me.p * nb * kVelSums + k) = (long long)image[(size_t)k];
+}
+
+// nbe_pair_velocity in an order of its own (with a velocity of A), and with a catalogue B both forms of
+// nbe_halo_velocity_profiles in strides of 256 and of 64
+static void walk_velocity(FILE* f, FILE* o) {
+    const std::vector<int64_t> h = read_n<int64_t>(f, 8);
+    const double L = read_n<double>(f, 1)[0];
+    const int ncell = (int)h[4], nb = (int)h[5], e = (int)h[6];
+    const bool has_va = h[7] != 0, half = h[2] < 0;
+    const std::vector<long long> T = read_n<long long>(f, (size_t)nb + 1);
+    const Catalogue A = load(f, h[0], h[1], L, ncell);
+    const std::vector<VelWord> WA = has_va ? load_words(f, h[0], A, e) : std::vector<VelWord>();
+    const Catalogue Bown = half ? Catalogue() : load(f, h[2], h[3], L, ncell);
+    const std::vector<VelWord> WBown = half ? std::vector<VelWord>() : load_words(f, h[2], Bown, e);
+    const Catalogue& B = half ? A : Bown;
+    const std::vector<VelWord>& WB = half ? WA : WBown;
+
+    const int s = (int)pair_isqrt(T[nb]);
+    const int64_t bad = A.bad + B.bad;
+    std::vector<unsigned long long> pairs((size_t)nb * kVelSums, 0ull);
+    if (!bad && has_va)
+        for (long long i = (long long)A.P.size() - 1; i >= 0; --i)
+            pair_velocity_particle(A.P.data(), WA.data(), i, B.P.data(), WB.data(), B.sk.data(), (long long)B.P.size(), ncell, half,
+                                   T.data(), nb, s, [&](int at, unsigned long long v) { pairs.at((size_t)at) += v; });
+    fwrite(&bad, sizeof bad, 1, o);
+    write_n(o, pairs);
+    if (half) return;
+    const size_t rows = A.P.size() * (size_t)nb * kVelSums;
+    std::vector<long long> group(rows, -1), wave(rows, -1);                     // -1: a word never written
+    const VelWord rest = {0, 0, 0, 0};
+    if (!bad)
+        for (size_t j = 0; j < A.P.size(); ++j) {
+            walk_velocity_centre(A.P[j], has_va ? WA[j] : rest, B, WB, ncell, T, nb, s, 256, group);
+            walk_velocity_centre(A.P[j], has_va ? WA[j] : rest, B, WB, ncell, T, nb, s, 64, wave);
+        }
+    write_n(o, group);
+    write_n(o, wave);
+}
+
 int main(int argc, char** argv) {
     void (*walk)(FILE*, FILE*) = nullptr;
     if (argc == 4) walk = !strcmp(argv[1], "fof") ? walk_fof : !strcmp(argv[1], "pairs") ? walk_pairs :
-                          !strcmp(argv[1], "profiles") ? walk_profiles : nullptr;
-    if (!walk) { fprintf(stderr, "usage: %s fof|pairs|profiles CASE RESULT\n", argv[0]); return 2; }
+                          !strcmp(argv[1], "profiles") ? walk_profiles : !strcmp(argv[1], "velocity") ? walk_velocity : nullptr;
+    if (!walk) { fprintf(stderr, "usage: %s fof|pairs|profiles|velocity CASE RESULT\n", argv[0]); return 2; }
     FILE* f = fopen(argv[2], "rb");
     if (!f) { perror(argv[2]); return 2; }
     FILE* o = fopen(argv[3], "wb");

@@ -1,11 +1,12 @@
 #!/usr/bin/env python
-"""Drive tools/catalog_host_walk.hip: write the small cases of the FoF, pair-count and profile tests, run the host program
-(built under -fsanitize=address,undefined, see its head) on each and compare what the bodies of csrc/nbe_catalog.h produced
-with tests/fof_ref.py, tests/pairs_ref.py and tests/profiles_ref.py.  A CPU machine only: nothing here touches a device.
+"""Drive tools/catalog_host_walk.hip: write the small cases of the FoF, pair-count, profile and velocity-moment tests, run the
+host program (built under -fsanitize=address,undefined, see its head) on each and compare what the bodies of
+csrc/nbe_catalog.h produced with tests/fof_ref.py, tests/pairs_ref.py, tests/profiles_ref.py and tests/pairvel_ref.py.  A CPU
+machine only: nothing here touches a device.
 
-    python tools/catalog_host_walk.py ./catalog_host_walk [fof|pairs|profiles ...]
+    python tools/catalog_host_walk.py ./catalog_host_walk [fof|pairs|profiles|velocity ...]
 
-tests/test_catalog_host_walk.py runs the same cases on a build without the sanitizers.
+tests/test_catalog_host_walk.py and tests/test_pairvel_host_walk.py run the same cases on a build without the sanitizers.
 """
 
 import os
@@ -21,6 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import fof_ref as F  # noqa: E402
 import pairs_ref as R  # noqa: E402
 import profiles_ref as PR  # noqa: E402
+import pairvel_ref as V  # noqa: E402
 
 
 def fof_cases():
@@ -180,7 +182,56 @@ def walk_profiles(prog, tmp, a, b, L, edges):
     return "%9d counted, ncell %4d: both forms equal to the reference" % (int(ref.sum()), R.ncell_of(T))
 
 
-MODES = {"fof": (fof_cases, walk_fof), "pairs": (pairs_cases, walk_pairs), "profiles": (profiles_cases, walk_profiles)}
+def velocity_cases():
+    """(name, a, va or None, b or None, vb, L, edges): tests/pairvel_ref.py's list"""
+    return V.cases()
+
+
+def write_velocity(f, v, x):
+    """The velocity v of the catalogue x in the layout and dtype of x's kind."""
+    x = np.asarray(x)
+    w = np.ascontiguousarray(v, x.dtype if x.ndim == 4 or x.dtype == np.float64 else np.float32)
+    assert np.array_equal(w.astype(np.float64), np.asarray(v).astype(np.float64)), "the case file's dtype would round the velocity"
+    w.tofile(f)
+
+
+def walk_velocity(prog, tmp, a, va, b, vb, L, edges):
+    T = R.thresholds(edges, L)
+    nb = len(T) - 1
+    e = V.exponent(va, vb)
+    pairs = None if va is None else V.moments_of(a, va, L, edges, b, vb)[0]
+    tables = None if b is None or np.asarray(a).ndim == 4 else V.profiles_of(a, va, b, vb, L, edges)[0]
+
+    def body(f):
+        np.array([L], np.float64).tofile(f)
+        np.array(T, np.int64).tofile(f)
+        ka = write_catalogue(f, a)
+        if va is not None:
+            write_velocity(f, va, a)
+        kb = write_catalogue(f, b)
+        if b is not None:
+            write_velocity(f, vb, b)
+        return [*ka, *kb, R.ncell_of(T), nb, e, va is not None]
+
+    with run(prog, "velocity", tmp, 8, body) as f:
+        bad = np.fromfile(f, np.int64, 1)[0]
+        got = np.fromfile(f, np.int64, 6 * nb).reshape(nb, 6)
+        rest = np.fromfile(f, np.int64)
+    assert bad == 0
+    if pairs is not None:
+        assert np.array_equal(got, pairs), "pair moments"
+    if tables is not None:
+        both = rest.reshape((2,) + tables.shape)
+        assert np.array_equal(both[0], tables), "workgroup form"
+        assert np.array_equal(both[1], tables), "wave form"
+    else:
+        assert rest.size == 0 or np.asarray(a).ndim == 4
+    n = int((pairs if pairs is not None else tables.sum(axis=0))[:, 0].sum())
+    return "%9d pairs, ncell %4d, e %3d: equal to the reference" % (n, R.ncell_of(T), e)
+
+
+MODES = {"fof": (fof_cases, walk_fof), "pairs": (pairs_cases, walk_pairs), "profiles": (profiles_cases, walk_profiles),
+         "velocity": (velocity_cases, walk_velocity)}
 
 
 def walk_mode(prog, mode, report=None):
