@@ -251,7 +251,9 @@ double nbe_vel_norm(double z, double Om);
  * receives the masses in units of 2^-22 particles, bitwise independent of scheduling; every particle adds exactly 2^22.
  * stats = 4 int32 (zeroed by the caller): [0] tiles of 8^3 particles whose footprint took the direct (global-atomic) path,
  * [1] particles with a non-finite or out-of-range position, which are NOT painted, [2:4] one int64: with count_atomics != 0
- * (measurement only: one more same-address atomic per tile) the number of 64-bit atomic adds into the mesh. */
+ * (measurement only: one more same-address atomic per tile) the number of 64-bit atomic adds into the mesh.  A footprint
+ * of any accepted size (positions up to 2^30 mesh cells apart on either side) that does not fit the LDS image takes the
+ * direct path, here and in the two painters below. */
 int nbe_paint_mesh(const void* disp, int disp_dtype, const int64_t n[3], const double boxsize[3], const int64_t res[3],
                    int worder, int count_atomics, void* mesh, void* stats, void* stream);
 /* mesh (int64, as above) -> delta = rho / rho_mean - 1 (float32), rho_mean = nparticles / (res0 res1 res2) */

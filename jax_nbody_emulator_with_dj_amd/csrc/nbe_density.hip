@@ -110,6 +110,12 @@ __device__ inline void particle_weights(const double* u, int* j0, F fn) {
         }
 }
 
+// true for a footprint of e0 x e1 x e2 nodes that does not fit an image of `cells` cells: the one place the painters
+// decide the path.  (Each extent is tested first: the product of three extents of up to 2^31 cells does not fit 64 bits.)
+__device__ inline bool beyond_image(long long e0, long long e1, long long e2, int cells) {
+    return e0 > cells || e1 > cells || e2 > cells || e0 * e1 * e2 > cells;
+}
+
 // measurement builds of a call (count_atomics != 0): the workgroup's global atomic adds into stats[2:4]
 __device__ inline void count_atomics(const PaintArgs& A, unsigned na, unsigned* shared) {
     atomicAdd(shared, na);
@@ -176,7 +182,7 @@ __global__ __launch_bounds__(kPaintThreads) void paint_kernel(PaintArgs A) {
     const long long e0 = (long long)hi[0] - lo[0] + 1, e1 = (long long)hi[1] - lo[1] + 1,
                     e2 = (long long)hi[2] - lo[2] + 1;
     const int r0 = A.r0, r1 = A.r1, r2 = A.r2;
-    if (e0 * e1 * e2 > kLdsCells) {
+    if (beyond_image(e0, e1, e2, kLdsCells)) {
         // footprint larger than the image: the same integer weights straight into the mesh
         if (tid == 0) atomicAdd(&A.stats[0], 1);
         unsigned na = 0;
@@ -269,11 +275,6 @@ struct FieldMeshes {
     long long cells;
     int r0, r1, r2, nchan;
 };
-
-// (each extent is tested first: the product of three extents of up to 2^31 cells does not fit 64 bits)
-__device__ inline bool beyond_image(long long e0, long long e1, long long e2) {
-    return e0 > kFieldCells || e1 > kFieldCells || e2 > kFieldCells || e0 * e1 * e2 > kFieldCells;
-}
 
 // a thread's node bounds mn, mx (INT_MAX: no live particle) into the workgroup's lo, hi; false if nothing is live (uniform)
 __device__ inline bool merge_footprint(const int* mn, const int* mx, int* lo, int* hi) {
@@ -402,7 +403,8 @@ __global__ __launch_bounds__(kPaintThreads) void paint_field_kernel(FieldArgs A)
     if (!merge_footprint(mn, mx, lo, hi)) return;          // no live particle in this tile
 
     const FieldMeshes M = {A.mesh, A.qmesh, (long long)A.r0 * A.r1 * A.r2, A.r0, A.r1, A.r2, nchan};
-    if (beyond_image((long long)hi[0] - lo[0] + 1, (long long)hi[1] - lo[1] + 1, (long long)hi[2] - lo[2] + 1)) {
+    if (beyond_image((long long)hi[0] - lo[0] + 1, (long long)hi[1] - lo[1] + 1, (long long)hi[2] - lo[2] + 1,
+                     kFieldCells)) {
         if (tid == 0) atomicAdd(&A.stats[0], 1);
         if (live[0]) direct_add<P>(M, u[0], V[0]);
         if (live[1]) direct_add<P>(M, u[1], V[1]);
@@ -500,7 +502,8 @@ __global__ __launch_bounds__(kPaintThreads) void paint_particles_kernel(Particle
     if (!merge_footprint(mn, mx, lo, hi)) return;          // no live particle in this chunk
 
     const FieldMeshes M = {A.mesh, A.qmesh, (long long)A.r0 * A.r1 * A.r2, A.r0, A.r1, A.r2, nchan};
-    if (beyond_image((long long)hi[0] - lo[0] + 1, (long long)hi[1] - lo[1] + 1, (long long)hi[2] - lo[2] + 1)) {
+    if (beyond_image((long long)hi[0] - lo[0] + 1, (long long)hi[1] - lo[1] + 1, (long long)hi[2] - lo[2] + 1,
+                     kFieldCells)) {
         if (tid == 0) atomicAdd(&A.stats[0], 1);
         if (live[0]) direct_add<P>(M, u[0], V[0]);
         if (live[1]) direct_add<P>(M, u[1], V[1]);
