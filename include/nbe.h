@@ -306,6 +306,21 @@ int nbe_paint_particles(const void* pos, int pos_dtype, const void* order, const
 int nbe_particle_keys(const void* pos, int pos_dtype, const void* shift, int shift_dtype, int shift_axis,
                       double shift_scale, int64_t count, const double boxsize[3], const int64_t res[3], int tile_edge,
                       int morton, void* keys, void* stream);
+/* Mesh readout, the adjoint of the three painters above, which the reference does not have:
+ * stands in for nbodykit's mesh.readout(position, resampler) and Pylians' MASL.CIC_interp.  field = (nchan, res0, res1,
+ * res2) float32, 1 <= nchan <= NBE_PAINT_MAX_CHANNELS; out = (nchan, count) float32.  The rows are either a catalogue, pos =
+ * (count, 3) float32 / float64 with an optional order, both as in nbe_paint_particles (disp and n are not read), or, with
+ * pos = NULL, the lattice n of nbe_paint_fields displaced by disp = (3, N0, N1, N2) float32 / float16 or bare (disp = NULL),
+ * count = N0 N1 N2, order = NULL.  With q_abc the fixed-point weights that the painters add for the row (integers that sum
+ * to exactly 2^22), out_c = (float)(2^-22 sum of q_abc f_c[node]), summed in float64 in the (a, b, c) order of the weights;
+ * q f is exact in float64, so the sum does not depend on fusing.  A row that the painters would not paint (a non-finite
+ * position or one beyond 2^30 mesh cells) gets `fill` in every channel and is counted in stats[1]; an entry of order outside
+ * 0 .. count-1 names no row: it is counted there too and nothing is written for it.  stats = 4 int32, zeroed by the caller.
+ * No atomics on out, one writer per word: the same bits for every order and stream.  out_c(p) = sum over nodes of
+ * W(p, node) f_c[node] is the transpose of nbe_paint_particles' mesh = sum over p of W(p, node), with the same integers. */
+int nbe_mesh_read(const void* field, int nchan, const int64_t res[3], const void* disp, int disp_dtype, const int64_t n[3],
+                  const void* pos, int pos_dtype, const void* order, int64_t count, const double boxsize[3], int worder,
+                  double fill, void* out, void* stats, void* stream);
 /* second half of project_field_from_particles (normalize_by_density): the meshes of nbe_paint_fields -> field = (nchan,
  * res) float32, in float64 with one rounding.  NBE_FIELD_MEAN: S 2^(e_c - 46) n_cells / nparticles.  NBE_FIELD_DENSITY:
  * S 2^(e_c - 24) / M, and `fill` where M = 0.  stats[2] += the cells with M >= 2^39, whose S may have wrapped. */
@@ -621,6 +636,38 @@ int nbe_block_average(const void* src, int64_t n_in, void* dst, int64_t n_out, v
 /* replaces the "linear" method of upsample_density_with_discodj (scripts/utils.py:186-234): dst (n_out^3 float32) =
  * periodic trilinear interpolation of src (n_in^3 float32) at the nodes i n_in / n_out; n_in divides n_out */
 int nbe_trilinear_upsample(const void* src, int64_t n_in, void* dst, int64_t n_out, void* stream);
+
+/* ---- Cosmic web (no context) -----------------------------------------------------------------------------
+ * Where in the cosmic web a voxel sits, which the reference's pipeline does not ask: the T-web of
+ * Hahn et al. (2007, MNRAS 375, 489) with the free threshold of Forero-Romero et al. (2009, MNRAS 396, 1815) from the tidal
+ * tensor phi,ij (nabla^2 phi = delta: nbe_lpt2_hessian_spectrum of the smoothed delta_k), and the V-web of Hoffman et al.
+ * (2012, MNRAS 425, 2049) from the velocity shear.  Pointers, `stream`, asynchrony and spectra as for "Input fields";
+ * max_blocks as for nbe_lpt2_source (the same bits for every grid).
+ *
+ * nbe_shear_spectrum: spectra = (3, n, n, n/2+1) of a vector mesh v.  Component p of nbe_lpt2_hessian_spectrum's pair list
+ * receives Sigma_ij = -scale (d_i v_j + d_j v_i) / 2 with nbe_divergence_spectrum's derivative i (2 pi / L) d_c, d_c = m_c or
+ * 0 on the Nyquist row of an even n; Hoffman et al. have scale = 1 / H0.  Each word is f times the float64 bracket
+ * (d_i v_j + d_j v_i) / 2 (exact products, one rounding) with f = -scale 2 pi / L, rounded to float32 once.  The real-space
+ * trace is -scale div v.  out = (count, n, n, n/2+1) receives components first .. first + count - 1 as in
+ * nbe_lpt2_hessian_spectrum: pieces give the bits of the whole.  out must not overlap spectra.
+ *
+ * nbe_tensor_eigenvalues: tensor = (6, n, n, n) float32 in the pair order, eig = (3, n, n, n) float32 receives
+ * lambda_1 >= lambda_2 >= lambda_3 per voxel: computed in float64 from the six float32 words, sorted, rounded once
+ * (csrc/nbe_web.h has the method and its error, far below one float32 rounding of |A|_F).  Where the three off-diagonal
+ * words are exactly 0 the result is the sorted diagonal, bit for bit.  A voxel with a non-finite word gives three NaNs.  A
+ * grid-stride pass with nbe_lpt2_source's access rule.  eig must not overlap tensor.
+ *
+ * nbe_web_classify: eig = (3, n, n, n) float32; thresholds = nthresholds finite float32 ON THE HOST, 1 <= nthresholds <=
+ * NBE_WEB_MAX_THRESHOLDS (a scan of lambda_th costs one read of eig); counts = (nthresholds, 5) int64, ZEROED by the caller:
+ * counts[t][m] += the voxels with exactly m eigenvalues > thresholds[t] in float32 comparison (0 void, 1 sheet, 2 filament,
+ * 3 knot), counts[t][4] += the voxels with a NaN eigenvalue, which have no type.  types = (n, n, n) uint8 or NULL: m under
+ * thresholds[which], 255 for a NaN voxel.  Sums of ones, reduced per workgroup before the 64-bit atomic. */
+#define NBE_WEB_MAX_THRESHOLDS 64
+int nbe_shear_spectrum(const void* spectra, int64_t n, double boxsize, double scale, int first, int count, void* out,
+                       int max_blocks, void* stream);
+int nbe_tensor_eigenvalues(const void* tensor, int64_t n, void* eig, int max_blocks, void* stream);
+int nbe_web_classify(const void* eig, int64_t n, const float* thresholds, int nthresholds, int which, void* types,
+                     void* counts, int max_blocks, void* stream);
 
 /* ---- Pairwise velocities (no context) ------------------------------------------------------------------
  * Velocity moments per bin of separation: the mean pairwise (streaming) velocity v12(r) and the

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NBE_LIB") or os.path.join(_HERE, "libnbe.so")   # NBE_LIB: timing-probe builds only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ("nbe_kernels.hip", "nbe_kernels_h3.hip", "nbe_density.hip", "nbe_lpt.hip", "nbe_fof.hip", "nbe_pairs.hip",
-           "nbe_profiles.hip", "nbe_pairvel.hip", "nbe_engine.cpp", "nbe_engine_net.cpp", "nbe_engine_weights.cpp", "nbe_engine_box.cpp", "nbe_engine_brick.cpp",
+           "nbe_profiles.hip", "nbe_pairvel.hip", "nbe_web.hip", "nbe_engine.cpp", "nbe_engine_net.cpp", "nbe_engine_weights.cpp", "nbe_engine_box.cpp", "nbe_engine_brick.cpp",
            "nbe_engine_probe.cpp", "nbe_engine_test.cpp")
 
 
@@ -89,6 +89,9 @@ SIGNATURES = {
                                       C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nbe_particle_keys": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int64,
                                     C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nbe_mesh_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_int, C.POINTER(C.c_int64),
+                                C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_double,
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "nbe_mesh_to_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.c_int64,
                                     C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nbe_deconvolve_mas": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
@@ -142,6 +145,11 @@ SIGNATURES = {
     "nbe_divergence_spectrum": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
     "nbe_lpt2_hessian_spectrum": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "nbe_lpt2_source": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
+    "nbe_shear_spectrum": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                     C.c_void_p]),
+    "nbe_tensor_eigenvalues": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
+    "nbe_web_classify": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_void_p]),
     "nbe_lpt2_spectrum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                     C.c_int, C.c_void_p]),
     "nbe_spectrum_resize": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),

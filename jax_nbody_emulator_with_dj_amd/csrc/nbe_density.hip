@@ -542,6 +542,78 @@ __global__ __launch_bounds__(256) void particle_keys_kernel(PositionArgs A, int 
     }
 }
 
+// ---- Mesh readout --------------------------------------------------------------------------
+// The adjoint of the painters: out_c(p) = 2^-22 sum of q f_c[node] over the fixed-point weights q that the painters add for
+// particle p (particle_weights, which sum to exactly 2^22), in float64 in that function's (a, b, c) order and rounded to
+// float32 once.  q <= 2^22 times a float32 is exact in float64, so fusing the product into the add changes nothing.  A
+// thread takes a row and reads its P^3 nodes, wrapped as the painters wrap them, for every channel; no atomics on the
+// output, one writer per word: the same bits for every grid and order.  Rows are those of the painters: entry e of `order`
+// (or e itself) of a catalogue through particle_position, or particle e of the lattice through paint_field_kernel's
+// expression.  (A template like particle_keys_kernel, so that it is emitted after the painters.)
+struct ReadArgs {
+    PositionArgs pos;           // a catalogue (pos.pos != NULL), or
+    const void* disp;           // the lattice n0 x n1 x n2 displaced by (3, N0, N1, N2), or bare (NULL)
+    int disp_half;
+    long long n0, n1, n2;
+    double a0, a1, a2;          // mesh cells per lattice step
+    const long long* order;     // catalogue only: (count,) or NULL
+    const float* field;         // (nchan, r0, r1, r2)
+    float* out;                 // (nchan, count)
+    int nchan, r0, r1, r2;
+    float fill;
+    int* stats;                 // [1] rows that are not read
+};
+
+template <int P>
+__global__ __launch_bounds__(256) void mesh_read_kernel(ReadArgs A) {
+    const long long count = A.pos.count, cells = (long long)A.r0 * A.r1 * A.r2;
+    const int r0 = A.r0, r1 = A.r1, r2 = A.r2, nchan = A.nchan;
+    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < count; e += (long long)gridDim.x * blockDim.x) {
+        double u[3];
+        long long idx = e;
+        bool live;
+        if (A.pos.pos) {
+            if (A.order) idx = A.order[e];
+            if (idx < 0 || idx >= count) {                 // nothing to read and no row to write
+                atomicAdd(&A.stats[1], 1);
+                continue;
+            }
+            live = particle_position(A.pos, idx, u);
+        } else {
+            const long long i2 = e % A.n2, rest = e / A.n2, i1 = rest % A.n1, i0 = rest / A.n1;
+            float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f;
+            if (A.disp) {
+                p0 = load_real(A.disp, A.disp_half, idx);
+                p1 = load_real(A.disp, A.disp_half, count + idx);
+                p2 = load_real(A.disp, A.disp_half, 2 * count + idx);
+            }
+            u[0] = (double)i0 * A.a0 + (double)p0 * A.pos.s0;
+            u[1] = (double)i1 * A.a1 + (double)p1 * A.pos.s1;
+            u[2] = (double)i2 * A.a2 + (double)p2 * A.pos.s2;
+            live = fabs(u[0]) < kUMax && fabs(u[1]) < kUMax && fabs(u[2]) < kUMax;
+        }
+        if (!live) {
+            atomicAdd(&A.stats[1], 1);
+#pragma unroll
+            for (int c = 0; c < NBE_PAINT_MAX_CHANNELS; ++c)
+                if (c < nchan) A.out[c * count + idx] = A.fill;
+            continue;
+        }
+        double acc[NBE_PAINT_MAX_CHANNELS] = {0.0, 0.0, 0.0, 0.0};
+        int j0[3];
+        particle_weights<P>(u, j0, [&](int a, int b, int c, unsigned q) {
+            const long long g = ((long long)wrap(j0[0] + a, r0) * r1 + wrap(j0[1] + b, r1)) * r2 + wrap(j0[2] + c, r2);
+            const double w = (double)q;
+#pragma unroll
+            for (int ch = 0; ch < NBE_PAINT_MAX_CHANNELS; ++ch)
+                if (ch < nchan) acc[ch] += w * (double)A.field[ch * cells + g];
+        });
+#pragma unroll
+        for (int c = 0; c < NBE_PAINT_MAX_CHANNELS; ++c)
+            if (c < nchan) A.out[c * count + idx] = (float)(acc[c] * (1.0 / kUnit));
+    }
+}
+
 // per channel: the largest |q| as float bits (unsigned order = float order for non-negative floats; atomicMax commutes)
 // in range[c], and the number of non-finite values of all channels in range[nchan]
 __global__ __launch_bounds__(256) void quantity_range_kernel(const void* q, int half, int nchan, long long count,
@@ -1459,6 +1531,53 @@ int nbe_particle_keys(const void* pos, int pos_dtype, const void* shift, int shi
     if (morton) hipLaunchKernelGGL(particle_keys_kernel<true>, grid, block, 0, s, P, r0, r1, r2, tile_edge, (long long*)keys);
     else hipLaunchKernelGGL(particle_keys_kernel<false>, grid, block, 0, s, P, r0, r1, r2, tile_edge, (long long*)keys);
     return launched("nbe_particle_keys");
+}
+
+int nbe_mesh_read(const void* field, int nchan, const int64_t res[3], const void* disp, int disp_dtype, const int64_t n[3],
+                  const void* pos, int pos_dtype, const void* order, int64_t count, const double boxsize[3], int worder,
+                  double fill, void* out, void* stats, void* stream) {
+    if (!field || !out || !stats || !res || !boxsize) return fail("nbe_mesh_read: NULL argument");
+    if (nchan < 1 || nchan > NBE_PAINT_MAX_CHANNELS)
+        return fail("nbe_mesh_read: %d channels unsupported (1 .. %d)", nchan, NBE_PAINT_MAX_CHANNELS);
+    if (worder < 1 || worder > 4) return fail("nbe_mesh_read: worder %d not in 1..4", worder);
+    ReadArgs A;
+    if (pos) {
+        if (disp) return fail("nbe_mesh_read: positions together with a displacement");
+        if (!position_args("nbe_mesh_read", A.pos, pos, pos_dtype, nullptr, NBE_F32, 0, 0.0, count, boxsize, res)) return 1;
+        A.n0 = A.n1 = A.n2 = 0;
+        A.a0 = A.a1 = A.a2 = 0.0;
+    } else {
+        if (!n || order) return fail("nbe_mesh_read: the lattice form needs n and takes no order");
+        if (disp && disp_dtype != NBE_F32 && disp_dtype != NBE_F16) return fail("nbe_mesh_read: dtype %d unsupported", disp_dtype);
+        for (int c = 0; c < 3; ++c) {
+            if (n[c] < 1 || n[c] > INT_MAX || res[c] < 1 || res[c] > (1 << 20) || !(boxsize[c] > 0.0) || !std::isfinite(boxsize[c]))
+                return fail("nbe_mesh_read: bad geometry on axis %d (n %lld, res %lld, boxsize %g)", c, (long long)n[c],
+                            (long long)res[c], boxsize[c]);
+        }
+        if ((double)n[0] * (double)n[1] * (double)n[2] > (double)INT_MAX || count != n[0] * n[1] * n[2])
+            return fail("nbe_mesh_read: count %lld is not the lattice %lld x %lld x %lld (up to 2^31 - 1 rows)",
+                        (long long)count, (long long)n[0], (long long)n[1], (long long)n[2]);
+        A.pos.pos = nullptr; A.pos.shift = nullptr;
+        A.pos.pos_f64 = A.pos.shift_half = A.pos.los = 0;
+        A.pos.vs = 0.0;
+        A.pos.s0 = res[0] / boxsize[0]; A.pos.s1 = res[1] / boxsize[1]; A.pos.s2 = res[2] / boxsize[2];
+        A.pos.count = count;
+        A.n0 = n[0]; A.n1 = n[1]; A.n2 = n[2];
+        A.a0 = (double)res[0] / n[0]; A.a1 = (double)res[1] / n[1]; A.a2 = (double)res[2] / n[2];
+    }
+    A.disp = pos ? nullptr : disp;
+    A.disp_half = disp_dtype == NBE_F16;
+    A.order = (const long long*)order;
+    A.field = (const float*)field;
+    A.out = (float*)out;
+    A.nchan = nchan;
+    A.r0 = (int)res[0]; A.r1 = (int)res[1]; A.r2 = (int)res[2];
+    A.fill = (float)fill;
+    A.stats = (int*)stats;
+    const dim3 grid(grid_for(count, 256)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    with_worder(worder, [&](auto P) { hipLaunchKernelGGL(mesh_read_kernel<decltype(P)::value>, grid, block, 0, s, A); });
+    return launched("nbe_mesh_read");
 }
 
 int nbe_mesh_to_field(const void* mesh, const void* qmesh, int nchan, const int exponents[], const int64_t res[3],

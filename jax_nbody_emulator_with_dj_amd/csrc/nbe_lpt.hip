@@ -497,6 +497,38 @@ __global__ __launch_bounds__(kLanes * kRows) void trilinear_kernel(const float* 
     }
 }
 
+// ---- velocity shear -------------------------------------------------------------------------------
+
+// Sigma_ij = -scale (d_i v_j + d_j v_i) / 2 of a vector mesh (the V-web's tensor, Hoffman et al. 2012, where scale = 1 / H0),
+// in lpt2_hessian_kernel's pair order and pieces and with divergence_kernel's derivative i kf d_c, d_c = 0 on the Nyquist
+// row of an even n: out = i f (d_i v_j + d_j v_i) / 2 with f = -scale kf.  The products of an integer below 2^11 and a
+// float32 are exact in float64, so the bracket is rounded once, halving is exact, and a diagonal component is d_i v_i.
+// (After every other kernel of this file, so that none of them moves in the code object.)
+__global__ __launch_bounds__(kLanes * kRows) void shear_kernel(const float2* __restrict__ v, float2* __restrict__ out,
+                                                               long long n, double f, int first, int count) {
+    const long long h = n / 2 + 1, rows = n * n, plane = rows * h;
+    const long long nyq = n % 2 == 0 ? n / 2 : -1;
+    NBE_FOR_ROWS(r, rows) {
+        const long long i0 = r / n, i1 = r - i0 * n;
+        const double d0 = i0 == nyq ? 0.0 : (double)freq(i0, n), d1 = i1 == nyq ? 0.0 : (double)freq(i1, n);
+        const float2* src = v + r * h;
+        float2* dst = out + r * h;
+        for (long long i2 = threadIdx.x; i2 < h; i2 += kLanes) {
+            const double d2 = i2 == nyq ? 0.0 : (double)i2;
+            const float2 v0 = src[i2], v1 = src[plane + i2], v2 = src[2 * plane + i2];
+            const double re[kPairs] = {d0 * v0.x, d1 * v1.x, d2 * v2.x, 0.5 * (d0 * v1.x + d1 * v0.x),
+                                       0.5 * (d0 * v2.x + d2 * v0.x), 0.5 * (d1 * v2.x + d2 * v1.x)};
+            const double im[kPairs] = {d0 * v0.y, d1 * v1.y, d2 * v2.y, 0.5 * (d0 * v1.y + d1 * v0.y),
+                                       0.5 * (d0 * v2.y + d2 * v0.y), 0.5 * (d1 * v2.y + d2 * v1.y)};
+#pragma unroll
+            for (int p = 0; p < kPairs; ++p) {
+                if (p < first || p >= first + count) continue;
+                dst[(p - first) * plane + i2] = make_float2((float)(-f * im[p]), (float)(f * re[p]));
+            }
+        }
+    }
+}
+
 bool size_ok(int64_t n) { return n >= NBE_LPT_MIN_N && n <= NBE_LPT_MAX_N; }
 
 dim3 row_grid(long long n) { return dim3((unsigned)grid_for(n * n, kRows)); }
@@ -552,6 +584,21 @@ int nbe_lpt2_hessian_spectrum(const void* spectrum, int64_t n, int first, int co
     hipLaunchKernelGGL(lpt2_hessian_kernel, capped(row_grid(n), max_blocks), kBlock, 0, (hipStream_t)stream,
                        (const float2*)spectrum, (float2*)out, (long long)n, first, count);
     return launched("nbe_lpt2_hessian_spectrum");
+}
+
+int nbe_shear_spectrum(const void* spectra, int64_t n, double boxsize, double scale, int first, int count, void* out,
+                       int max_blocks, void* stream) {
+    if (!spectra || !out) return fail("nbe_shear_spectrum: NULL argument");
+    if (!size_ok(n)) return fail("nbe_shear_spectrum: n %lld not in %d .. %d", (long long)n, NBE_LPT_MIN_N, NBE_LPT_MAX_N);
+    if (!(boxsize > 0.0) || !std::isfinite(boxsize) || !std::isfinite(scale))
+        return fail("nbe_shear_spectrum: bad boxsize %g or scale %g", boxsize, scale);
+    if (first < 0 || count < 1 || first > kPairs - count)
+        return fail("nbe_shear_spectrum: components %d .. %d not in 0 .. %d", first, first + count - 1, kPairs - 1);
+    const long long words = 8 * n * n * (n / 2 + 1);
+    if (overlap(spectra, 3 * words, out, count * words)) return fail("nbe_shear_spectrum: out aliases spectra");
+    hipLaunchKernelGGL(shear_kernel, capped(row_grid(n), max_blocks), kBlock, 0, (hipStream_t)stream,
+                       (const float2*)spectra, (float2*)out, (long long)n, -scale * (2.0 * kPi / boxsize), first, count);
+    return launched("nbe_shear_spectrum");
 }
 
 int nbe_lpt2_source(const void* hess, int64_t n, void* out, int max_blocks, void* stream) {

@@ -72,7 +72,7 @@ except Exception:  # pragma: no cover
 
 __all__ = ["paint_density", "deconvolve_mas", "power_spectrum", "minkowski_functionals", "bispectrum",
            "field_statistics", "field_pdf", "paint_field", "rsd_factor", "power_spectrum_multipoles",
-           "power_spectrum_wedges", "paint_particles", "cross_correlation", "shot_noise"]
+           "power_spectrum_wedges", "paint_particles", "cross_correlation", "shot_noise", "read_mesh"]
 
 WORDERS = {1: "NGP", 2: "CIC", 3: "TSC", 4: "PCS"}
 _UNIT = 2.0 ** 22           # fixed-point units per particle mass (include/nbe.h, nbe_paint_mesh)
@@ -663,6 +663,125 @@ def paint_particles(positions, boxsize=1000.0, res=512, worder=2, deconvolve=Tru
     if single:
         field = field[0]
     return (_back(x, field), _back(x, delta)) if return_delta else _back(x, field)
+
+
+# ---- mesh readout ----------------------------------------------------------------------------
+
+def _validate_read(field, boxsize, positions, displacement, lattice, worder, fill, sort):
+    f = _check_array(field, "field")
+    if f.ndim not in (3, 4) or min(f.shape) < 1 or (f.ndim == 4 and f.shape[0] > _MAX_CHANNELS):
+        raise ValueError("field must have shape (r0, r1, r2) or (C, r0, r1, r2) with 1 <= C <= %d, got %s"
+                         % (_MAX_CHANNELS, tuple(f.shape)))
+    if _dtype_name(f) != "float32":
+        raise ValueError("field must be float32, got %s" % _dtype_name(f))
+    res = tuple(int(v) for v in f.shape[-3:])
+    if max(res) > 1 << 20:
+        raise ValueError("read_mesh: mesh %s unsupported (up to 2^20 cells a side)" % (res,))
+    boxsize, worder = _triple(boxsize, "boxsize", "a length"), _check_worder(worder)
+    if isinstance(fill, (bool, np.bool_)) or not isinstance(fill, numbers.Real):
+        raise ValueError("fill must be a number (nan included), got %r" % (fill,))
+    sort = _check_sort(sort)
+    if sum(a is not None for a in (positions, displacement, lattice)) != 1:
+        raise ValueError("read_mesh needs exactly one of positions, displacement and lattice")
+    x = n = None
+    if positions is not None:
+        x = _check_array(positions, "positions")
+        if x.ndim != 2 or x.shape[1] != 3:
+            raise ValueError("positions must have shape (count, 3), got %s" % (tuple(x.shape),))
+        if _dtype_name(x) not in ("float32", "float64"):
+            raise ValueError("positions must be float32 or float64, got %s" % _dtype_name(x))
+        if not 1 <= int(x.shape[0]) <= _MAX_PARTICLES:
+            raise ValueError("read_mesh: %d rows unsupported (1 .. 2^31 - 1)" % int(x.shape[0]))
+    elif displacement is not None:
+        x = _check_array(displacement, "displacement")
+        if x.ndim != 4 or x.shape[0] != 3 or min(x.shape) < 1:
+            raise ValueError("displacement must have shape (3, N0, N1, N2), got %s" % (tuple(x.shape),))
+        if _dtype_name(x) not in ("float32", "float16"):
+            raise ValueError("displacement must be float32 or float16, got %s" % _dtype_name(x))
+        n = tuple(int(v) for v in x.shape[1:])
+    else:
+        n = _triple(lattice, "lattice", "an int")
+    if n is not None and n[0] * n[1] * n[2] > _MAX_PARTICLES:
+        raise ValueError("read_mesh: a lattice of %s exceeds one call (2^31 - 1 rows)" % (n,))
+    if x is not None:
+        _same_kind(f, x, "field", "positions" if positions is not None else "displacement")
+    return f, res, boxsize, worder, float(fill), sort, x, n
+
+
+def _read_mesh(f, res, boxsize, worder, fill, p=None, x=None, n=None, sort=False):
+    """Device work of read_mesh.  f: contiguous CUDA (C,) + res float32 tensor; p: contiguous (count, 3) float32 / float64
+    positions, or None: the lattice n, displaced by the contiguous (3,) + n float32 / float16 tensor x or bare.  Returns
+    (out (C, count) float32, stats): stats[1] rows that got `fill`."""
+    l = _lib.lib()
+    dev = f.device
+    nchan = int(f.shape[0])
+    count = int(p.shape[0]) if p is not None else n[0] * n[1] * n[2]
+    cells = res[0] * res[1] * res[2]
+    if sort == "auto":
+        # paint_particles sorts from 2^18 rows on because an LDS image saves it global atomics; the readout has none to save,
+        # and on a fully shuffled catalogue of 512^3 rows keys + torch.sort cost more than the locality returns (19.7 ms
+        # sorted against 16.7 ms unsorted, profiles/web_timing_512.txt): "auto" reads in the order given
+        sort = False
+    with torch.cuda.device(dev):
+        s = _stream(dev)
+        L3, r3 = (C.c_double * 3)(*boxsize), _i64(res)
+        order = None
+        pdt = 0
+        if p is not None:
+            pdt = 2 if p.dtype == torch.float64 else 0
+            if sort:
+                keys = torch.empty(count, dtype=torch.int64, device=dev)
+                edge = _KEY_EDGES[cells >= _KEY_SPARSE * count]
+                _lib.check(l.nbe_particle_keys(_ptr(p), pdt, None, 0, 0, 0.0, count, L3, r3, int(edge), int(_KEY_MORTON),
+                                               _ptr(keys), s))
+                order = torch.sort(keys)[1]
+                del keys
+        out = torch.empty((nchan, count), dtype=torch.float32, device=dev)
+        stats = torch.zeros(4, dtype=torch.int32, device=dev)
+        _lib.check(l.nbe_mesh_read(_ptr(f), nchan, r3, _ptr_or_null(x), 1 if x is not None and x.dtype == torch.float16 else 0,
+                                   _i64(n) if n is not None else None, _ptr_or_null(p), pdt, _ptr_or_null(order), count, L3,
+                                   worder, fill, _ptr(out), _ptr(stats), s))
+    return out, stats
+
+
+def read_mesh(field, boxsize=1000.0, positions=None, displacement=None, worder=2, fill=float("nan"), sort="auto",
+              lattice=None, return_stats=False):
+    """The value of a mesh at particles: the adjoint of the painters (nbodykit's mesh.readout(position, resampler),
+    Pylians' MASL.CIC_interp; the reference has no such step).  What a halo's environment, a reconstruction or a velocity
+    at a particle is read with.
+
+    field: (r0, r1, r2) or (C, r0, r1, r2) float32, C <= 4, NumPy array or CUDA tensor; a periodic mesh over boxsize.
+    Exactly one of: positions, (count, 3) float32 / float64 as paint_particles takes them (any number of boxes away);
+    displacement, (3, N0, N1, N2) float32 / float16, the displaced lattice of paint_density; lattice, an int or a 3-tuple,
+    the bare lattice.  worder: the window, as the painters'.  Returns float32 of the field's kind: (count,) or (C, count)
+    for positions, (N0, N1, N2) or (C, N0, N1, N2) for the lattice forms.  With return_stats also {"not_read": rows}.
+
+    out_c = 2^-22 sum of q f_c[node] over the integer weights q that the painter of the same worder adds for the row (they
+    sum to exactly 2^22), summed in float64 in the weights' order and rounded once: a constant field reads back as itself,
+    and sum(mesh * g) == sum(read(g) * 2^22) holds exactly for paint_particles' integer mesh and an integer-valued g.  A
+    row the painters would reject (non-finite, or beyond 2^30 mesh cells) gets `fill` in every channel.  sort: True reads
+    the rows in the order of the mesh tile they fall into, with paint_particles' key and torch.sort (locality only: one
+    writer per word, the same bits for every sort and every order of the rows); False reads them in the order given;
+    "auto" is False, because the sort measured slower than what it saves."""
+    f, res, boxsize, worder, fill, sort, x, n = _validate_read(field, boxsize, positions, displacement, lattice, worder,
+                                                               fill, sort)
+    if not isinstance(return_stats, (bool, np.bool_)):
+        raise ValueError("return_stats must be a bool, got %r" % (return_stats,))
+    dev = _device_of(f)
+    fd = _to_device(f, dev, (torch.float32,))
+    single = fd.ndim == 3
+    fd = fd.reshape((-1,) + res)
+    if positions is not None:
+        out, stats = _read_mesh(fd, res, boxsize, worder, fill, p=_to_device(x, dev, (torch.float32, torch.float64)),
+                                sort=sort)
+    else:
+        xd = None if x is None else _to_device(x, dev, (torch.float32, torch.float16))
+        out, stats = _read_mesh(fd, res, boxsize, worder, fill, x=xd, n=n)
+        out = out.reshape((-1,) + tuple(n))
+    if single:
+        out = out[0]
+    out = _back(f, out)
+    return (out, {"not_read": int(stats[1])}) if return_stats else out
 
 
 def shot_noise(boxsize, count=None, weights=None):

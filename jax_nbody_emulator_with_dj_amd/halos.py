@@ -16,11 +16,13 @@ Here the displacement stays where `process_box` left it:
     hp = halo_profiles(cat, displacement, 1000.0, profile_edges(0.05, 5.0, 20), overdensity=200.0)   # counts (H, 20), R, N
     vp = halo_velocity_profiles(cat, displacement, velocity, 1000.0, edges)         # v_r, sigma_r, sigma_t (H, nb); cat with CMVelocity
     v12 = halo_pairwise_velocity(cat, 1000.0, np.linspace(1.0, 50.0, 21))           # v12, sigma_r, sigma_t of the halos
+    env = halo_environment(cat, delta_m, 1000.0, smoothing=8.0, threshold=0.2)      # eigenvalues, delta_s, web_type per halo
 
     python -m jax_nbody_emulator_with_dj_amd.halos --displacement_file emu_dis.npy --output_dir out/ [--halo_pk 256]
         [--halo_xi [--xi_rmin 1 --xi_rmax 50 --xi_nbins 20 --xi_log] [--xi_nmu N]]
         [--halo_profiles [--profile_rmin 0.05 --profile_rmax 5 --profile_nbins 20] [--so_overdensity 200 --so_reference mean]]
         [--velocity_file emu_vel.npy [--halo_vprofiles] [--halo_v12]]
+        [--halo_environment 256 [--web_smoothing 8 --web_threshold 0.2]]
 
 Definition (DESIGN.md section 12.5 has the proofs; tests/fof_ref.py restates it in NumPy).  With U = 2^30, particle
 p = (i0 n + i1) n + i2 of the (n, n, n) lattice has the integer coordinates X_c = rint((i_c / n + psi_c / L) U) mod U,
@@ -59,7 +61,8 @@ except Exception:  # pragma: no cover
     torch = None
 
 __all__ = ["fof_halos", "particle_mass", "halo_mass_function", "density_slab", "paint_halos", "halo_bias",
-           "halo_correlation", "halo_profiles", "halo_velocity_profiles", "halo_pairwise_velocity"]
+           "halo_correlation", "halo_profiles", "halo_velocity_profiles", "halo_pairwise_velocity",
+           "halo_environment"]
 
 _U = 1 << 30                    # include/nbe.h, "Halos": coordinate units per box side
 _MIN_N, _MAX_N = 2, 1024        # NBE_FOF_MIN_N, NBE_FOF_MAX_N
@@ -408,6 +411,46 @@ def halo_profiles(cat, matter, boxsize, r_edges, min_length=None, max_length=Non
     return out
 
 
+def halo_environment(cat, delta, boxsize, smoothing, threshold=0.0, worder=1, min_length=None):
+    """Where in the cosmic web every halo of a catalogue sits: the eigenvalues of the tidal tensor of the smoothed matter
+    field and the smoothed density contrast, read at the halo's centre of mass (web.cosmic_web's eigenvalue mesh through
+    density.read_mesh; the environment that assembly-bias studies of a halo catalogue are cut on, which the reference
+    does not have).
+
+    cat, min_length: the halos and their selection as paint_halos.  delta: cubic (n, n, n) float32 matter density contrast
+    of the catalogue's kind.  boxsize, smoothing (a length, or None), threshold (one number): as web.cosmic_web.  worder: the
+    window of the readout; 1 (NGP) reads the voxel that holds the centre, so that web_type is that voxel's type exactly.
+    Returns a dict in the catalogue's kind: eigenvalues (H, 3) float32, lambda_1 >= lambda_2 >= lambda_3 for worder = 1 (an
+    interpolation of each sorted mesh otherwise); delta_s (H,) float32; web_type (H,) uint8, the number of read eigenvalues
+    above the threshold in float32 comparison, 255 for a NaN; Length (H,), and count."""
+    from . import web
+    from .density import _check_worder, _read_mesh
+    keep, count = _select_halos(cat, None, min_length, None, False)
+    d, n, L, sigma, th, _, _, _ = web._validate_web(delta, boxsize, smoothing, threshold, "tidal", None, 1.0, None,
+                                                    "halo_environment")
+    if len(th) != 1:
+        raise ValueError("halo_environment takes one threshold, got %d" % len(th))
+    worder = _check_worder(worder)
+    pos = cat["CMPosition"] if keep is None else cat["CMPosition"][keep]
+    pos = _check_array(pos, "CMPosition")
+    _same_kind(d, pos, "delta", "CMPosition")
+    dev = _device_of(d)
+    with torch.cuda.device(dev):
+        eig, _, _, _, smooth = web._web(_to_device(d, dev, (torch.float32,)), n, L, sigma, th, None, 1.0, None,
+                                        want_smooth=True)
+        field = torch.cat([eig, smooth[None]])
+        del eig, smooth
+        pd = _to_device(pos, dev, (torch.float32, torch.float64))
+        if pd.dtype not in (torch.float32, torch.float64):
+            pd = pd.to(torch.float64)
+        out, _ = _read_mesh(field, (n, n, n), (L, L, L), worder, float("nan"), p=pd.contiguous(), sort=False)
+        e = out[:3]
+        above = (e > float(th[0])).sum(0).to(torch.uint8)
+        wt = torch.where(torch.isnan(e).any(0), torch.full_like(above, web.NO_TYPE), above)
+    return {"eigenvalues": _back(d, out[:3].t().contiguous()), "delta_s": _back(d, out[3].contiguous()),
+            "web_type": _back(d, wt), "Length": cat["Length"] if keep is None else cat["Length"][keep], "count": count}
+
+
 def _select_moving_halos(cat, min_length, max_length, what):
     """_select_halos for a function that reads CMVelocity: (rows mask or None, count)."""
     if isinstance(cat, dict) and "CMPosition" in cat and "CMVelocity" not in cat:
@@ -541,7 +584,7 @@ def build_parser():
                     help="also paint the halos and the matter onto a RES^3 mesh: %s and %s (k, p_hh, p_mm, p_hm, r, bias, "
                          "nmodes, shot_noise, count) inside --output_dir" % (HALO_DELTA_FILE, HALO_PK_FILE))
     ap.add_argument("--mas_worder", type=int, choices=(1, 2, 3, 4), default=2,
-                    help="with --halo_pk: 1 NGP, 2 CIC, 3 TSC, 4 PCS (default: 2)")
+                    help="with --halo_pk or --halo_environment: 1 NGP, 2 CIC, 3 TSC, 4 PCS (default: 2)")
     ap.add_argument("--halo_weight", choices=sorted(HALO_WEIGHT_NAMES), default="number",
                     help="with --halo_pk: count halos, or weight each by its particle count (default: number)")
     add_xi_arguments(ap)
@@ -550,6 +593,7 @@ def build_parser():
                     help="the velocity of the same particles, (3, N, N, N) or (N, N, N, 3) (.npy): the catalogue's CMVelocity, "
                          "for --halo_vprofiles and --halo_v12")
     add_velocity_arguments(ap)
+    add_environment_arguments(ap)
     return ap
 
 
@@ -732,6 +776,80 @@ def halo_v12_arrays(cat, boxsize, r_edges):
     return arrs
 
 
+HALO_ENVIRONMENT_FILE = "halo_environment.npz"
+
+
+def add_environment_arguments(ap, suppress=False, scan=False):
+    """The options --halo_environment, --web_smoothing and --web_threshold, shared with run_emulator as add_xi_arguments's
+    are; there --web_threshold takes several values for --cosmic_web (scan), of which --halo_environment reads the first."""
+    value = argparse.SUPPRESS if suppress else None
+    ap.add_argument("--halo_environment", type=int, default=value, metavar="RES",
+                    help="also paint the matter onto a RES^3 mesh (--mas_worder) and read the tidal tensor's eigenvalues, the "
+                         "smoothed density and the T-web type at every halo: %s (eigenvalues, delta_s, web_type, Length, count, "
+                         "smoothing, threshold) inside the output directory" % HALO_ENVIRONMENT_FILE)
+    ap.add_argument("--web_smoothing", type=float, default=value, metavar="R",
+                    help="the Gaussian smoothing length of the web in Mpc/h (default: two cells of its mesh)")
+    if scan:
+        ap.add_argument("--web_threshold", type=float, nargs="+", default=value, metavar="T",
+                        help="the eigenvalue threshold(s) of the web, up to 64 (default: 0)")
+    else:
+        ap.add_argument("--web_threshold", type=float, default=value, metavar="T",
+                        help="the eigenvalue threshold of the web (default: 0)")
+
+
+def web_settings(args, boxsize, res, die):
+    """(smoothing, thresholds) of a parsed command line for a web on a res^3 mesh: --web_smoothing or two cells, and
+    --web_threshold as a list (default [0.0]); `die(message)` for values web.cosmic_web would refuse."""
+    smoothing = getattr(args, "web_smoothing", None)
+    smoothing = 2.0 * boxsize / res if smoothing is None else float(smoothing)
+    if not (smoothing > 0 and math.isfinite(smoothing)):
+        die("--web_smoothing must be positive, got %r" % smoothing)
+    th = getattr(args, "web_threshold", None)
+    th = [0.0] if th is None else [float(v) for v in (th if isinstance(th, (list, tuple)) else [th])]
+    if not 1 <= len(th) <= 64 or not all(math.isfinite(v) and abs(v) < 3.0e38 for v in th):
+        die("--web_threshold takes 1 .. 64 finite values, got %r" % th)
+    return smoothing, th
+
+
+def environment_options(args, boxsize, die, worder=2):
+    """The settings of --halo_environment as a dict (res, worder, smoothing, threshold), or None without it; `die(message)`
+    for --web_smoothing / --web_threshold without a consumer (`args.cosmic_web` is run_emulator's other one)."""
+    res = getattr(args, "halo_environment", None)
+    if res is None:
+        if not getattr(args, "cosmic_web", False):
+            for name in ("web_smoothing", "web_threshold"):
+                if getattr(args, name, None) is not None:
+                    die("--%s needs --halo_environment%s" % (name, " or --cosmic_web" if hasattr(args, "ndiv") else ""))
+        return None
+    if not 2 <= res <= 2048:
+        die("--halo_environment must be in 2 .. 2048, got %d" % res)
+    smoothing, th = web_settings(args, boxsize, res, die)
+    return dict(res=int(res), worder=int(worder), smoothing=smoothing, threshold=th[0])
+
+
+def halo_environment_arrays(cat, disp, boxsize, env):
+    """The arrays of halo_environment.npz for a catalogue and the displacement it was found in: the matter painted onto
+    env's mesh (density.paint_density, deconvolved), halo_environment's eigenvalues, delta_s, web_type (NGP readout), Length
+    and count, with smoothing and threshold -- or None for a catalogue without a halo."""
+    if int(cat["Length"].shape[0]) == 0:
+        return None
+    from .density import paint_density
+    delta = paint_density(disp, boxsize=boxsize, res=env["res"], worder=env["worder"], deconvolve=True)
+    out = halo_environment(cat, delta, boxsize, env["smoothing"], threshold=env["threshold"], worder=1)
+    to_np = lambda a: a.cpu().numpy() if _is_torch(a) else np.asarray(a)
+    return dict(eigenvalues=to_np(out["eigenvalues"]), delta_s=to_np(out["delta_s"]), web_type=to_np(out["web_type"]),
+                Length=to_np(out["Length"]).astype(np.int64), count=np.int64(out["count"]),
+                smoothing=np.float64(env["smoothing"]), threshold=np.float32(env["threshold"]))
+
+
+def save_halo_environment(out_dir, arrs):
+    """Write halo_environment.npz, or print the one line that says why not (None for no halo)."""
+    if arrs is None:
+        print("no halo in the catalogue: %s is not written" % HALO_ENVIRONMENT_FILE)
+        return
+    np.savez(os.path.join(str(out_dir), HALO_ENVIRONMENT_FILE), **arrs)
+
+
 def save_halo_velocity(out_dir, name, arrs):
     """Write halo_vprofiles.npz or halo_v12.npz (`name`), or print the one line that says why not (None for no halo)."""
     if arrs is None:
@@ -772,6 +890,7 @@ def main(argv=None):
     vmom = velocity_moment_options(a, a.boxsize, a.velocity_file is not None, sys.exit)
     if a.velocity_file is not None and vmom is None:
         sys.exit("--velocity_file needs --halo_vprofiles or --halo_v12")
+    env = environment_options(a, a.boxsize, sys.exit, a.mas_worder)
     disp = load_displacement(a.displacement_file)
     vel = None
     if vmom is not None:
@@ -801,6 +920,8 @@ def main(argv=None):
         save_halo_velocity(a.output_dir, HALO_VPROFILES_FILE, halo_vprofile_arrays(cat, disp, vel, a.boxsize, vmom["vprofiles"]))
     if vmom is not None and vmom["v12"] is not None:
         save_halo_velocity(a.output_dir, HALO_V12_FILE, halo_v12_arrays(cat, a.boxsize, vmom["v12"]))
+    if env is not None:
+        save_halo_environment(a.output_dir, halo_environment_arrays(cat, disp, a.boxsize, env))
 
 
 if __name__ == "__main__":

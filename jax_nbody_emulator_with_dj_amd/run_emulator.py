@@ -52,7 +52,13 @@ reference, count; the spherical-overdensity radii and masses at the box's redshi
 writes <output_dir>/halo_vprofiles.npz (halos.halo_velocity_profiles in the shells of --profile_*: r_edges, r_mid, counts,
 sums, exponent, v_r, sigma_r, sigma_t, Length, count) and `--halo_v12` <output_dir>/halo_v12.npz
 (halos.halo_pairwise_velocity in the bins of --xi_*: r_edges, r_mid, npairs, sums, exponent, v12, sigma_r, sigma_t, count),
-the catalogue's CMVelocity coming from the emulated velocity; a box without a halo writes none of these and says so. `--xcorr FILE` (with --density_res) writes <output_dir>/emu_xcorr.npz, density.cross_correlation of
+the catalogue's CMVelocity coming from the emulated velocity; a box without a halo writes none of these and says so.  With `--fof`, `--halo_environment RES` paints the matter onto a
+RES^3 mesh (`--mas_worder`, deconvolved) and writes <output_dir>/halo_environment.npz (halos.halo_environment with the NGP
+readout: eigenvalues, delta_s, web_type, Length, count, smoothing, threshold).  With `--density_res`, `--cosmic_web` writes
+the T-web of emu_delta (web.cosmic_web with mass = emu_delta): <output_dir>/emu_web_type.npy (uint8, the first threshold)
+and <output_dir>/emu_web.npz (thresholds, counts, volume_fraction, mass_fraction, smoothing); `--web_smoothing R` is the
+Gaussian length in Mpc/h (default: two cells of the mesh) and `--web_threshold T [T ...]` the eigenvalue thresholds (default
+0; --halo_environment reads the first).  `--xcorr FILE` (with --density_res) writes <output_dir>/emu_xcorr.npz, density.cross_correlation of
 emu_delta against the saved (N, N, N) field FILE (k, p_aa, p_bb, p_ab, nmodes, r, transfer, bias): the reference's
 emulator-against-target check (scripts/utils.py:1451-1470).
 
@@ -234,6 +240,13 @@ def build_parser():
     add_profile_arguments(ap, suppress=True)                 # --halo_profiles, --profile_rmin / _rmax / _nbins, --so_overdensity / _reference
     from .halos import add_velocity_arguments
     add_velocity_arguments(ap, suppress=True)                # --halo_vprofiles, --halo_v12
+    from .halos import add_environment_arguments
+    add_environment_arguments(ap, suppress=True, scan=True)  # --halo_environment, --web_smoothing, --web_threshold
+    ap.add_argument('--cosmic_web', action='store_true', default=argparse.SUPPRESS,
+                    help='With --density_res: also write the T-web of the density field (Gaussian smoothing --web_smoothing, '
+                         'thresholds --web_threshold): <output_dir>/emu_web_type.npy (uint8: 0 void, 1 sheet, 2 filament, '
+                         '3 knot under the first threshold) and <output_dir>/emu_web.npz (thresholds, counts, '
+                         'volume_fraction, mass_fraction, smoothing)')
     ap.add_argument('--xcorr', type=Path, metavar='FILE', default=argparse.SUPPRESS,
                     help='With --density_res: also write r(k), transfer and bias of emu_delta against the saved (N, N, N) '
                          'float32 field FILE to <output_dir>/emu_xcorr.npz')
@@ -402,6 +415,34 @@ def halo_velocity_options(args):
     return vmom
 
 
+def halo_environment_options(args):
+    """The settings of --halo_environment (halos.environment_options: res, worder, smoothing, threshold), or None without
+    it.  It needs --fof."""
+    from .halos import environment_options
+    env = environment_options(args, float(getattr(args, 'boxsize', 1000.0)), _die, int(getattr(args, 'mas_worder', 2)))
+    if env is not None and not getattr(args, 'fof', False):
+        _die('--halo_environment needs --fof')
+    return env
+
+
+WEB_KEYS = ('thresholds', 'counts', 'volume_fraction', 'mass_fraction', 'smoothing')
+
+
+def cosmic_web_options(args):
+    """The settings of --cosmic_web (smoothing, thresholds), or None without it (read apart from density_options, whose
+    dict they leave as it was).  It needs --density_res, and a mesh web.cosmic_web takes."""
+    if not getattr(args, 'cosmic_web', False):
+        return None
+    res = getattr(args, 'density_res', None)
+    if res is None:
+        _die('--cosmic_web needs --density_res')
+    if not 2 <= res <= 2048:
+        _die(f'--cosmic_web needs a mesh of 2 .. 2048 cells a side, got {res}')
+    from .halos import web_settings
+    smoothing, thresholds = web_settings(args, float(getattr(args, 'boxsize', 1000.0)), int(res), _die)
+    return dict(smoothing=smoothing, thresholds=thresholds)
+
+
 def xcorr_option(args):
     """The (N, N, N) float32 field of --xcorr, or None without it.  It needs --density_res and that mesh size."""
     path = getattr(args, 'xcorr', None)
@@ -417,14 +458,15 @@ def xcorr_option(args):
     return np.ascontiguousarray(field, dtype=np.float32)
 
 
-def fof_catalog(disp, fof, Om, halo=None, xi=None, profiles=None, z=0.0, vel=None, vmom=None):
+def fof_catalog(disp, fof, Om, halo=None, xi=None, profiles=None, z=0.0, vel=None, vmom=None, env=None):
     """The arrays of fof_catalog.npz for the device displacement of one box, as {'fof': arrays}; with the settings of
     --halo_pk also 'halo': halos.halo_spectra's result (None for a box without a halo); with those of --halo_xi also
     'halo_xi': halos.halo_xi_arrays's; with those of --halo_profiles also 'halo_profiles': halos.halo_profile_arrays's at
     redshift z; with those of --halo_vprofiles / --halo_v12 (vmom, and the device velocity vel, which then gives the
-    catalogue its CMVelocity) also 'halo_vprofiles': halos.halo_vprofile_arrays's and 'halo_v12': halos.halo_v12_arrays's."""
-    from .halos import (catalog_arrays, fof_halos, halo_profile_arrays, halo_spectra, halo_v12_arrays, halo_vprofile_arrays,
-                        halo_xi_arrays)
+    catalogue its CMVelocity) also 'halo_vprofiles': halos.halo_vprofile_arrays's and 'halo_v12': halos.halo_v12_arrays's;
+    with those of --halo_environment (env) also 'halo_environment': halos.halo_environment_arrays's."""
+    from .halos import (catalog_arrays, fof_halos, halo_environment_arrays, halo_profile_arrays, halo_spectra,
+                        halo_v12_arrays, halo_vprofile_arrays, halo_xi_arrays)
     cat = fof_halos(disp, boxsize=fof['boxsize'], linking_length=fof['linking_length'], nmin=fof['nmin'],
                     velocity=vel if vmom is not None else None)
     out = {'fof': catalog_arrays(cat, int(disp.shape[1]), fof['boxsize'], Om, fof['linking_length'], False, fof['nmin'])}
@@ -439,6 +481,8 @@ def fof_catalog(disp, fof, Om, halo=None, xi=None, profiles=None, z=0.0, vel=Non
         out['halo_vprofiles'] = halo_vprofile_arrays(cat, disp, vel, fof['boxsize'], vmom['vprofiles'])
     if vmom is not None and vmom['v12'] is not None:
         out['halo_v12'] = halo_v12_arrays(cat, fof['boxsize'], vmom['v12'])
+    if env is not None:
+        out['halo_environment'] = halo_environment_arrays(cat, disp, fof['boxsize'], env)
     return out
 
 
@@ -498,6 +542,8 @@ def run(args):
     halo_xi = halo_xi_options(args)
     halo_prof = halo_profile_options(args)
     halo_vmom = halo_velocity_options(args)
+    halo_env = halo_environment_options(args)
+    web = cosmic_web_options(args)
     target = xcorr_option(args)
     if bispec:
         for k1, k2 in BISPECTRUM_CONFIGS:                    # density.bispectrum's closure condition, before any work
@@ -509,13 +555,15 @@ def run(args):
               f"boxsize {dens['boxsize']}, P(k) {dens['pk']}" + (", Minkowski functionals" if mink else "")
               + (", bispectrum" if bispec else "") + (", one-point statistics" if onepoint else "")
               + (", velocity mesh" if paint_vel else "") + (f", redshift space along axis {rsd}" if rsd is not None else "")
-              + (", multipoles" if multipoles else "") + (f", {wedges} wedges" if wedges is not None else ""))
+              + (", multipoles" if multipoles else "") + (f", {wedges} wedges" if wedges is not None else "")
+              + (f", T-web smoothed over {web['smoothing']:g}" if web is not None else ""))
     if fof is not None:
         print(f"  Halos: FoF b = {fof['linking_length']}, nmin {fof['nmin']}, boxsize {fof['boxsize']}"
               + (f", halo spectra on a {halo['res']}^3 mesh" if halo is not None else "")
               + (f", halo pairs in {len(halo_xi['r_edges']) - 1} bins" if halo_xi is not None else "")
               + (f", halo profiles in {len(halo_prof['r_edges']) - 1} bins" if halo_prof is not None else "")
-              + (", halo velocity moments" if halo_vmom is not None else ""))
+              + (", halo velocity moments" if halo_vmom is not None else "")
+              + (f", halo environment on a {halo_env['res']}^3 mesh" if halo_env is not None else ""))
     print()
 
     shape = None
@@ -564,6 +612,9 @@ def run(args):
             if extra is not None and key in extra:
                 from .halos import save_halo_velocity
                 save_halo_velocity(out_dir, key + '.npz', extra[key])
+        if extra is not None and 'halo_environment' in extra:
+            from .halos import save_halo_environment
+            save_halo_environment(out_dir, extra['halo_environment'])
         if extra is not None and 'delta' in extra:
             np.save(out_dir / 'emu_delta.npy', extra['delta'])
             if 'pk' in extra:
@@ -590,6 +641,9 @@ def run(args):
                 np.savez(out_dir / 'emu_pk_rsd_wedges.npz', **extra['pk_rsd_wedges'])
             if 'xcorr' in extra:
                 np.savez(out_dir / 'emu_xcorr.npz', **extra['xcorr'])
+            if 'web' in extra:
+                np.save(out_dir / 'emu_web_type.npy', extra['web']['types'])
+                np.savez(out_dir / 'emu_web.npz', **{key: extra['web'][key] for key in WEB_KEYS})
 
     def with_density(dis_in, z, Om):
         """process_box on the device, the density field of its float32 displacement, host copies of the fields."""
@@ -599,7 +653,8 @@ def run(args):
         result = emu.process_box(box_t, z=z, Om=Om, show_progress=not args.quiet)
         disp = result[0] if args.vel else result
         extra = {} if fof is None else fof_catalog(disp, fof, Om, halo, halo_xi, halo_prof, float(z),
-                                                   vel=result[1] if halo_vmom is not None else None, vmom=halo_vmom)
+                                                   vel=result[1] if halo_vmom is not None else None, vmom=halo_vmom,
+                                                   env=halo_env)
         out_dt = np.dtype(args.output_precision)
         if dens is None:
             host = tuple(t.cpu().numpy().astype(out_dt, copy=False) for t in (result if args.vel else (result,)))
@@ -616,6 +671,10 @@ def run(args):
             extra['mf'] = minkowski_functionals(delta, boxsize=dens['boxsize'])
         if bispec or onepoint:
             extra['bk'], extra['onepoint'] = density_summaries(delta, dens, bispec, onepoint)
+        if web is not None:
+            from .web import cosmic_web
+            w = cosmic_web(delta, dens['boxsize'], web['smoothing'], threshold=web['thresholds'], mass=delta)
+            extra['web'] = dict({key: w[key] for key in WEB_KEYS}, types=w['types'].cpu().numpy())
         if paint_vel or rsd is not None:
             extra.update(velocity_fields(disp, result[1], dens, paint_vel, rsd, z, Om, multipoles, wedges))
         host = tuple(t.cpu().numpy().astype(out_dt, copy=False) for t in (result if args.vel else (result,)))
